@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: audio samples / second of the FastSpeech2 + HiFi-GAN hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: set up, W warm-up steps, exactly K timed steps, one JSON line.  `--full`
+adds everything else this file measures: the per-class kernel table and `roofline` (two profiled steps, then HIP events on the
+dominant class inside the timed region), the extra keys below and the CPU baseline.  `--dump-outputs DIR` writes what the last timed
+step returned (int16 PCM and mel lengths; config 4: every utterance's PCM in input order) as DIR/<name>.npy in float32 / float64;
+the inputs depend on the arguments only, so two builds can be compared output for output.
 
 N > 1: one rank per GPU over RCCL.  Under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process IS
 one rank; called plainly (`python bench.py --gpus 8`) it starts N fresh rank processes itself -- before torch is imported or the GPU
@@ -20,13 +26,13 @@ What `value` is:
   * timed region: SURVEY.md 8(d)'s boundary, ids in (pinned) host memory -> int16 PCM in (pinned) host memory, exactly --steps steps
     between two barrier + synchronize brackets, MAX over ranks; `ms_per_step` = that time / steps, `ms_per_step_median` the median
     of the per-step times;
-  * extra keys carry the rest: `hbm_resident` (same steps with ids / PCM resident in HBM), `split_precision_mode` (the bf16x3 fast
-    mode: its own ms_per_step, roofline and measured error against the reference fixtures), `latency_b1_ms`, `parity`.
+  * with --full, extra keys carry the rest: `hbm_resident` (same steps with ids / PCM resident in HBM), `split_precision_mode` (the
+    bf16x3 fast mode: its own ms_per_step, roofline and measured error against the reference fixtures), `latency_b1_ms`, `parity`.
 
 Multi-GPU: utterances shard across ranks with no data-path collective ("scaling": "weak", 32 utterances per GPU); RCCL is used once,
 to broadcast the packed weight blob from rank 0 (`rccl_ranks`, `weight_bcast_ms`, `weight_blob_bytes` in the JSON line).
 
-Other BASELINE.json configurations, each under this run's clock as an extra key (and as `--workload` for a line of its own):
+Other BASELINE.json configurations, each under a --full run's clock as an extra key (and as `--workload` for a line of its own):
   `c3_mixed`     config 3: B = 32 utterances of 40..200 phonemes (padded to 200, T = 1200), ragged compute, VALID samples/s, own roofline;
   `c4_sharded`   config 4: 256 utterances (config 3's lengths x 8) through e2e_tts_amd.dist.synthesize_sharded -- snake-dealt over the
                  ranks, padded batches of 32, PCM gathered on rank 0 in input order -- with the per-rank balance (strong scaling);
@@ -382,6 +388,37 @@ def fixture_errors(eng, hop):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 * 10**6   # under 64 MB with the .npy headers
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each array as DIR/<name>.npy, integers widened exactly (float32 up to 2^24, float64 beyond).  Over
+    DUMP_BUDGET_BYTES the largest arrays are cut down to a fixed sample (PCG64(0), sorted flat indices, the same in every run for the same
+    shapes), written with its indices as <name>_sample_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.dtype.kind in "iu" and a.dtype.itemsize > 2:
+            exact32 = a.size == 0 or max(abs(int(a.min())), abs(int(a.max()))) <= 1 << 24
+        else:
+            exact32 = a.dtype.kind in "iu" or (a.dtype.kind == "f" and a.dtype.itemsize <= 4)
+        conv[name] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    for name in sorted(conv, key=lambda n: -conv[n].nbytes):
+        if total <= DUMP_BUDGET_BYTES:
+            break
+        a = conv[name].reshape(-1)
+        keep = max(0, (DUMP_BUDGET_BYTES - (total - a.nbytes)) // (a.itemsize + 8))   # the sample + its float64 indices fit
+        idx = np.unique(np.random.Generator(np.random.PCG64(0)).integers(0, a.size, size=keep)) if keep else np.zeros(0, np.int64)
+        total += idx.size * (a.itemsize + 8) - a.nbytes
+        conv[name] = a[idx]
+        conv[name + "_sample_index"] = idx.astype(np.float64)
+    for name, a in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step: {', '.join(f'{n} {a.shape}' for n, a in conv.items())} -> {dirname} ({total / 1e6:.1f} MB)")
+
+
 def mixed_lengths(n=BATCH):
     """lengths linspace(40, 200, 32) rounded, shuffled with PCG64(2)."""
     lens = np.round(np.linspace(40, 200, n)).astype(np.int64)
@@ -403,9 +440,15 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the per-class kernel table and `roofline` (HIP events in the timed "
+                         "region), the extra keys and the CPU baseline.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (int16 PCM, mel lengths) as DIR/<name>.npy in "
+                         "float32 / float64, at most 64 MB in all (a fixed, seeded sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys (hbm_resident / split_precision_mode / latency_b1_ms / parity / c3_mixed / c4_sharded / c5_longform)")
+                    help="with --full: skip the extra keys (hbm_resident / split_precision_mode / latency_b1_ms / parity / c3_mixed / c4_sharded / c5_longform)")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--workload", choices=("fixed", "mixed", "c4"), default="fixed",
                     help="fixed: the headline B=32 x L=128 batch; mixed: BASELINE config 3 (32 utterances of 40..200 phonemes, padded to 200 "
@@ -604,14 +647,18 @@ def main():
             assert int(self.mel_lens.sum()) == self.valid_frames and int(self.mel_lens.max()) == self.T
 
     def run_c4(n_utt, nsteps, nwarm):
-        """BASELINE config 4 through dist.synthesize_sharded; returns (elapsed max over ranks, per-step times, valid samples, stats)."""
+        """BASELINE config 4 through dist.synthesize_sharded; returns (elapsed max over ranks, per-step times, valid samples, stats,
+        the last timed pass's PCM list (rank 0))."""
         from e2e_tts_amd import dist as edist
         lists = c4_id_lists(n_utt)
         st = {}
-        fn = lambda: edist.synthesize_sharded(eng, lists, speaker=1, batch_size=BATCH, hop_length=hop, device=coll_dev if dist is not None else None, stats=st)
-        out = None
+        last = [None]
+
+        def fn():
+            last[0] = edist.synthesize_sharded(eng, lists, speaker=1, batch_size=BATCH, hop_length=hop, device=coll_dev if dist is not None else None, stats=st)
         for _ in range(max(nwarm, 1)):
-            out = fn()
+            fn()
+        out = last[0]
         if rank == 0:   # input order and exact lengths (6 frames per phoneme with the "fixed" weights)
             assert len(out) == n_utt and all(o.dtype == np.int16 and o.size == len(l) * FRAMES_PER_PHONEME * hop for o, l in zip(out, lists))
             if stub:
@@ -619,7 +666,7 @@ def main():
         el, per = timed(fn, nsteps)
         el = max_over_ranks(el)
         samples = sum(len(l) for l in lists) * FRAMES_PER_PHONEME * hop
-        return el, per, samples, st
+        return el, per, samples, st, last[0]
 
     def c4_record(el, per, samples, st, nsteps, n_utt):
         spr = st.get("samples_per_rank") or []
@@ -634,41 +681,53 @@ def main():
     fp32 = args.precision == "fp32"
     c4 = args.workload == "c4"
     if c4:
-        elapsed, per_step, job_samples, c4_stats = run_c4(args.utterances, args.steps, args.warmup)
+        elapsed, per_step, job_samples, c4_stats, last_out = run_c4(args.utterances, args.steps, args.warmup)
         value = job_samples * args.steps / elapsed
         B, L, T = BATCH, 200, 1200
         valid_frames = job_samples // hop
         ids_source = "synthetic ids, PCG64"
-        # class table / dominant kernel of this rank's share (one more pass; not in the timed region)
-        from e2e_tts_amd import dist as edist
-        eng.profile_filter(None)
-        eng.profile_enable(True)
-        edist.synthesize_sharded(eng, c4_id_lists(args.utterances), speaker=1, batch_size=BATCH, hop_length=hop, device=coll_dev if dist is not None else None)
-        sync()
-        stats_all = eng.profile_read()
-        eng.profile_enable(False)
-        dom = max(stats_all, key=lambda st: st["ms"])
-        prof_steps = 1
+        if rank == 0 and args.dump_outputs:
+            # the utterances' PCM back to back in input order, and where each one starts
+            lengths = np.array([o.size for o in last_out], np.int64)
+            dump_outputs(args.dump_outputs, {"pcm": np.concatenate(last_out),
+                                             "pcm_offsets": np.concatenate([[0], np.cumsum(lengths)[:-1]]), "pcm_lengths": lengths})
+        if args.full:
+            # class table / dominant kernel of this rank's share (one more pass; not in the timed region)
+            from e2e_tts_amd import dist as edist
+            eng.profile_filter(None)
+            eng.profile_enable(True)
+            edist.synthesize_sharded(eng, c4_id_lists(args.utterances), speaker=1, batch_size=BATCH, hop_length=hop, device=coll_dev if dist is not None else None)
+            sync()
+            stats_all = eng.profile_read()
+            eng.profile_enable(False)
+            dom = max(stats_all, key=lambda st: st["ms"])
+            prof_steps = 1
     else:
         ids_np, lens_np, ids_source = batch_workload(args.workload, args.batch, roll=rank)
         hb = HostBatch(ids_np, lens_np)
         B, L, T, valid_frames = hb.B, hb.L, hb.T, hb.valid_frames
         hb.warm(args.warmup)
-        elapsed, per_step, stats_all, dom = measure(hb.step, args.steps)
+        if args.full:
+            elapsed, per_step, stats_all, dom = measure(hb.step, args.steps)
+        else:
+            elapsed, per_step = timed(hb.step, args.steps)
         elapsed = max_over_ranks(elapsed)
         value = world * valid_frames * hop * args.steps / elapsed   # valid samples only (padding excluded)
         prof_steps = 2
+        if rank == 0 and args.dump_outputs:   # before any extra reuses the buffers
+            dump_outputs(args.dump_outputs, {"pcm": hb.pcm, "mel_lens": hb.mel_lens})
 
     if rank == 0:
         try:
             traffic_json = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json")))
         except (OSError, ValueError):
             traffic_json = {}
-        class_table(stats_all, prof_steps, "")
-        roofline = roofline_of(dom, args.steps if not c4 else prof_steps, traffic_json)
-        conv = [st for st in stats_all if st["name"].startswith(CONV_CLASSES)]
-        roofline["all_conv_tflops"] = round(sum(st["flops"] for st in conv) / max(sum(st["ms"] for st in conv) * 1e-3, 1e-9) / 1e12, 3)
-        roofline["kernel_ms_per_step"] = round(sum(st["ms"] for st in stats_all) / prof_steps, 3)
+        if args.full:
+            class_table(stats_all, prof_steps, "")
+            roofline = roofline_of(dom, args.steps if not c4 else prof_steps, traffic_json)
+            conv = [st for st in stats_all if st["name"].startswith(CONV_CLASSES)]
+            roofline["all_conv_tflops"] = round(sum(st["flops"] for st in conv) / max(sum(st["ms"] for st in conv) * 1e-3, 1e-9) / 1e12, 3)
+            roofline["kernel_ms_per_step"] = round(sum(st["ms"] for st in stats_all) / prof_steps, 3)
         blocks_note = ("; default model_config (6+6 FFT blocks H=384, HiFi-GAN V1), random-init weights" if args.blocks == "transformer"
                        else "; model_config with block_type=conformer (6+6 Conformer blocks H=384, 8 heads, k31; HiFi-GAN V1), random-init weights")
         if c4:
@@ -692,18 +751,19 @@ def main():
             "real_time_factor": value / dims.sample_rate,
             "ms_per_step_median": statistics.median(per_step) * 1e3,
             "ms_per_step_min_max": [min(per_step) * 1e3, max(per_step) * 1e3],
-            "roofline": roofline,
             "rccl_ranks": (dist.get_world_size() if (dist is not None and backend == "nccl") else (0 if dist is not None else 1)),
             "collective_backend": backend, "weight_bcast_ms": weight_bcast_ms, "weight_blob_bytes": blob_bytes,
         }
+        if args.full:
+            out["roofline"] = roofline
         if c4:
             out["c4_sharded"] = c4_record(elapsed, per_step, job_samples, c4_stats, args.steps, args.utterances)
-    extras = not args.no_extras and not c4 and args.workload == "fixed" and args.batch == BATCH
+    extras = args.full and not args.no_extras and not c4 and args.workload == "fixed" and args.batch == BATCH
     # ---- config 4 beside the headline, at every N (every rank takes part; rank 0 reports)
     if extras:
         k4 = 2 if not stub else 1
         try:   # an extra must not take the headline line down with it (an error raised on every rank alike leaves the ranks in step)
-            el4, per4, s4, st4 = run_c4(256, k4, 1)
+            el4, per4, s4, st4, _ = run_c4(256, k4, 1)
             if rank == 0:
                 out["c4_sharded"] = c4_record(el4, per4, s4, st4, k4, 256)
                 log(f"[bench] c4_sharded: {out['c4_sharded']['samples_per_s']:,.0f} valid samples/s, {out['c4_sharded']['ms_per_pass']:.1f} ms per pass of 256 "
@@ -789,7 +849,7 @@ def main():
             except Exception as ex:   # an extra must not take the headline line down with it
                 out["c5_longform"] = {"error": repr(ex)}
                 log(f"[bench] c5_longform failed: {ex!r}")
-        if world == 1 and not args.no_cpu_baseline and not stub and not c4:
+        if world == 1 and args.full and not args.no_cpu_baseline and not stub and not c4:
             out["cpu_baseline"] = cpu_baseline(cfg, stats, ac_state, voc_state, ids_np)
             log(f"[bench] cpu_baseline: {out['cpu_baseline']}")
         print(json.dumps(out), flush=True)

@@ -157,7 +157,7 @@ def test_bench_multi_rank_branch_contract_world2():
     import subprocess
     env = dict(os.environ, E2ETTS_BENCH_STUB="1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"]
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -192,7 +192,7 @@ def test_bench_called_plainly_with_gpus_2_launches_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher in the command.  The parent starts two fresh rank processes
     before importing torch, relays rank 0's one JSON line and exits 0; the line carries the headline keys for n_gpus = 2 and the
     config-4 record (256 utterances sharded over both ranks) beside them.  Stand-in engine, gloo: the harness, not a measurement."""
-    d = _run_bench_plainly("--gpus", "2", "--steps", "3", "--warmup", "1")
+    d = _run_bench_plainly("--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
     assert d["data"] == "stub" and d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 64 and d["collective_backend"] == "gloo" and d["rccl_ranks"] == 0
     assert d["weight_bcast_ms"] > 0
@@ -225,7 +225,7 @@ def test_bench_rank_failure_is_reported_by_the_launcher():
 def test_bench_called_plainly_with_gpus_8_under_gloo():
     """The N = 8 shape of the driver's scaling run, rehearsed here with the stand-in engine over gloo (the driver's own N = 8 run needs an
     8-GPU node): eight self-launched ranks, one JSON line, whole-job aggregate over all eight, the config-4 list dealt evenly."""
-    d = _run_bench_plainly("--gpus", "8", "--steps", "2", "--warmup", "1")
+    d = _run_bench_plainly("--gpus", "8", "--steps", "2", "--warmup", "1", "--full")
     assert d["data"] == "stub" and d["n_gpus"] == 8 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 256 and d["config"]["parallelism"] == "utterance-sharded x8"
     samples = 8 * 32 * 768 * 256

@@ -5,10 +5,12 @@
 # BENCH_ARGS (env): extra bench.py arguments, e.g. "--precision bf16x3 --batch 1 --steps 20".
 # Runs the variant list twice and prints ms/step of the matching classes and of the whole step.  Restores the LAST variant at the end.
 set -e
+tmp=$(mktemp -d)   # the bench line and its class table of the current variant
+trap 'rm -rf "$tmp"' EXIT
 pat=${1:-resblock_pair|conv_x3_128x128}
 vars=${VARIANTS:-old new}
 for v in $vars $vars; do
   cp tools/bin/lib_$v.so e2e_tts_amd/lib/libe2etts_hip.so
-  python3 bench.py --no-cpu-baseline --no-extras $BENCH_ARGS > gpurun_out/ab.json 2> gpurun_out/ab.log
-  echo "$v $(grep -E "\[bench\] ($pat)" gpurun_out/ab.log | awk '{printf "%s=%s ", $2, $6}') step=$(python3 -c 'import json;print(round(json.load(open("gpurun_out/ab.json"))["ms_per_step"],3))')"
+  python3 bench.py --full --no-cpu-baseline --no-extras $BENCH_ARGS > "$tmp/ab.json" 2> "$tmp/ab.log"
+  echo "$v $(grep -E "\[bench\] ($pat)" "$tmp/ab.log" | awk '{printf "%s=%s ", $2, $6}') step=$(python3 -c "import json,sys;print(round(json.load(open(sys.argv[1]))['ms_per_step'],3))" "$tmp/ab.json")"
 done

@@ -22,7 +22,7 @@ export TMPDIR=/tmp
 want() { [ "$only" = all ] || [ "$only" = "$1" ]; }
 trace() {  # name, then the bench.py arguments
   local name=$1; shift
-  rocprofv3 --kernel-trace --stats -d "$out/trace_$name" --output-format csv -- python3 bench.py --no-cpu-baseline --no-extras "$@" > "$out/${name}_under_rocprof.json" 2> "$out/trace_$name.err"
+  rocprofv3 --kernel-trace --stats -d "$out/trace_$name" --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-extras "$@" > "$out/${name}_under_rocprof.json" 2> "$out/trace_$name.err"
   cp "$(find "$out/trace_$name" -name '*kernel_stats.csv' | head -1)" "$out/${name}_kernel_stats.csv"
   grep "\[bench\]" "$out/trace_$name.err" > "$out/${name}_classes.txt" || true
   if [ "${name#b1_}" != "$name" ]; then   # the B = 1 path: order and overlap of ~190 short launches
@@ -41,7 +41,7 @@ pmc() {  # directory name under $out, then the bench.py arguments
   done
 }
 if want headline; then
-  python3 bench.py --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
+  python3 bench.py --full --steps 20 --warmup 5 > "$out/bench.json" 2> "$out/bench.err"
   echo "[profile] bench done"
   trace fp32
   pmc pmc_headline/fp32 --precision fp32
