@@ -19,6 +19,9 @@ LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_hip.so")
 # library only when E2ETTS_TEST_HOOKS=1 is in the environment (tests/conftest.py sets it); nothing in the product path asks for it.
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_hip_test.so")
 ABI_VERSION = 4   # E2ETTS_ABI_VERSION of the include/e2etts.h this binding mirrors
+# E2ETTS_PRECISION_* of include/e2etts.h: 'bf16' and 'bf16_act' are vocoder-only ('bf16': plain bf16 operands, the long-form streaming
+# config's arithmetic; 'bf16_act': every activation bf16, rounded where the reference's module run with .bfloat16() rounds)
+PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, "bf16_act": 3}
 
 E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM, E_KEY = 0, -1, -2, -3, -4, -5
 
@@ -396,10 +399,10 @@ class Engine:
     def set_precision(self, vocoder: str = "fp32", decoder: Optional[str] = None):
         """'fp32' (exact fp32 MFMA: the engine's default and the reference's arithmetic) or 'bf16x3' (split-precision bf16 MFMA: the
         opt-in fast mode, PCM within 1 LSB of the reference's) for the vocoder and for the decoder + mel_linear + postnet (defaults
-        to the vocoder's choice).  Encoder / variance adaptor: always fp32."""
-        modes = {"fp32": 0, "bf16x3": 1, "bf16": 2}   # 'bf16' (plain, vocoder only) is the long-form streaming config's arithmetic
-        dec = decoder if decoder is not None else ("bf16x3" if vocoder == "bf16" else vocoder)
-        self._check(self.lib.e2etts_set_precision(self._h, modes[vocoder], modes[dec]), "e2etts_set_precision")
+        to the vocoder's choice).  Encoder / variance adaptor: always fp32.  Vocoder only: 'bf16' (plain bf16 operands, fp32 activations) and
+        'bf16_act' (bf16 activations rounded where the reference's .bfloat16() module rounds; HiFi-GAN tail, widths multiple of 32)."""
+        dec = decoder if decoder is not None else ("bf16x3" if vocoder in ("bf16", "bf16_act") else vocoder)
+        self._check(self.lib.e2etts_set_precision(self._h, PRECISIONS[vocoder], PRECISIONS[dec]), "e2etts_set_precision")
 
     @_locked
     def set_ragged(self, on: bool = True):

@@ -66,6 +66,29 @@ __device__ __forceinline__ unsigned bc_pack(float a, float b) {
   return __builtin_bit_cast(unsigned, r);
 }
 
+// ---- precision "bf16_act" (E2ETTS_PRECISION_BF16_ACT, include/e2etts.h): bf16 tensors at the kernels' global edges, every elementwise
+// step computed in fp32 on bf16 values and rounded to nearest-even (the A16 template parameter; A16 = false is the mode-2 code, untouched)
+__device__ __forceinline__ float bc_rnd(float x) { return (float)(__bf16)x; }
+__device__ __forceinline__ float4 bc_rnd4(float4 v) { return make_float4(bc_rnd(v.x), bc_rnd(v.y), bc_rnd(v.z), bc_rnd(v.w)); }
+__device__ __forceinline__ float4 bc_unpack4(uint2 u) {   // four bf16 -> fp32 (exact)
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+}
+// utterance `off` elements into a bf16 addend tensor (typed const float* as BConvParams::in_add is), or null
+__device__ __forceinline__ const float* bc_addend16(const float* a, long long off) {
+  return a ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(a) + off) : nullptr;
+}
+__device__ __forceinline__ uint2 bc_pack4(float4 v) { return make_uint2(bc_pack(v.x, v.y), bc_pack(v.z, v.w)); }
+// bf16(lrelu(x)) of eight bf16 values
+__device__ __forceinline__ uint4 bc_lrelu8(uint4 u, float slope) {
+  unsigned w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float lo = __uint_as_float(w[i] << 16), hi = __uint_as_float(w[i] & 0xffff0000u);
+    w[i] = bc_pack(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 // The instruction order of one (chunk, tap) unit, handed to the scheduler as a pipeline (sched_group_barrier): M MFMAs, each followed by
 // its share of the unit's R LDS reads (the NEXT unit's activation fragments) and, behind the last MFMA of each k-step, that k-step's
 // share of the L weight requests (the slot those MFMAs just freed).  An MFMA occupies the matrix pipe for 32 cycles and the wavefront can
@@ -90,7 +113,8 @@ __device__ __forceinline__ void bc_pipeline() {
 // batch is a round trip to L2 / HBM with the CU otherwise idle: 6-piece batches took 8 600 cycles for a 178-row x 256-channel slab).
 // in_add / in_div (fp32 input only): further tensors summed into the input while staging -- x = (((in + a0) + a1) + a2) / div, the order and
 // operations of accum_div_kernel (small_kernels.hip), whose launch and whose pass over the tensors this replaces.
-template <bool IN_BF16, int SB, int NTHR = 256>
+// A16 (bf16 input only): bf16(lrelu(x)) with the slope, the activation of precision "bf16_act" (a slope of 1 copies).
+template <bool IN_BF16, int SB, int NTHR = 256, bool A16 = false>
 __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt, const int T, const int Cin, const int NCH, const int RS,
                                          const int t_first, const int srows, const float slope, const int tid,
                                          const float* a0 = nullptr, const float* a1 = nullptr, const float* a2 = nullptr, const float div = 1.0f) {
@@ -99,6 +123,52 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
   constexpr int esz = IN_BF16 ? 2 : 4;
   const __amdgpu_buffer_rsrc_t in_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(in_utt), 0, (int)((long long)T * Cin * esz), 0x00020000);
+  if constexpr (IN_BF16 && A16) {
+    if (a0) {   // precision "bf16_act", joined: x = bf16(bf16(bf16(in + a0) + a1) + a2), bf16(x / div), then bf16(lrelu(x)); bf16 addends
+      constexpr int SJ = 4;
+      const int bytes = (int)((long long)T * Cin * 2);
+      const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a0), 0, bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a1 ? a1 : a0), 0, bytes, 0x00020000);
+      const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a2 ? a2 : a0), 0, bytes, 0x00020000);
+      for (int base = tid; base < npieces; base += NTHR * SJ) {
+        uint4 v[SJ], w0[SJ], w1[SJ], w2[SJ];
+        bool ok[SJ];
+        int dst[SJ];
+#pragma unroll
+        for (int i = 0; i < SJ; ++i) {
+          const int idx = base + i * NTHR;
+          const int row = idx / ppr, pc = idx - row * ppr;
+          const int t = t_first + row;
+          ok[i] = idx < npieces && t >= 0 && t < T && pc * 8 < Cin;
+          dst[i] = idx < npieces ? row * RS + pc * 16 : -1;
+          const int off = (min(max(t, 0), T - 1) * Cin + min(pc * 8, Cin - 8)) * 2;
+          v[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, off, 0, 0));
+          w0[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r0, off, 0, 0));
+          if (a1) w1[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r1, off, 0, 0));
+          if (a2) w2[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r2, off, 0, 0));
+        }
+#pragma unroll
+        for (int i = 0; i < SJ; ++i) {
+          const unsigned xv[4] = {v[i].x, v[i].y, v[i].z, v[i].w}, u0[4] = {w0[i].x, w0[i].y, w0[i].z, w0[i].w};
+          const unsigned u1[4] = {w1[i].x, w1[i].y, w1[i].z, w1[i].w}, u2[4] = {w2[i].x, w2[i].y, w2[i].z, w2[i].w};
+          unsigned o[4];
+#pragma unroll
+          for (int h = 0; h < 4; ++h) {
+            float lo = __uint_as_float(xv[h] << 16), hi = __uint_as_float(xv[h] & 0xffff0000u);
+            lo = bc_rnd(lo + __uint_as_float(u0[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u0[h] & 0xffff0000u));
+            if (a1) { lo = bc_rnd(lo + __uint_as_float(u1[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u1[h] & 0xffff0000u)); }
+            if (a2) { lo = bc_rnd(lo + __uint_as_float(u2[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u2[h] & 0xffff0000u)); }
+            if (div != 1.0f) { lo = bc_rnd(lo / div); hi = bc_rnd(hi / div); }
+            o[h] = bc_pack(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
+          }
+          uint4 r = make_uint4(o[0], o[1], o[2], o[3]);
+          if (!ok[i]) r = make_uint4(0, 0, 0, 0);
+          if (dst[i] >= 0) *reinterpret_cast<uint4*>(smem + dst[i]) = r;
+        }
+      }
+      return;
+    }
+  }
   if constexpr (!IN_BF16) {
     if (a0) {   // the joined form: four pieces per thread and batch, every input's loads issued before the first is used
       constexpr int SJ = 4;
@@ -172,6 +242,9 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
       uint4 v;
       if constexpr (IN_BF16) {
         v = __builtin_bit_cast(uint4, ra[i]);
+        if constexpr (A16) {
+          if (slope != 1.0f) v = bc_lrelu8(v, slope);
+        }
       } else {
         float4 a = ra[i], c = rb[i];
         a.x = fmaxf(a.x, a.x * slope); a.y = fmaxf(a.y, a.y * slope); a.z = fmaxf(a.z, a.z * slope); a.w = fmaxf(a.w, a.w * slope);
@@ -286,7 +359,7 @@ struct BPairGroup {
   PairParams p[BC_GROUP_MAX];
 };
 
-template <int MT, int NT, int WGM, int WGN, int D, bool IN_BF16>
+template <int MT, int NT, int WGM, int WGN, int D, bool IN_BF16, bool A16 = false>
 __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp) {
   static_assert(WGM * WGN == 4, "four wavefronts per workgroup");
   // the member this workgroup serves (uniform): its parameters stay in the kernel-argument segment, read through scalar loads
@@ -331,10 +404,11 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
   BC_STAMP(st1);
   // ---- slab: rows [t0 - pad, t0 - pad + srows) x all channels, as bf16
   constexpr int SB = (2 * NT * D >= 24) ? (IN_BF16 ? 12 : 8) : (IN_BF16 ? 16 : 12);   // the ring's registers are live while the slab is staged
-  bc_stage<IN_BF16, SB>(smem, reinterpret_cast<const char*>(p.in) + (long long)b * p.T * p.Cin * (IN_BF16 ? 2 : 4), p.T, p.Cin, NCH, RS,
+  bc_stage<IN_BF16, SB, 256, A16>(smem, reinterpret_cast<const char*>(p.in) + (long long)b * p.T * p.Cin * (IN_BF16 ? 2 : 4), p.T, p.Cin, NCH, RS,
                                        t0 - p.pad, srows, p.in_slope, tid,
-                                       p.in_add[0] ? p.in_add[0] + (long long)b * p.T * p.Cin : nullptr, p.in_add[1] ? p.in_add[1] + (long long)b * p.T * p.Cin : nullptr,
-                                       p.in_add[2] ? p.in_add[2] + (long long)b * p.T * p.Cin : nullptr, p.in_div);
+                                       (A16 && IN_BF16) ? bc_addend16(p.in_add[0], (long long)b * p.T * p.Cin) : p.in_add[0] ? p.in_add[0] + (long long)b * p.T * p.Cin : nullptr,
+                                       (A16 && IN_BF16) ? bc_addend16(p.in_add[1], (long long)b * p.T * p.Cin) : p.in_add[1] ? p.in_add[1] + (long long)b * p.T * p.Cin : nullptr,
+                                       (A16 && IN_BF16) ? bc_addend16(p.in_add[2], (long long)b * p.T * p.Cin) : p.in_add[2] ? p.in_add[2] + (long long)b * p.T * p.Cin : nullptr, p.in_div);
   BC_STAMP(st2);
   __syncthreads();   // the one barrier of the tile: slab visible
   BC_STAMP(st3);
@@ -365,7 +439,18 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
   if (p.bias) bias4 = *reinterpret_cast<const float4*>(p.bias + ecol);
   const long long ob = (long long)b * p.T * p.Cout;
   float4 resv[MT][PASSES], accv[MT][PASSES];
-  if (p.res) {
+  if constexpr (A16) {   // bf16 residual and running sum (the sum is the bf16 output itself)
+    const __bf16* res16 = reinterpret_cast<const __bf16*>(p.res);
+    const __bf16* out16 = reinterpret_cast<const __bf16*>(p.out_b);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int ps = 0; ps < PASSES; ++ps) {
+        const int t = min(t0 + (wm * MT + m) * 32 + ps * RPP + prow, p.T - 1);
+        if (p.res) resv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(res16 + ob + (long long)t * p.Cout + ecol));
+        if (p.accumulate) accv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(out16 + ob + (long long)t * p.Cout + ecol));
+      }
+  } else if (p.res) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -374,7 +459,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
         resv[m][ps] = *reinterpret_cast<const float4*>(p.res + ob + (long long)t * p.Cout + ecol);
       }
   }
-  if (p.accumulate) {
+  if (!A16 && p.accumulate) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -398,6 +483,28 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
       const int row = ps * RPP + prow;
       const int t = tb + row;
       float4 v = *reinterpret_cast<const float4*>(patch + row * ELD + pc4);
+      if constexpr (A16) {   // bias -> round -> (act -> round) -> (+ residual -> round) -> (+ sum -> round -> / div -> round)
+        v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
+        v = bc_rnd4(v);
+        if (p.act_slope != 1.0f) {
+          v.x = fmaxf(v.x, v.x * p.act_slope); v.y = fmaxf(v.y, v.y * p.act_slope);
+          v.z = fmaxf(v.z, v.z * p.act_slope); v.w = fmaxf(v.w, v.w * p.act_slope);
+          v = bc_rnd4(v);
+        }
+        if (p.res) {
+          const float4 rv = resv[m][ps];
+          v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+          v = bc_rnd4(v);
+        }
+        if (p.accumulate) {
+          const float4 ov = accv[m][ps];
+          v.x += ov.x; v.y += ov.y; v.z += ov.z; v.w += ov.w;
+          v = bc_rnd4(v);
+          if (p.out_div != 1.0f) v = bc_rnd4(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
+        }
+        if (t < p.T) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p.out_b) + ob + (long long)t * p.Cout + ecol) = bc_pack4(v);
+        continue;
+      }
       v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
       v.x = fmaxf(v.x, v.x * p.act_slope); v.y = fmaxf(v.y, v.y * p.act_slope);
       v.z = fmaxf(v.z, v.z * p.act_slope); v.w = fmaxf(v.w, v.w * p.act_slope);
@@ -440,7 +547,9 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
 // layout, conv2 from it, the epilogue out = conv2 + b2 + x (+ out_old, / div).  Four workgroup barriers per tile in all (resblock_pair:
 // two per 32-channel chunk of conv1 alone), 128-position x 32-channel wavefront tiles (MT = 4: one 1-KiB weight fragment per four MFMAs,
 // half of what the L1 can deliver), the weights of conv2's first D units requested before conv1's epilogue.
-template <int MT, int WGM, int WGN, int D, bool ACCUM>
+// A16 (precision "bf16_act"): x, the residual, the running sum and out are bf16; intermediate = bf16(lrelu(bf16(conv1 + b1))) -- rounded
+// twice --, out = bf16(bf16(conv2 + b2) + x) (then bf16(+ sum), bf16(/ div)).
+template <int MT, int WGM, int WGN, int D, bool ACCUM, bool A16 = false>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPairGroup grp) {
   static_assert(WGM * WGN == 4 || WGM * WGN == 8, "four or eight wavefronts per workgroup (eight: 256 channels, one workgroup per CU)");
   constexpr int NTHR = 64 * WGM * WGN;
@@ -477,9 +586,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
   const __amdgpu_buffer_rsrc_t w1_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.bimg1), 0, NCH * NU * 2048, 0x00020000);
   const __amdgpu_buffer_rsrc_t w2_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.bimg2), 0, NCH * NU * 2048, 0x00020000);
   E2ETTS_BC_RING_FILL(w1_rsrc, nt0, NU)
-  const float* x_b = p.x + (long long)b * p.x_bs;
-  float* out_b = p.out + (long long)b * p.out_bs;
-  bc_stage<false, (NTHR == 512 ? 8 : 12), NTHR>(smem, x_b, p.T, C, NCH, RS, i0 - pad1, BMI + halo1, p.slope, tid);
+  // (A16: bf16 elements; the fp32 form is written as before so that the mode-2 instantiations compile as they did)
+  const float* x_b = A16 ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(p.x) + (long long)b * p.x_bs) : p.x + (long long)b * p.x_bs;
+  float* out_b = A16 ? reinterpret_cast<float*>(reinterpret_cast<__bf16*>(p.out) + (long long)b * p.out_bs) : p.out + (long long)b * p.out_bs;
+  bc_stage<A16, (NTHR == 512 ? 8 : 12), NTHR, A16>(smem, x_b, p.T, C, NCH, RS, i0 - pad1, BMI + halo1, p.slope, tid);
   BC_STAMP(st1);
   __syncthreads();   // slab visible
   BC_STAMP(st2);
@@ -517,6 +627,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
         float v[4] = {acc[m][0][4 * q] + bq[q].x, acc[m][0][4 * q + 1] + bq[q].y, acc[m][0][4 * q + 2] + bq[q].z, acc[m][0][4 * q + 3] + bq[q].w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
+          if constexpr (A16) v[i] = bc_rnd(v[i]);   // the conv's own rounding, before the activation's
           v[i] = fmaxf(v[i], v[i] * p.slope);
           v[i] = ok ? v[i] : 0.f;
           acc[m][0][4 * q + i] = 0.f;
@@ -549,8 +660,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
       const int t = min(max(o0 + wm * (32 * MT) + m * 32 + ps * RPP + prow, 0), p.T - 1);
-      resv[m][ps] = *reinterpret_cast<const float4*>(x_b + (long long)t * C + ecol);
-      if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = *reinterpret_cast<const float4*>(out_b + (long long)t * C + ecol); }
+      if constexpr (A16) {
+        resv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)t * C + ecol));
+        if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)t * C + ecol)); }
+      } else {
+        resv[m][ps] = *reinterpret_cast<const float4*>(x_b + (long long)t * C + ecol);
+        if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = *reinterpret_cast<const float4*>(out_b + (long long)t * C + ecol); }
+      }
     }
   const float4 bias2 = *reinterpret_cast<const float4*>(p.b2 + ecol);
   __syncthreads();   // intermediate dead: the region now carries the epilogue's patches
@@ -570,6 +686,21 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
       const int row = ps * RPP + prow;
       const int t = o0 + rb + row;
       float4 v = *reinterpret_cast<const float4*>(patch + row * ELD + pc4);
+      if constexpr (A16) {
+        v.x += bias2.x; v.y += bias2.y; v.z += bias2.z; v.w += bias2.w;
+        v = bc_rnd4(v);
+        const float4 rv = resv[m][ps];
+        v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
+        v = bc_rnd4(v);
+        if (ACCUM && p.accumulate) {
+          const float4 ov = accv[m][ps];
+          v.x += ov.x; v.y += ov.y; v.z += ov.z; v.w += ov.w;
+          v = bc_rnd4(v);
+          if (p.out_div != 1.0f) v = bc_rnd4(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
+        }
+        if (t < t_end && rb + row < BMO) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)t * C + ecol) = bc_pack4(v);
+        continue;
+      }
       v.x += bias2.x; v.y += bias2.y; v.z += bias2.z; v.w += bias2.w;
       const float4 rv = resv[m][ps];
       v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
@@ -619,7 +750,9 @@ struct BRbGroup {
 // ((S_0 + S_1) + S_2) / n, so the bits are those of the separate launches + join.  Per stage the activations then cross the memory system
 // twice (x in, sum out) instead of nine times (x in three times, three partial sums out, three in again at the join or in the next layer's
 // staging) -- which is what the 32-channel stage of a 48 kHz window (35 MB per tensor) spends its time on.
-template <int MT, int WGM, int WGN, int D, bool ACCUM, bool STAGE>
+// A16 (precision "bf16_act"): x and out are bf16; I = bf16(lrelu(bf16(c1 + b1))), x_{m+1} = bf16(bf16(c2 + b2) + x_m) -- the residual stream
+// stays in registers, as bf16 values --, the stage sum S = bf16(S + x_n) in member order and bf16(S / n).
+template <int MT, int WGM, int WGN, int D, bool ACCUM, bool STAGE, bool A16 = false>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kernel(const BRbGroup grp) {
   constexpr int NT = 1;
   constexpr int NWAVE = WGM * WGN, NTHR = 64 * NWAVE;
@@ -658,8 +791,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
   unsigned char* Is = smem + xrows * RS;
   const int origin = tile * RO - H;     // global position of tile row 0
   const int nt0 = wn;
-  const float* x_b = grp.p[member].x + (long long)b * grp.p[member].x_bs;
-  float* out_b = grp.p[member].out + (long long)b * grp.p[member].out_bs;
+  // (A16: bf16 elements; the fp32 form is written as before so that the mode-2 instantiations compile as they did)
+  const float* x_b = A16 ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(grp.p[member].x) + (long long)b * grp.p[member].x_bs)
+                         : grp.p[member].x + (long long)b * grp.p[member].x_bs;
+  float* out_b = A16 ? reinterpret_cast<float*>(reinterpret_cast<__bf16*>(grp.p[member].out) + (long long)b * grp.p[member].out_bs)
+                     : grp.p[member].out + (long long)b * grp.p[member].out_bs;
 
   unsigned long long d0 = 0, d1 = 0, d2 = 0, d3 = 0, d4 = 0, d5 = 0, sc1 = 0, se1 = 0, sc2 = 0, se2 = 0;
   BC_STAMP(d0);
@@ -701,7 +837,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
 #pragma unroll
       for (int ps = 0; ps < PASSES; ++ps) {
         const int g = origin + wm * (32 * MT) + m * 32 + ps * RPP + prow;
-        const float4 v = *reinterpret_cast<const float4*>(x_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
+        float4 v;
+        if constexpr (A16) v = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
+        else v = *reinterpret_cast<const float4*>(x_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
         rowv[m][ps] = (g >= 0 && g < T) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
       }
 #pragma unroll
@@ -740,7 +878,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float v[4] = {src[m][4 * q], src[m][4 * q + 1], src[m][4 * q + 2], src[m][4 * q + 3]};
-          if (bias) { v[0] += bq[q].x; v[1] += bq[q].y; v[2] += bq[q].z; v[3] += bq[q].w; }
+          if (bias) {
+            v[0] += bq[q].x; v[1] += bq[q].y; v[2] += bq[q].z; v[3] += bq[q].w;
+            if constexpr (A16) { v[0] = bc_rnd(v[0]); v[1] = bc_rnd(v[1]); v[2] = bc_rnd(v[2]); v[3] = bc_rnd(v[3]); }   // the conv's rounding
+          }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             v[i] = fmaxf(v[i], v[i] * p.slope);
@@ -813,10 +954,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
         const float4 bv = *reinterpret_cast<const float4*>(p.b2[pm] + wn * 32 + 8 * q + 4 * lh);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
+          if constexpr (A16) {
+            xres[m][4 * q + 0] = bc_rnd(bc_rnd(acc[m][0][4 * q + 0] + bv.x) + xres[m][4 * q + 0]);
+            xres[m][4 * q + 1] = bc_rnd(bc_rnd(acc[m][0][4 * q + 1] + bv.y) + xres[m][4 * q + 1]);
+            xres[m][4 * q + 2] = bc_rnd(bc_rnd(acc[m][0][4 * q + 2] + bv.z) + xres[m][4 * q + 2]);
+            xres[m][4 * q + 3] = bc_rnd(bc_rnd(acc[m][0][4 * q + 3] + bv.w) + xres[m][4 * q + 3]);
+          } else {
           xres[m][4 * q + 0] = (acc[m][0][4 * q + 0] + bv.x) + xres[m][4 * q + 0];
           xres[m][4 * q + 1] = (acc[m][0][4 * q + 1] + bv.y) + xres[m][4 * q + 1];
           xres[m][4 * q + 2] = (acc[m][0][4 * q + 2] + bv.z) + xres[m][4 * q + 2];
           xres[m][4 * q + 3] = (acc[m][0][4 * q + 3] + bv.w) + xres[m][4 * q + 3];
+          }
           acc[m][0][4 * q + 0] = 0.f; acc[m][0][4 * q + 1] = 0.f; acc[m][0][4 * q + 2] = 0.f; acc[m][0][4 * q + 3] = 0.f;
         }
       }
@@ -827,7 +975,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
     }
     if constexpr (STAGE) {   // the running sum over the ResBlocks, in the join's order: (S_0 + S_1) + S_2 ...
 #pragma unroll
-      for (int m = 0; m < MT; ++m) sum[m] = mem == 0 ? xres[m] : sum[m] + xres[m];
+      for (int m = 0; m < MT; ++m) {
+        if constexpr (A16) {
+          if (mem == 0) sum[m] = xres[m];
+          else
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sum[m][r] = bc_rnd(sum[m][r] + xres[m][r]);
+        } else {
+          sum[m] = mem == 0 ? xres[m] : sum[m] + xres[m];
+        }
+      }
     }
   }
   BC_STAMP(d2);
@@ -847,7 +1004,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
           const int g = origin + wm * (32 * MT) + m * 32 + ps * RPP + prow;
-          ov[ps] = *reinterpret_cast<const f32x4_t*>(out_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
+          if constexpr (A16) {
+            const float4 u = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
+            ov[ps] = f32x4_t{u.x, u.y, u.z, u.w};
+          } else {
+            ov[ps] = *reinterpret_cast<const f32x4_t*>(out_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
+          }
         }
       }
       const f32x16& src = STAGE ? sum[STAGE ? m : 0] : xres[m];
@@ -860,6 +1022,18 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
         const int g = origin + row;
         const float4 pv = *reinterpret_cast<const float4*>(patch + (ps * RPP + prow) * ELD + pc4);
         f32x4_t v = {pv.x, pv.y, pv.z, pv.w};
+        if constexpr (A16) {
+          float4 w = pv;
+          if (STAGE) {
+            if (grp.n > 1) w = bc_rnd4(make_float4(w.x / sdiv, w.y / sdiv, w.z / sdiv, w.w / sdiv));
+          } else if (ACCUM && p.accumulate) {
+            w.x += ov[ps][0]; w.y += ov[ps][1]; w.z += ov[ps][2]; w.w += ov[ps][3];
+            w = bc_rnd4(w);
+            if (p.out_div != 1.0f) w = bc_rnd4(make_float4(w.x / p.out_div, w.y / p.out_div, w.z / p.out_div, w.w / p.out_div));
+          }
+          if (row >= H && row < R - H && g < g_end) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)g * C + wn * 32 + pc4) = bc_pack4(w);
+          continue;
+        }
         if (STAGE) {
           if (grp.n > 1) v = v / sdiv;
         } else if (ACCUM && p.accumulate) {
@@ -951,9 +1125,13 @@ const char* bc_launch(const BConvParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  if (p0.act16 && p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  else if (p0.act16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  else if (p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
   else hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false>), dim3((unsigned)nwg), dim3(256), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "conv_bf16: launch failed";
 }
@@ -989,8 +1167,10 @@ const char* conv_bf16_class(const BConvParams& p) {
 static const char* bc_check(const BConvParams& p) {
   if (!p.in || !p.wimg || (!p.out && !p.out_b)) return "conv_bf16: null pointer";
   if (!conv_bf16_supported(p)) return "conv_bf16: unsupported shape";
-  if (p.accumulate && !p.out) return "conv_bf16: accumulate needs the fp32 output";
-  if (p.in_add[0] && p.in_bf16) return "conv_bf16: in_add needs an fp32 input";
+  if (p.act16 && (p.out || !p.out_b || p.outb_slope != 1.0f || (p.in_add[0] && !p.in_bf16)))
+    return "conv_bf16: bf16 activations write the bf16 output alone (and join bf16 inputs only)";
+  if (p.accumulate && !p.out && !p.act16) return "conv_bf16: accumulate needs the fp32 output";
+  if (p.in_add[0] && p.in_bf16 && !p.act16) return "conv_bf16: in_add needs an fp32 input (or bf16 activations)";
   if ((p.in_add[1] && !p.in_add[0]) || (p.in_add[2] && !p.in_add[1])) return "conv_bf16: in_add must be filled from the front";
   if (((uintptr_t)p.in_add[0] | (uintptr_t)p.in_add[1] | (uintptr_t)p.in_add[2]) & 15) return "conv_bf16: pointers must be 16-byte aligned";
   if (p.out_div != 1.0f && !p.accumulate) return "conv_bf16: out_div needs accumulate";
@@ -1007,7 +1187,7 @@ const char* launch_conv_bf16_group(const BConvParams* ps, int n, hipStream_t s) 
   ref.rows_hint = (int)std::min<long long>((long long)ps[0].B * ps[0].T * n, 0x7fffffffLL);
   for (int k = 0; k < n; ++k) {
     if (const char* m = bc_check(ps[k])) return m;
-    if (ps[k].B != ps[0].B || ps[k].T != ps[0].T || ps[k].Cin != ps[0].Cin || ps[k].Cout != ps[0].Cout || ps[k].in_bf16 != ps[0].in_bf16 ||
+    if (ps[k].B != ps[0].B || ps[k].T != ps[0].T || ps[k].Cin != ps[0].Cin || ps[k].Cout != ps[0].Cout || ps[k].in_bf16 != ps[0].in_bf16 || ps[k].act16 != ps[0].act16 ||
         (ps[k].tap_split > 0) != (ps[0].tap_split > 0))
       return "conv_bf16: the members of a group share B, T, Cin, Cout and the input type";
     if (ps[k].dil * (ps[k].KW - 1) > ref.dil * (ref.KW - 1)) { ref.KW = ps[k].KW; ref.dil = ps[k].dil; }
@@ -1058,9 +1238,13 @@ const char* pb_launch(const PairParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].mode == 3 && any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].mode == 3) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "pair_bf16: launch failed";
 }
@@ -1080,7 +1264,7 @@ int pb_mt(long long tiles4) {
 
 bool pair_bf16_supported(const PairParams& p) {
   static const bool on = !(getenv("E2ETTS_BPAIR") && atoi(getenv("E2ETTS_BPAIR")) == 0);   // tuning aid: 0 keeps resblock_pair.hip
-  if (!on || p.mode != 2 || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
+  if (!on || (p.mode != 2 && p.mode != 3) || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
   if (!(p.C == 32 || p.C == 64 || p.C == 128 || p.C == 256) || !(p.KW & 1) || p.KW < 3 || p.KW > 15 || p.dil < 1 || p.dil * (p.KW - 1) > BC_MAX_HALO) return false;
   static const bool on256 = !(getenv("E2ETTS_BPAIR256") && atoi(getenv("E2ETTS_BPAIR256")) == 0);   // tuning aid
   if (p.C == 256 && !on256) return false;
@@ -1099,7 +1283,7 @@ const char* launch_pair_bf16_group(const PairParams* ps, int n, hipStream_t s) {
     if (p.out_div != 1.0f && !p.accumulate) return "pair_bf16: out_div needs accumulate";
     if (((uintptr_t)p.x | (uintptr_t)p.out | (uintptr_t)p.bimg1 | (uintptr_t)p.bimg2 | (uintptr_t)p.b1 | (uintptr_t)p.b2) & 15) return "pair_bf16: pointers must be 16-byte aligned";
     if (p.x == p.out) return "pair_bf16: in-place is not possible (tiles read their neighbours' rows)";
-    if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C) return "pair_bf16: the members of a group share B, T and C";
+    if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C || p.mode != ps[0].mode) return "pair_bf16: the members of a group share B, T, C and the activation type";
     tiles4 += pb_tiles4(p);
   }
   const int mt = pb_mt(tiles4);
@@ -1153,9 +1337,13 @@ const char* rb_launch(const RbParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].act16 && any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "rb_bf16: launch failed";
 }
@@ -1184,9 +1372,11 @@ const char* rb_launch_stage(const RbParams* ps, int n, hipStream_t s) {
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "rb_bf16: launch failed";
 }
 
@@ -1222,7 +1412,7 @@ const char* launch_rb_bf16_group(const RbParams* ps, int n, hipStream_t s) {
     for (int m = 0; m < p.n_pairs; ++m)
       if (((uintptr_t)p.bimg[m][0] | (uintptr_t)p.bimg[m][1] | (uintptr_t)p.b1[m] | (uintptr_t)p.b2[m]) & 15) return "rb_bf16: weights and biases must be 16-byte aligned";
     if (p.x == p.out) return "rb_bf16: in-place is not possible (tiles read their neighbours' rows)";
-    if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C) return "rb_bf16: the members of a group share B, T and C";
+    if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C || p.act16 != ps[0].act16) return "rb_bf16: the members of a group share B, T, C and the activation type";
   }
   // 32 channels: 8 wavefronts of 64 positions each (two per SIMD: one covers the other's image writes and barriers) or 4 of 128
   static const int w32 = getenv("E2ETTS_BRB_W32") ? atoi(getenv("E2ETTS_BRB_W32")) : 8;   // tuning aid (3: tiles of 384 positions, two workgroups per CU)
@@ -1243,7 +1433,7 @@ bool rb_bf16_stage_supported(const RbParams* ps, int n) {
   if (!on || !ps || n < 1 || n > BC_GROUP_MAX || ps[0].C != 32) return false;
   int Hm = 0, gxm = 0, hkm = 0;
   for (int k = 0; k < n; ++k) {
-    if (!rb_bf16_supported(ps[k]) || ps[k].accumulate || ps[k].x != ps[0].x || ps[k].B != ps[0].B || ps[k].T != ps[0].T || ps[k].C != ps[0].C ||
+    if (!rb_bf16_supported(ps[k]) || ps[k].accumulate || ps[k].x != ps[0].x || ps[k].act16 != ps[0].act16 || ps[k].B != ps[0].B || ps[k].T != ps[0].T || ps[k].C != ps[0].C ||
         ps[k].slope != ps[0].slope)
       return false;
     int H, gx;

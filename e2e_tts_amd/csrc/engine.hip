@@ -94,6 +94,10 @@ struct e2etts_engine {
   // split-precision image -> its hi halves in conv_bf16.hip's order (launch_bf16_image), for the vocoder's plain-bf16 mode; value: image
   // and the tap_split it was built with (polyphase upsamplers keep two taps per 32-column tile)
   std::map<const float*, std::pair<void*, int>> bimg_of;
+  // precision "bf16_act" only: the images of the convolutions mode 2 does not stage from bimg_of (ResBlock2), and the bf16-rounded
+  // copies (as fp32) of every vocoder bias and of conv_post's weights, keyed by the fp32 tensor; both built once at load
+  std::map<const float*, std::pair<void*, int>> bimg_act;
+  std::map<const float*, float*> r16_of;
   size_t frag_bytes = 0;
   bool ac_loaded = false, voc_loaded = false;
   std::vector<FFTLayer> enc, dec;
@@ -376,6 +380,10 @@ void free_frags(e2etts_engine* e) {
   e->frag_of.clear();
   for (auto& kv : e->bimg_of) (void)hipFree(kv.second.first);
   e->bimg_of.clear();
+  for (auto& kv : e->bimg_act) (void)hipFree(kv.second.first);
+  e->bimg_act.clear();
+  for (auto& kv : e->r16_of) (void)hipFree(kv.second);
+  e->r16_of.clear();
   for (float* f : e->rb_frag_base)
     if (f) (void)hipFree(f);
   e->rb_frag_base.clear();
@@ -414,16 +422,40 @@ int make_frag32(e2etts_engine* e, const float* w, uint64_t cout, uint64_t kw, ui
 }
 
 // hi halves of a vocoder convolution's split-precision image in conv_bf16.hip's order (plain-bf16 mode).  tap_split: see BConvParams.
-int make_bimg(e2etts_engine* e, const float* wx3, uint64_t cout, uint64_t kw, uint64_t cin, int tap_split = 0) {
-  if (!wx3 || (cout % 32) || e->bimg_of.count(wx3)) return E2ETTS_OK;
+int make_bimg(e2etts_engine* e, const float* wx3, uint64_t cout, uint64_t kw, uint64_t cin, int tap_split = 0,
+              std::map<const float*, std::pair<void*, int>>* into = nullptr) {
+  auto& dst = into ? *into : e->bimg_of;
+  if (!wx3 || (cout % 32) || dst.count(wx3)) return E2ETTS_OK;
   if (tap_split > 0 && (kw != 3 || (tap_split % 32))) tap_split = 0;   // no polyphase image: the kernel multiplies the zeros
   void* img = nullptr;
   const size_t bytes = bf16_image_bytes((int)cout, (int)kw, (int)cin, tap_split);
   HIPCHK(e, hipMalloc(&img, bytes));
   e->dev_bytes += bytes;
   e->frag_bytes += bytes;
-  e->bimg_of[wx3] = {img, tap_split};
+  dst[wx3] = {img, tap_split};
   KCHK(e, launch_bf16_image(wx3, img, (int)cout, (int)kw, (int)cin, tap_split, e->stream));
+  return E2ETTS_OK;
+}
+
+// precision "bf16_act": a copy of n fp32 values rounded to bf16 (nearest-even), kept as fp32, made once at load
+int make_r16(e2etts_engine* e, const float* src, size_t n) {
+  if (!src || e->r16_of.count(src)) return E2ETTS_OK;
+  std::vector<float> h(n);
+  HIPCHK(e, hipMemcpyAsync(h.data(), src, n * 4, hipMemcpyDefault, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  for (float& f : h) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7f800000u) != 0x7f800000u) u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
+    memcpy(&f, &u, 4);
+  }
+  float* d = nullptr;
+  HIPCHK(e, hipMalloc(&d, n * 4));
+  e->dev_bytes += n * 4;
+  e->frag_bytes += n * 4;
+  e->r16_of[src] = d;
+  HIPCHK(e, hipMemcpyAsync(d, h.data(), n * 4, hipMemcpyDefault, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
 }
 
@@ -617,6 +649,7 @@ int bind_vocoder(e2etts_engine* e) {
   const uint64_t C0 = c.voc_init_ch;
   RET(bind_conv(e, "voc.pre", C0, 7, c.n_mel, e->voc_pre));
   RET(make_bimg(e, e->voc_pre.wx3, C0, 7, c.n_mel));
+  RET(make_r16(e, e->voc_pre.b, C0));
   e->voc_up.resize(c.voc_stages);
   e->rb_c1.assign((size_t)c.voc_stages * c.voc_n_kernels, {});
   e->rb_c2.assign((size_t)c.voc_stages * c.voc_n_kernels, {});
@@ -630,6 +663,7 @@ int bind_vocoder(e2etts_engine* e) {
     // the last upsampler of HiFi-GAN V1 (64 columns), exact fp32: fragments for the zero-tap-skipping 256 x 32 tile (conv_gemm.hip)
     if (s * cout == 64) RET(make_frag32(e, e->voc_up[i].w, s * cout, 3, cin, true));
     RET(make_bimg(e, e->voc_up[i].wx3, s * cout, 3, cin, (int)(s * cout / 2)));
+    RET(make_r16(e, e->voc_up[i].b, s * cout));
     ch = cout;
     for (int j = 0; j < c.voc_n_kernels; ++j) {
       const int idx = i * c.voc_n_kernels + j;
@@ -640,12 +674,16 @@ int bind_vocoder(e2etts_engine* e) {
         std::string q = "voc.rb." + std::to_string(idx) + ".";
         if (c.voc_resblock == 2) {  // ResBlock2: one convolution per dilation (V/layers.py:52-56)
           RET(bind_conv(e, q + "c." + std::to_string(m), ch, k, ch, e->rb_c1[idx][m]));
+          RET(make_bimg(e, e->rb_c1[idx][m].wx3, ch, k, ch, 0, &e->bimg_act));
+          RET(make_r16(e, e->rb_c1[idx][m].b, ch));
           continue;
         }
         RET(bind_conv(e, q + "c1." + std::to_string(m), ch, k, ch, e->rb_c1[idx][m]));
         RET(bind_conv(e, q + "c2." + std::to_string(m), ch, k, ch, e->rb_c2[idx][m]));
         RET(make_bimg(e, e->rb_c1[idx][m].wx3, ch, k, ch));
         RET(make_bimg(e, e->rb_c2[idx][m].wx3, ch, k, ch));
+        RET(make_r16(e, e->rb_c1[idx][m].b, ch));
+        RET(make_r16(e, e->rb_c2[idx][m].b, ch));
       }
     }
     // fused pairs: all of a stage or none (the two forms use the stage's scratch buffers differently)
@@ -697,6 +735,8 @@ int bind_vocoder(e2etts_engine* e) {
   } else {
     RET(get_tensor(e, "voc.post.w", 7 * ch, &e->voc_post.w));
     RET(get_tensor(e, "voc.post.b", 1, &e->voc_post.b));
+    RET(make_r16(e, e->voc_post.w, 7 * ch));
+    RET(make_r16(e, e->voc_post.b, 1));
   }
   return E2ETTS_OK;
 }
@@ -1141,6 +1181,266 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   return E2ETTS_OK;
 }
 
+// HifiGan.forward in precision "bf16_act" (E2ETTS_PRECISION_BF16_ACT; the reference module after .bfloat16(), V/generator.py:37-53,
+// V/layers.py:33-40 / 59-64): every activation in HBM is bf16 [B, n, C], every step rounded as include/e2etts.h lists.  On the engine's
+// stream: conv_pre and the upsamplers on conv_bf16 (bf16 in / out), the ResBlocks as the fusion level asks -- 2: whole ResBlocks
+// (rb_bf16, the 32-channel stage as ONE launch with its sum), 1: fused pairs (pair_bf16), 0: two conv_bf16 launches per pair; the stage sum
+// in the ResBlocks' epilogues (S = bf16(S + rb_j), then bf16(S / num_kernels)) or, at small windows, in the next upsampler's staging (see
+// small_window below) -- and conv_post_bf16.  Every level gives the same bits.  The
+// padded batch is computed in full (no ragged row limits).  Everything the call needs is checked before the first launch.
+int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& WAV, DevBuf& PCM, bool own_out) {
+  const auto& c = e->cfg;
+  const int nk = c.voc_n_kernels, nd = c.voc_n_dil;
+  long long len = T, ch = c.voc_init_ch, maxv = len * ch;
+  for (int i = 0; i < c.voc_stages; ++i) {
+    len *= c.voc_up_rate[i];
+    ch /= 2;
+    maxv = std::max(maxv, len * ch);
+  }
+  if (len != (long long)T * c.hop_length) return e->fail(E2ETTS_EINVAL, "upsample product != hop_length");
+  if (len > 0x7fffffffLL / 2) return e->fail(E2ETTS_EINVAL, "utterance too long");
+  // ---- parameters, and every launch's geometry, before anything is launched
+  auto img = [&](const ConvW& w, int* split) -> const void* {
+    if (!w.wx3) return nullptr;
+    auto it = e->bimg_of.find(w.wx3);
+    if (it == e->bimg_of.end()) {
+      it = e->bimg_act.find(w.wx3);
+      if (it == e->bimg_act.end()) return nullptr;
+    }
+    if (split) *split = it->second.second;
+    return it->second.first;
+  };
+  auto r16 = [&](const float* p) -> const float* {
+    auto it = e->r16_of.find(p);
+    return it == e->r16_of.end() ? nullptr : it->second;
+  };
+  auto conv_q = [&](const ConvW& w, const void* in, int in_bf16, float in_slope, void* out, int Tn, int Cin, int Cout, int KW, int dil,
+                    int pad, BConvParams& q) -> bool {
+    q = BConvParams();
+    int split = 0;
+    q.wimg = img(w, &split);
+    q.in = in; q.in_bf16 = in_bf16; q.in_slope = in_slope; q.tap_split = split; q.KWe = split > 0 ? 2 : KW;
+    q.bias = r16(w.b); q.out_b = out; q.act16 = 1;
+    q.B = B; q.T = Tn; q.Cin = Cin; q.Cout = Cout; q.KW = KW; q.dil = dil; q.pad = pad;
+    return q.wimg && q.bias && conv_bf16_supported(q);
+  };
+  {
+    BConvParams q;
+    bool ok = conv_q(e->voc_pre, mel_btc, 0, 1.0f, nullptr, T, c.n_mel, c.voc_init_ch, 7, 1, 3, q);
+    long long n = T, cc = c.voc_init_ch;
+    for (int i = 0; i < c.voc_stages && ok; ++i) {
+      const int s = c.voc_up_rate[i], co = (int)cc / 2;
+      ok = conv_q(e->voc_up[i], nullptr, 1, 0.1f, nullptr, (int)n, (int)cc, s * co, 3, 1, 1, q);
+      n *= s;
+      cc = co;
+      for (int j = 0; j < nk && ok; ++j)
+        for (int m = 0; m < nd && ok; ++m) {
+          const int idx = i * nk + j, k = c.voc_rb_kernel[j], d = c.voc_rb_dil[j][m];
+          ok = conv_q(e->rb_c1[idx][m], nullptr, 1, 0.1f, nullptr, (int)n, co, co, k, d, (k * d - d) / 2, q);
+          if (ok && c.voc_resblock == 1) ok = conv_q(e->rb_c2[idx][m], nullptr, 1, 1.0f, nullptr, (int)n, co, co, k, 1, (k - 1) / 2, q);
+        }
+    }
+    if (!ok || !r16(e->voc_post.w) || !r16(e->voc_post.b) || ch > 128 || (ch % 4))
+      return e->fail(E2ETTS_EINVAL, "precision bf16_act: this vocoder (weights without bf16 images, or a geometry conv_bf16 does not serve at T = %d) has no bf16-activation route", T);
+  }
+  const size_t vb = (size_t)B * maxv * 2;
+  RET(ensure(e, e->v0, vb));
+  RET(ensure(e, e->v1, vb));
+  RET(ensure(e, e->v2, vb));
+  RET(ensure(e, e->v3, vb));
+  RET(ensure(e, WAV, (size_t)B * len * 4));
+  RET(ensure(e, PCM, (size_t)B * len * 2));
+  if (!own_out) e->have_wav = false;
+  void *S = e->v0.p, *XU = e->v1.p, *T1 = e->v2.p, *CUR = e->v3.p;
+  auto run_conv = [&](const char* nm, const BConvParams& q, double fl) -> int {
+    ProfScope ps(e, nm, fl, 2.0 * ((double)q.B * q.T * (q.Cin + q.Cout * (q.res ? 2 : 1) + (q.accumulate ? q.Cout : 0))) + 2.0 * q.KWe * q.Cin * q.Cout);
+    KCHK(e, launch_conv_bf16(q, e->stream));
+    return E2ETTS_OK;
+  };
+  // Small windows (the streaming chunks): the ResBlocks of a stage as grouped launches (launch_rb_bf16_group / launch_pair_bf16_group), each
+  // into buffers of its own, their sum formed by the next upsampler while it stages its input -- the same roundings in the same order
+  // as the accumulating epilogues (bf16(bf16(S_0 + S_1) + S_2), then / num_kernels), so the same bits
+  const bool small_window = nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && nk <= BC_GROUP_MAX && (long long)B * T <= 2048 && e->fuse_pairs >= 1;
+  if (small_window)
+    for (int j = 0; j + 1 < nk; ++j)
+      for (int k = 0; k < 3; ++k) RET(ensure(e, e->vside[j][k], vb));
+  const float* pend_add[3] = {nullptr, nullptr, nullptr};
+  float pend_div = 1.0f;
+  BConvParams q;
+  conv_q(e->voc_pre, mel_btc, 0, 1.0f, S, T, c.n_mel, c.voc_init_ch, 7, 1, 3, q);   // bf16(conv_pre(bf16(mel)) + b)
+  RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)T * c.voc_init_ch * 7 * c.n_mel));
+  long long n = T;
+  ch = c.voc_init_ch;
+  for (int i = 0; i < c.voc_stages; ++i) {
+    const int s = c.voc_up_rate[i], co = (int)ch / 2;
+    // bf16(ConvTranspose1d(bf16(lrelu_0.1(x))) + b) as the polyphase 3-tap convolution (row q of [n, s co] = rows q s .. q s + s - 1)
+    conv_q(e->voc_up[i], S, 1, 0.1f, XU, (int)n, (int)ch, s * co, 3, 1, 1, q);
+    for (int k = 0; k < 3; ++k) q.in_add[k] = pend_add[k];   // the previous stage's sum, formed while staging
+    q.in_div = pend_div;
+    pend_add[0] = pend_add[1] = pend_add[2] = nullptr; pend_div = 1.0f;
+    RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * s * co * 2 * ch));
+    n *= s;
+    ch = co;
+    bool stage_done = false;
+    auto rbq = [&](int j, RbParams& r) -> bool {
+      const int idx = i * nk + j;
+      r = RbParams();
+      r.x = reinterpret_cast<const float*>(XU); r.out = reinterpret_cast<float*>(S); r.n_pairs = nd; r.B = B; r.T = (int)n; r.C = co;
+      r.KW = c.voc_rb_kernel[j]; r.x_bs = r.out_bs = n * co; r.slope = 0.1f; r.act16 = 1;
+      if (c.voc_resblock != 1 || nd > RB_MAX_PAIRS) return false;
+      for (int m = 0; m < nd; ++m) {
+        r.bimg[m][0] = img(e->rb_c1[idx][m], nullptr); r.bimg[m][1] = img(e->rb_c2[idx][m], nullptr);
+        r.b1[m] = r16(e->rb_c1[idx][m].b); r.b2[m] = r16(e->rb_c2[idx][m].b); r.dil[m] = c.voc_rb_dil[j][m];
+      }
+      return rb_bf16_supported(r);
+    };
+    if (e->fuse_pairs >= 2 && nk <= BC_GROUP_MAX) {   // whole ResBlocks
+      RbParams rq[E2ETTS_MAX_RB_KERNELS];
+      bool ok = true;
+      double fl = 0;
+      for (int j = 0; j < nk && ok; ++j) {
+        ok = rbq(j, rq[j]);
+        if (ok) fl += rb_bf16_flops(rq[j]);
+      }
+      if (ok && rb_bf16_stage_supported(rq, nk)) {   // the whole stage and its sum in one launch
+        char nm[48];
+        snprintf(nm, sizeof nm, "rb_bf16_act_stage_%d", co);
+        ProfScope ps(e, nm, fl, 2.0 * 2.0 * B * (double)n * co);
+        KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
+        stage_done = true;
+      } else if (ok && small_window && i + 1 < c.voc_stages) {   // every ResBlock in one launch, largest kernel first; joined downstream
+        void* Sj[E2ETTS_MAX_RB_KERNELS];
+        RbParams gq[E2ETTS_MAX_RB_KERNELS];
+        int order[E2ETTS_MAX_RB_KERNELS];
+        for (int j = 0; j < nk; ++j) { Sj[j] = j ? e->vside[j - 1][0].p : S; order[j] = j; }
+        std::sort(order, order + nk, [&](int a, int b2) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b2]; });
+        double by = 0;
+        for (int t = 0; t < nk; ++t) {
+          gq[t] = rq[order[t]];
+          gq[t].out = reinterpret_cast<float*>(Sj[order[t]]);
+          by += rb_bf16_bytes(gq[t]) / 2;
+        }
+        char nm[48];
+        snprintf(nm, sizeof nm, "rb_bf16_act_group_%d", co);
+        ProfScope ps(e, nm, fl, by);
+        KCHK(e, launch_rb_bf16_group(gq, nk, e->stream));
+        for (int j = 1; j < nk; ++j) pend_add[j - 1] = reinterpret_cast<const float*>(Sj[j]);
+        pend_div = (float)nk;
+        stage_done = true;
+      } else if (ok) {
+        for (int j = 0; j < nk; ++j) {
+          rq[j].accumulate = j > 0;
+          if (j > 0 && j == nk - 1) rq[j].out_div = (float)nk;
+          char nm[48];
+          snprintf(nm, sizeof nm, "rb_bf16_act_%d", co);
+          ProfScope ps(e, nm, rb_bf16_flops(rq[j]), rb_bf16_bytes(rq[j]) / 2);
+          KCHK(e, launch_rb_bf16(rq[j], e->stream));
+        }
+        stage_done = true;
+      }
+    }
+    if (!stage_done && small_window && i + 1 < c.voc_stages && c.voc_resblock == 1) {   // pair m of every ResBlock in one launch
+      bool ok = true;
+      PairParams gq[E2ETTS_MAX_RB_KERNELS];
+      const void* curj[E2ETTS_MAX_RB_KERNELS];
+      void *Sj[E2ETTS_MAX_RB_KERNELS], *T1j[E2ETTS_MAX_RB_KERNELS], *CURj[E2ETTS_MAX_RB_KERNELS];
+      int order[E2ETTS_MAX_RB_KERNELS];
+      for (int j = 0; j < nk; ++j) {
+        Sj[j] = j ? e->vside[j - 1][0].p : S; T1j[j] = j ? e->vside[j - 1][1].p : T1; CURj[j] = j ? e->vside[j - 1][2].p : CUR;
+        curj[j] = XU; order[j] = j;
+      }
+      std::sort(order, order + nk, [&](int a, int b2) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b2]; });
+      auto member = [&](int j, int m, PairParams& pq) {
+        const int idx = i * nk + j;
+        pq = PairParams();
+        pq.x = reinterpret_cast<const float*>(curj[j]);
+        pq.out = reinterpret_cast<float*>(m == nd - 1 ? Sj[j] : (curj[j] == CURj[j] ? T1j[j] : CURj[j]));
+        pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
+        pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
+        pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = c.voc_rb_kernel[j]; pq.dil = c.voc_rb_dil[j][m]; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
+        pq.mode = 3;
+      };
+      for (int j = 0; j < nk && ok; ++j)   // every member of every launch servable: decided before anything is launched
+        for (int m = 0; m < nd && ok; ++m) {
+          PairParams pq;
+          member(j, m, pq);
+          ok = pair_bf16_supported(pq);
+        }
+      for (int m = 0; m < nd && ok; ++m) {
+        double fl = 0, by = 0;
+        for (int t = 0; t < nk; ++t) {
+          member(order[t], m, gq[t]);
+          fl += resblock_pair_flops(gq[t]); by += resblock_pair_bytes(gq[t]) / 2;
+        }
+        char nm[48];
+        snprintf(nm, sizeof nm, "pair_bf16_act_group_%d", co);
+        ProfScope ps(e, nm, fl, by);
+        KCHK(e, launch_pair_bf16_group(gq, nk, e->stream));
+        for (int t = 0; t < nk; ++t) curj[order[t]] = gq[t].out;
+      }
+      if (ok) {
+        for (int j = 1; j < nk; ++j) pend_add[j - 1] = reinterpret_cast<const float*>(Sj[j]);
+        pend_div = (float)nk;
+        stage_done = true;
+      }
+    }
+    for (int j = 0; j < nk && !stage_done; ++j) {
+      const int idx = i * nk + j, k = c.voc_rb_kernel[j];
+      const void* cur = XU;
+      for (int m = 0; m < nd; ++m) {
+        const int d = c.voc_rb_dil[j][m];
+        const bool last = m == nd - 1;
+        const int acc = last && j > 0 ? 1 : 0;
+        const float div = last && j > 0 && j == nk - 1 ? (float)nk : 1.0f;
+        if (c.voc_resblock == 2) {   // x = bf16(bf16(c(bf16(lrelu(x))) + b) + x); never in place (neighbouring rows are still read)
+          void* out = last ? S : (cur == CUR ? T1 : CUR);
+          conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, out, (int)n, co, co, k, d, (k * d - d) / 2, q);
+          q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
+          RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+          cur = out;
+          continue;
+        }
+        PairParams pq;
+        if (e->fuse_pairs >= 1) {
+          pq.x = reinterpret_cast<const float*>(cur); pq.out = reinterpret_cast<float*>(last ? S : (cur == CUR ? T1 : CUR));
+          pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
+          pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
+          pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = k; pq.dil = d; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
+          pq.mode = 3; pq.accumulate = acc; pq.out_div = div;
+        }
+        if (e->fuse_pairs >= 1 && pair_bf16_supported(pq)) {
+          char nm[48];
+          snprintf(nm, sizeof nm, "pair_bf16_act_%d", co);
+          ProfScope ps(e, nm, resblock_pair_flops(pq), resblock_pair_bytes(pq) / 2);
+          KCHK(e, launch_pair_bf16(pq, e->stream));
+          cur = pq.out;
+          continue;
+        }
+        // two launches: xt = bf16(lrelu(bf16(c1 + b1))) handed over in bf16, then x = bf16(bf16(c2(xt) + b2) + x) (conv2 may write over x:
+        // its slab reads xt, and each output row reads only its own residual row -- but never over the stage input XU)
+        void* mid = cur == T1 ? CUR : T1;
+        void* out = last ? S : (cur == XU ? (mid == T1 ? CUR : T1) : const_cast<void*>(cur));
+        conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, mid, (int)n, co, co, k, d, (k * d - d) / 2, q);
+        q.act_slope = 0.1f;
+        RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+        conv_q(e->rb_c2[idx][m], mid, 1, 1.0f, out, (int)n, co, co, k, 1, (k - 1) / 2, q);
+        q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
+        RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+        cur = out;
+      }
+    }
+  }
+  {
+    ProfScope ps(e, "conv_post_bf16", 2.0 * B * (double)n * 7 * ch, (double)B * n * (ch * 2.0 + 6.0));
+    KCHK(e, launch_conv_post_bf16(S, r16(e->voc_post.w), r16(e->voc_post.b), ptr<float>(WAV), ptr<int16_t>(PCM), B, n, (int)ch, 7, e->stream));
+  }
+  if (!own_out) {
+    e->voc_B = B; e->voc_T = T;
+    e->have_wav = true;
+  }
+  return E2ETTS_OK;
+}
+
 // HifiGan.forward (V/generator.py:37-53) on channels-last mel [B, T, n_mel] already in HBM
 int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want_wav, bool want_pcm, const int32_t* ragged_lens = nullptr,
                  const int64_t* ragged_lens_host = nullptr, DevBuf* out_wav = nullptr, DevBuf* out_pcm = nullptr) {
@@ -1151,6 +1451,7 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
   const auto& c = e->cfg;
   if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
   if (B <= 0 || T <= 0) return e->fail(E2ETTS_EINVAL, "B and T must be positive");
+  if (e->voc_precision == E2ETTS_PRECISION_BF16_ACT) return vocoder_act16(e, mel_btc, B, T, WAV, PCM, own_out);   // (ragged limits unused)
   // largest activation of any stage, in floats per utterance
   long long len = T, ch = c.voc_init_ch;
   long long maxv = len * ch;
@@ -2253,10 +2554,25 @@ int e2etts_set_precision(e2etts_engine* e, int vocoder_precision, int decoder_pr
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   if (vocoder_precision != E2ETTS_PRECISION_FP32 && vocoder_precision != E2ETTS_PRECISION_BF16X3 &&
-      vocoder_precision != E2ETTS_PRECISION_BF16)
+      vocoder_precision != E2ETTS_PRECISION_BF16 && vocoder_precision != E2ETTS_PRECISION_BF16_ACT)
     return e->fail(E2ETTS_EINVAL, "unknown vocoder precision %d", vocoder_precision);
   if (decoder_precision != E2ETTS_PRECISION_FP32 && decoder_precision != E2ETTS_PRECISION_BF16X3)
-    return e->fail(E2ETTS_EINVAL, "decoder precision must be fp32 or bf16x3 (got %d)", decoder_precision);
+    return e->fail(E2ETTS_EINVAL, "decoder precision must be fp32 or bf16x3 (got %d; bf16 and bf16_act are vocoder-only)", decoder_precision);
+  if (vocoder_precision == E2ETTS_PRECISION_BF16_ACT) {   // the geometries it serves, decided here rather than in the middle of a call
+    const auto& c = e->cfg;
+    if (c.voc_istft_nfft) return e->fail(E2ETTS_EINVAL, "precision bf16_act serves the HiFi-GAN tail only, not the iSTFT tail");
+    long long ch = c.voc_init_ch;
+    bool ok = ch >= 32 && ch % 32 == 0 && c.n_mel >= 8 && c.n_mel % 8 == 0 && (c.voc_resblock == 1 || c.voc_resblock == 2);
+    for (int i = 0; i < c.voc_stages && ok; ++i) {
+      ch /= 2;
+      ok = ch >= 32 && ch % 32 == 0;
+    }
+    for (int j = 0; j < c.voc_n_kernels && ok; ++j)
+      for (int m = 0; m < c.voc_n_dil && ok; ++m) ok = c.voc_rb_dil[j][m] * (c.voc_rb_kernel[j] - 1) <= 64;
+    if (!ok || ch > 128)
+      return e->fail(E2ETTS_EINVAL, "precision bf16_act needs every vocoder width a multiple of 32 (>= 32; final <= 128) and ResBlock reaches <= 64 rows: "
+                                    "init width %d over %d stages has no bf16-I/O route", c.voc_init_ch, c.voc_stages);
+  }
   e->voc_precision = vocoder_precision;
   e->dec_precision = decoder_precision;
   return E2ETTS_OK;

@@ -155,7 +155,8 @@ struct PairParams {
   float slope = 0.1f;            // leaky-ReLU slope of both activations
   int accumulate = 0;            // out = out_old + result
   float out_div = 1.0f;          // then / out_div (needs accumulate)
-  int mode = 1;                  // 0: exact fp32, 1: bf16x3 split precision, 2: plain bf16
+  int mode = 1;                  // 0: exact fp32, 1: bf16x3 split precision, 2: plain bf16; 3: bf16 activations (precision "bf16_act", launch_pair_bf16
+                                 // only: x, out and the running sum are bf16 [B, T, C]; pair_bf16_kernel lists the rounding points)
   double act_frac = 1.0;         // host-side bookkeeping only (see ConvParams::act_frac)
   const void* bimg1 = nullptr;   // mode 2, optional: conv1's and conv2's weights in conv_bf16.hip's order (launch_bf16_image): the pair then
   const void* bimg2 = nullptr;   // may run on launch_pair_bf16 (same bits as launch_resblock_pair in mode 2)
@@ -187,6 +188,7 @@ struct RbParams {
   float slope = 0.1f;
   int accumulate = 0;            // out = out_old + result
   float out_div = 1.0f;          // then / out_div (needs accumulate)
+  int act16 = 0;                 // precision "bf16_act": x and out (and the running sum) are bf16; see rb_bf16_kernel for the rounding points
 };
 bool rb_bf16_supported(const RbParams& p);
 const char* launch_rb_bf16_group(const RbParams* p, int n, hipStream_t s);   // members share B, T, C, n_pairs; KW / dilations / buffers per member
@@ -255,6 +257,9 @@ struct BConvParams {
   float outb_slope = 1.0f;
   int B = 0, T = 0, Cin = 0, Cout = 0, KW = 1, dil = 1, pad = 0;
   int rows_hint = 0;              // 0: tile shape by B x T; tuning aid otherwise (bench)
+  int act16 = 0;                  // precision "bf16_act": `res` and the result (out_b, also the running sum of accumulate) are bf16; the
+                                  // epilogue rounds after the bias, the activation, the residual, the sum and the division; a bf16 input is
+                                  // staged as bf16(max(x, x * in_slope)).  out must be null, outb_slope 1, in_add empty
 };
 bool conv_bf16_supported(const BConvParams& p);
 const char* launch_conv_bf16(const BConvParams& p, hipStream_t s);
@@ -311,5 +316,8 @@ const char* launch_transpose_bct_btc(const float* in, float* out, int B, int C, 
 const char* launch_conv_post(const float* x, const float* w, const float* bias, float* wav, int16_t* pcm, int B,
                              long long N, int C, int KW, hipStream_t s, const int32_t* act_rows = nullptr, const int32_t* act_rows_host = nullptr,
                              const float* const* x_add = nullptr, float x_div = 1.0f);
+// precision "bf16_act": x bf16 [B, N, C]; w16 / bias16 hold bf16-rounded values (fp32); every step rounded (small_kernels.hip)
+const char* launch_conv_post_bf16(const void* x, const float* w16, const float* bias16, float* wav, int16_t* pcm, int B, long long N, int C, int KW,
+                                  hipStream_t s);
 
 }  // namespace e2etts

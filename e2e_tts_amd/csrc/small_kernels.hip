@@ -712,6 +712,56 @@ __global__ __launch_bounds__(TPB) void conv_post_kernel(const float* __restrict_
   if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)__fmul_rn(v, 32768.0f);
 }
 
+// The same tail in precision "bf16_act" (include/e2etts.h): x bf16 [B, N, C]; x = bf16(lrelu_0.01(x)); y = bf16(conv + b) with the bf16-rounded
+// weights and bias the engine keeps (fp32 accumulation in conv_post_kernel's order); wav = bf16(tanh(y)); pcm from that rounded wav.
+__device__ __forceinline__ float cp_rnd(float x) { return (float)(__bf16)x; }
+template <int TPB>
+__global__ __launch_bounds__(TPB) void conv_post_bf16_kernel(const __bf16* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ wav,
+                                                             int16_t* __restrict__ pcm, long long N, int C, int KW) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int ldx = C + 4;
+  const int pad = (KW - 1) / 2;
+  const int rows = TPB + KW - 1;
+  float* xs = sm;
+  float* ws = sm + rows * ldx;
+  const int b = blockIdx.y;
+  const long long t0 = (long long)blockIdx.x * TPB;
+  const __bf16* xb = x + (long long)b * N * C;
+  const int c4n = C / 4;
+  for (int i = threadIdx.x; i < rows * c4n; i += TPB) {
+    const int r = i / c4n, c = (i - r * c4n) * 4;
+    const long long t = t0 - pad + r;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t >= 0 && t < N) {
+      const uint2 u = *reinterpret_cast<const uint2*>(xb + t * C + c);
+      v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+      v.x = cp_rnd(v.x >= 0.f ? v.x : v.x * 0.01f);
+      v.y = cp_rnd(v.y >= 0.f ? v.y : v.y * 0.01f);
+      v.z = cp_rnd(v.z >= 0.f ? v.z : v.z * 0.01f);
+      v.w = cp_rnd(v.w >= 0.f ? v.w : v.w * 0.01f);
+    }
+    *reinterpret_cast<float4*>(xs + r * ldx + c) = v;
+  }
+  for (int i = threadIdx.x; i < KW * C; i += TPB) ws[i] = w[i];
+  __syncthreads();
+  const long long t = t0 + threadIdx.x;
+  if (t >= N) return;
+  float acc = 0.f;
+  for (int j = 0; j < KW; ++j) {
+    const float* xr = xs + (threadIdx.x + j) * ldx;
+    const float* wr = ws + j * C;
+    for (int c = 0; c < C; c += 4) {
+      const float4 a = *reinterpret_cast<const float4*>(xr + c);
+      const float4 ww = *reinterpret_cast<const float4*>(wr + c);
+      acc += (a.x * ww.x + a.y * ww.y) + (a.z * ww.z + a.w * ww.w);
+    }
+  }
+  const float v = cp_rnd(tanhf(cp_rnd(acc + bias[0])));
+  if (wav) wav[(long long)b * N + t] = v;
+  if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)__fmul_rn(v, 32768.0f);
+}
+
 }  // namespace
 
 #define CHECK_LAUNCH(name) (hipGetLastError() == hipSuccess ? nullptr : name ": launch failed")
@@ -965,6 +1015,19 @@ const char* launch_conv_post(const float* x, const float* w, const float* bias, 
   if ((xa[1] && !xa[0]) || (xa[2] && !xa[1])) return "conv_post: x_add must be filled from the front";
   hipLaunchKernelGGL(conv_post_kernel<TPB>, grid, dim3(TPB), lds, s, x, w, bias, wav, pcm, N, C, KW, act_rows, rm, xa[0], xa[1], xa[2], x_div);
   return CHECK_LAUNCH("conv_post");
+}
+
+const char* launch_conv_post_bf16(const void* x, const float* w16, const float* bias16, float* wav, int16_t* pcm, int B, long long N, int C, int KW,
+                                  hipStream_t s) {
+  if (!x || !w16 || !bias16) return "conv_post_bf16: null pointer";
+  if (C % 4 || C <= 0 || C > 128 || KW <= 0 || KW > 15 || !(KW & 1) || B <= 0 || N <= 0) return "conv_post_bf16: bad dims";
+  if ((uintptr_t)x & 7) return "conv_post_bf16: x must be 8-byte aligned";
+  constexpr int TPB = 256;
+  const size_t lds = ((size_t)(TPB + KW - 1) * (C + 4) + (size_t)KW * C) * sizeof(float);
+  if (lds > 64 * 1024) return "conv_post_bf16: LDS tile exceeds 64 KiB";
+  hipLaunchKernelGGL(conv_post_bf16_kernel<TPB>, dim3((unsigned)((N + TPB - 1) / TPB), B), dim3(TPB), lds, s, reinterpret_cast<const __bf16*>(x), w16,
+                     bias16, wav, pcm, N, C, KW);
+  return CHECK_LAUNCH("conv_post_bf16");
 }
 
 const char* launch_var_positions(const float* x, int32_t* posbuf, const float* table, int table_rows, const float* alpha,

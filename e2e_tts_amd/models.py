@@ -182,17 +182,42 @@ class HifiGan(_EngineBacked):
         """No-op: weight norm is folded when the checkpoint is packed (reference V/generator.py:55-62)."""
         return None
 
+    def bfloat16(self):
+        """The reference module's ``.bfloat16()``: the engine's vocoder precision "bf16_act" (every activation bf16, rounded where that
+        module rounds; include/e2etts.h).  ``forward`` then takes a bf16 or fp32 mel and returns a bf16 tensor.  Returns self."""
+        if self._engine is not None:
+            self._engine.set_precision("bf16_act")   # ValueError for a geometry it does not serve; the engine keeps its mode
+        self._bf16 = True
+        return self
+
+    def float(self):
+        """Back to the reference's fp32 arithmetic (precision "fp32").  Returns self."""
+        if self._engine is not None:
+            self._engine.set_precision("fp32")
+        self._bf16 = False
+        return self
+
+    def _ensure_engine(self) -> Engine:
+        fresh = self._engine is None
+        eng = super()._ensure_engine()
+        if fresh and getattr(self, "_bf16", False):
+            eng.set_precision("bf16_act")
+        return eng
+
     def forward(self, x):
-        """x [B, 80, T] (torch tensor, any device, or numpy) -> wav [B, 1, T * hop] on the GPU (V/generator.py:37-53)."""
+        """x [B, 80, T] (torch tensor, any device, or numpy) -> wav [B, 1, T * hop] on the GPU (V/generator.py:37-53); after ``bfloat16()``
+        the wav is a bf16 tensor (the engine's wav values are bf16 values: the cast is exact)."""
         torch = _torch()
         eng = self._ensure_engine()
         dev = torch.device("cuda", self._device)
-        x = torch.as_tensor(x, dtype=torch.float32).contiguous()
+        x = torch.as_tensor(x).to(torch.float32).contiguous()   # a bf16 mel widens exactly
         if x.dim() != 3 or x.shape[1] != self._dims_cache.n_mel:
             raise ValueError(f"expected mel of shape [B, {self._dims_cache.n_mel}, T], got {tuple(x.shape)}")
         B, _, T = x.shape
         wav = torch.empty((B, T * self._dims_cache.hop_length), dtype=torch.float32, device=dev)
         eng.vocoder(x, B, T, channels_first=True, out_wav=wav)
+        if getattr(self, "_bf16", False):
+            wav = wav.to(torch.bfloat16)
         return wav.unsqueeze(1)
 
     __call__ = forward
@@ -215,6 +240,9 @@ class iSTFT(HifiGan):
         self.post_n_fft = config["gen_istft_n_fft"]
         self._dims_cache = _vocoder_only_dims(config, vocoder="istft")
         self._device = _device_index(device)
+
+    def bfloat16(self):
+        raise NotImplementedError("bf16 activations (precision 'bf16_act') serve the HiFi-GAN tail only, not the iSTFT tail")
 
     def _run(self, x):
         torch = _torch()

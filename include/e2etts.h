@@ -22,8 +22,14 @@
  *    streams and joins them back into that stream before anything else reads their sum: invisible to the caller, same
  *    results bit for bit); calls on one engine are serialised by an internal mutex;
  *    distinct engines are independent (one process per GPU in multi-GPU runs);
- *  - all activations are fp32, channels-last ([B, N, C]); weights come packed by
- *    e2e_tts_amd/packer.py (weight-norm and BatchNorm folded, conv weights tap-major).
+ *  - activations are channels-last ([B, N, C]); what the vocoder keeps in HBM between layers, per vocoder precision (below):
+ *      E2ETTS_PRECISION_FP32      fp32 activations, fp32 weights;
+ *      E2ETTS_PRECISION_BF16X3    fp32 activations, weights as bf16 hi + lo pairs;
+ *      E2ETTS_PRECISION_BF16      fp32 activations, residuals and stage sums (a bf16 copy of a conv's input where two launches hand one
+ *                                 over), bf16 weight images;
+ *      E2ETTS_PRECISION_BF16_ACT  bf16 activations, residuals and stage sums (2 bytes per element), bf16 weight images, bf16-rounded biases;
+ *    the acoustic model's activations are fp32 in every mode.  Weights come packed by e2e_tts_amd/packer.py (weight-norm and BatchNorm
+ *    folded, conv weights tap-major).
  */
 #ifndef E2ETTS_H
 #define E2ETTS_H
@@ -228,6 +234,26 @@ E2ETTS_API int e2etts_tempo(e2etts_engine* engine, const int16_t* pcm_in, size_t
 #define E2ETTS_PRECISION_BF16X3 1
 #define E2ETTS_PRECISION_BF16 2 /* vocoder only: hi x hi product alone (plain bf16 operands, fp32 accumulation): the arithmetic
                                    BASELINE config 5 (long-form streaming) names; waveform error ~5e-4, above the fp32 bar */
+/* E2ETTS_PRECISION_BF16_ACT (vocoder only): the arithmetic of the reference's HifiGan cast with .bfloat16() and fed a bf16 mel
+ * (V/generator.py:37-53, V/layers.py:33-40 and 59-64).  Every tensor the vocoder keeps in HBM is bf16 [B, N, C]; each convolution
+ * accumulates in fp32 (bf16 products) and rounds its output once; each elementwise step is computed in fp32 on bf16 values and rounded to
+ * nearest-even:
+ *   input            mel staged as bf16(mel)
+ *   conv_pre         x = bf16(acc + b)                                                    (generator.py:38)
+ *   per upsampler    x = bf16(lrelu_0.1(x)); x = bf16(acc + b) (ConvTranspose1d; the polyphase form has the same products)   (:40-41)
+ *   ResBlock1 pair   xt = bf16(lrelu(x)); xt = bf16(c1 + b1); xt = bf16(lrelu(xt)); xt = bf16(c2 + b2); x = bf16(xt + x)  (layers.py:35-39)
+ *   ResBlock2 step   xt = bf16(lrelu(x)); xt = bf16(c + b); x = bf16(xt + x)               (layers.py:62-64)
+ *   stage sum        xs = rb_0; xs = bf16(xs + rb_j) in j order; x = bf16(xs / num_kernels)   (generator.py:45-48)
+ *   tail             x = bf16(lrelu_0.01(x)); y = bf16(conv_post + b); wav = bf16(tanh(y))   (:49-51)
+ *   PCM              trunc(wav * 32768) of the rounded wav
+ * (note the double rounding bf16(lrelu(bf16(c1 + b1))): mode 2 rounds once, bf16(lrelu(c1 + b1))).  Weights: bf16 of the fp32 weight-norm
+ * fold (mode 2's images); biases and conv_post's weights rounded to bf16 once, at load.  Difference from the reference's module: it
+ * evaluates the weight norm in bf16 from bf16 weight_g / weight_v (two roundings); the engine rounds the fp32 fold once.  Accumulation
+ * order differs from torch's CPU kernels, so single outputs may differ by one bf16 ulp, and such flips spread through later layers.
+ * Served: the HiFi-GAN tail, ResBlock1 or ResBlock2, every vocoder width a multiple of 32 (>= 32).  e2etts_set_precision returns
+ * E2ETTS_EINVAL up front for the iSTFT tail, narrower widths, and this value as the decoder precision.  Ragged batches: the vocoder
+ * computes the padded rows (valid samples are the same with ragged on or off).  All fusion levels give the same bits. */
+#define E2ETTS_PRECISION_BF16_ACT 3
 E2ETTS_API int e2etts_set_precision(e2etts_engine* engine, int vocoder_precision, int decoder_precision);
 
 /* Ragged batches (default on).  e2etts_synthesize hands back, per utterance, only mel_lens[b] * hop valid samples; with
@@ -238,7 +264,8 @@ E2ETTS_API int e2etts_set_precision(e2etts_engine* engine, int vocoder_precision
  * The frame level (decoder, postnet, vocoder) is skipped from the mel lengths the engine computes itself; the phoneme level (encoder,
  * predictors) additionally when `lens` is HOST memory (the launch grids are built from the lengths on the host; with `lens` in device
  * memory the phoneme level computes the padded batch -- same results).  Batches of up to 64 utterances launch grids without idle
- * workgroups; larger ones still skip the rows but keep the padded grid. */
+ * workgroups; larger ones still skip the rows but keep the padded grid.  With vocoder precision E2ETTS_PRECISION_BF16_ACT the vocoder
+ * computes the padded rows in either case (the decoder and postnet still skip them); valid samples are identical with ragged on or off. */
 E2ETTS_API int e2etts_set_ragged(e2etts_engine* engine, int enable);
 
 /* Test hook for ragged mode, present only in the TEST build of the library (compiled with -DE2ETTS_TEST_HOOKS into
