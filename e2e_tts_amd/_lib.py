@@ -79,6 +79,8 @@ def load_library() -> C.CDLL:
     lib.e2etts_order_after.argtypes = [P, P]
     lib.e2etts_acoustic.restype = I
     lib.e2etts_acoustic.argtypes = [P, P, P, I, I, P, I, F, F, F, P, P, C.POINTER(I), P, P, P, P, P]
+    lib.e2etts_acoustic_ctl.restype = I
+    lib.e2etts_acoustic_ctl.argtypes = [P, P, P, I, I, P, I, P, I, P, I, P, I, P, P, C.POINTER(I), P, P, P, P, P]
     lib.e2etts_fetch_mel.restype = I
     lib.e2etts_fetch_mel.argtypes = [P, P, P]
     lib.e2etts_fetch_tap.restype = I
@@ -91,6 +93,8 @@ def load_library() -> C.CDLL:
     lib.e2etts_vocoder_btc.argtypes = [P, P, I, I, P, P]
     lib.e2etts_synthesize.restype = I
     lib.e2etts_synthesize.argtypes = [P, P, P, I, I, P, I, F, F, F, P, SZ, P, C.POINTER(I)]
+    lib.e2etts_synthesize_ctl.restype = I
+    lib.e2etts_synthesize_ctl.argtypes = [P, P, P, I, I, P, I, P, I, P, I, P, I, P, SZ, P, C.POINTER(I)]
     lib.e2etts_fetch_pcm.restype = I
     lib.e2etts_fetch_pcm.argtypes = [P, P, SZ]
     lib.e2etts_fetch_wav.restype = I
@@ -136,7 +140,7 @@ EXPORTED_SYMBOLS = [
     "e2etts_fetch_mel", "e2etts_fetch_tap", "e2etts_fetch_tap_i32", "e2etts_vocoder", "e2etts_vocoder_btc", "e2etts_synthesize", "e2etts_fetch_pcm",
     "e2etts_fetch_wav", "e2etts_vocoder_stream_begin", "e2etts_vocoder_stream_push", "e2etts_vocoder_stream_fetch",
     "e2etts_set_precision", "e2etts_set_ragged", "e2etts_set_fused_resblocks", "e2etts_profile_enable", "e2etts_profile_filter", "e2etts_profile_read", "e2etts_device_bytes", "e2etts_stream", "e2etts_sync",
-    "e2etts_load_weights_bcast", "e2etts_order_after", "e2etts_tempo",
+    "e2etts_load_weights_bcast", "e2etts_order_after", "e2etts_tempo", "e2etts_acoustic_ctl", "e2etts_synthesize_ctl",
 ]
 
 
@@ -174,6 +178,56 @@ def _expect(x, name: str, dtype: str, count: int, at_least: bool = False):
         raise TypeError(f"{name}: dtype {dt}, expected {dtype}")
     if n < count or (not at_least and n != count):
         raise ValueError(f"{name}: {n} elements, expected {'at least ' if at_least else ''}{count}")
+
+
+def _is_scalar(x) -> bool:
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+def control_array(x, B: int, L: int, name: str = "control", uv_pitch: bool = False):
+    """One duration / pitch / energy control, as ``UnsupervisedFastSpeech2.inference`` of the reference takes it (a number, or a tensor
+    that broadcasts against the prediction it multiplies: [B, L] for duration and energy, [B, L] for pitch without use_uv, [B, L, 2] with
+    it), materialised to one of the counts of e2etts_acoustic_ctl.
+
+    Returns ``(None, float)`` for a number (the scalar entry points serve it) or ``(values, n)``: a C-contiguous float32 numpy array or
+    torch tensor (on the device the input was on) of n = 1, B or B * L values -- [B, 1] is per utterance; [B, L], [1, L] and [L] are per
+    phoneme.  Under use_uv (``uv_pitch``) the last dimension must be 1: one factor for the f0 and the uv column (separate factors are not
+    supported).  Anything else raises ValueError."""
+    if x is None:
+        return None, 1.0
+    if _is_scalar(x):
+        return None, float(x)
+    is_np = isinstance(x, np.ndarray)
+    if not is_np and not hasattr(x, "data_ptr"):
+        raise TypeError(f"{name}: expected a number, a numpy array or a torch tensor, got {type(x)}")
+    shape = tuple(int(d) for d in x.shape)
+    if uv_pitch and len(shape) >= 1:
+        if shape[-1] != 1:
+            raise ValueError(f"{name}: shape {shape} under use_uv: the last dimension must be 1 (one factor for f0 and uv; "
+                             "separate f0 and uv factors are not supported)")
+        shape = shape[:-1]
+    if len(shape) > 2:
+        raise ValueError(f"{name}: shape {tuple(x.shape)} has too many dimensions for a [B={B}, L={L}] control")
+    s2 = (1,) * (2 - len(shape)) + shape   # numpy / torch broadcasting: missing leading dimensions are 1
+    if s2[0] not in (1, B) or s2[1] not in (1, L):
+        raise ValueError(f"{name}: shape {tuple(x.shape)} does not broadcast to [B={B}, L={L}]"
+                         + (" (use_uv: [B, L, 1], [B, 1, 1], ...)" if uv_pitch else ""))
+    if s2[1] == L and L > 1:
+        target, n = (B, L), B * L          # per phoneme ([1, L] and [L] repeated on every row)
+    elif s2[0] == B and B > 1:
+        target, n = (B,), B                # per utterance
+    elif s2 == (B, L):
+        target, n = (B * L,), B * L        # B == L == 1
+    else:
+        target, n = (1,), 1                # one value for the batch
+    if is_np:
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(x, np.float32).reshape(s2), (B, L) if n == B * L else s2)).reshape(target)
+    else:
+        import torch
+        v = x.detach().to(torch.float32).reshape(s2)
+        v = v.expand(B, L) if n == B * L else v
+        v = v.contiguous().reshape(target).contiguous()
+    return v, n
 
 
 def _locked(fn):
@@ -263,6 +317,16 @@ class Engine:
         self._check(self.lib.e2etts_load_weights_bcast(self._h, _addr(blob), int(nbytes), C.c_void_p(rccl_comm), int(root)),
                     "e2etts_load_weights_bcast")
 
+    def _controls(self, d_control, p_control, e_control, B: int, L: int):
+        """None when all three controls are numbers (the scalar entry points), else [(values or None, n)] for d, p, e as
+        e2etts_acoustic_ctl takes them (control_array; a number becomes one value for the batch)."""
+        uv = not self.dims.pitch_no_uv
+        arrs = [control_array(x, B, L, name, uv_pitch=(name == "p_control" and uv))
+                for x, name in ((d_control, "d_control"), (p_control, "p_control"), (e_control, "e_control"))]
+        if all(v is None for v, _ in arrs):
+            return None
+        return [(v, n) if v is not None else (np.array([n], np.float32), 1) for v, n in arrs]
+
     # ---- acoustic model
     @_locked
     def acoustic(self, ids, lens, speaker, d_control=1.0, p_control=1.0, e_control=1.0, want=("dur", "mel_lens")):
@@ -275,7 +339,8 @@ class Engine:
         _expect(speaker, "speaker", "int64", n_spk)
         if n_spk not in (1, B):
             raise ValueError(f"speaker holds {n_spk} ids, expected 1 or {B}")
-        self._order(ids, lens, speaker)
+        ctl = self._controls(d_control, p_control, e_control, B, L)
+        self._order(ids, lens, speaker, *(c[0] for c in (ctl or ())))
         out = {}
         pf, ef = bool(self.dims.pitch_frame), bool(self.dims.energy_frame)   # frame_level features: T columns, fetched after the call (below)
         bufs = dict(
@@ -288,12 +353,16 @@ class Engine:
             energy_pred=np.empty((B, L), np.float32) if "energy_pred" in want and not ef else None,
         )
         T = C.c_int(0)
-        rc = self.lib.e2etts_acoustic(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), n_spk,
-                                      float(d_control), float(p_control), float(e_control),
-                                      _addr(bufs["dur"]), _addr(bufs["mel_lens"]), C.byref(T), _addr(bufs["pitch_idx"]),
-                                      _addr(bufs["energy_idx"]), _addr(bufs["log_d"]), _addr(bufs["pitch_pred"]),
-                                      _addr(bufs["energy_pred"]))
-        self._check(rc, "e2etts_acoustic")
+        outs = (_addr(bufs["dur"]), _addr(bufs["mel_lens"]), C.byref(T), _addr(bufs["pitch_idx"]), _addr(bufs["energy_idx"]),
+                _addr(bufs["log_d"]), _addr(bufs["pitch_pred"]), _addr(bufs["energy_pred"]))
+        if ctl is None:
+            rc = self.lib.e2etts_acoustic(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), n_spk,
+                                          float(d_control), float(p_control), float(e_control), *outs)
+            self._check(rc, "e2etts_acoustic")
+        else:
+            rc = self.lib.e2etts_acoustic_ctl(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), n_spk,
+                                              *(a for v, n in ctl for a in (_addr(v), n)), *outs)
+            self._check(rc, "e2etts_acoustic_ctl")
         out.update({k: v for k, v in bufs.items() if v is not None})
         out["T"] = T.value
         out["B"] = B
@@ -365,11 +434,18 @@ class Engine:
         _expect(mel_lens, "out_mel_lens", "int64", B)
         if n_spk not in (1, B):
             raise ValueError(f"speaker holds {n_spk} ids, expected 1 or {B}")
-        self._order(ids, lens, speaker, out_pcm, mel_lens)
-        rc = self.lib.e2etts_synthesize(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), int(speaker.shape[0]),
-                                        float(d_control), float(p_control), float(e_control), _addr(out_pcm), cap,
-                                        _addr(mel_lens), C.byref(T))
-        self._check(rc, "e2etts_synthesize")
+        ctl = self._controls(d_control, p_control, e_control, B, L)
+        self._order(ids, lens, speaker, out_pcm, mel_lens, *(c[0] for c in (ctl or ())))
+        if ctl is None:
+            rc = self.lib.e2etts_synthesize(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), int(speaker.shape[0]),
+                                            float(d_control), float(p_control), float(e_control), _addr(out_pcm), cap,
+                                            _addr(mel_lens), C.byref(T))
+            self._check(rc, "e2etts_synthesize")
+        else:
+            rc = self.lib.e2etts_synthesize_ctl(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), n_spk,
+                                                *(a for v, n in ctl for a in (_addr(v), n)), _addr(out_pcm), cap, _addr(mel_lens),
+                                                C.byref(T))
+            self._check(rc, "e2etts_synthesize_ctl")
         pcm = out_pcm
         if out_pcm is None and fetch_pcm:
             pcm = np.empty((B, T.value * self.dims.hop_length), np.int16)

@@ -89,19 +89,29 @@ class TTS:
 
     # ---- reference API/utils.py:64-80
     def arrange_text(self, text: List[str]) -> List[str]:
+        return self.arrange_text_owners(text, self.max_len)[0]
+
+    @staticmethod
+    def arrange_text_owners(text: List[str], max_len: int):
+        """arrange_text, and for every piece the index of the text it came from (a long line is cut at " , " into pieces that each
+        belong to that line alone).  -> (pieces, owners)."""
         arranged_text: List[str] = []
-        for line in text:
-            if round(len(line) / self.max_len) != 1:
+        owners: List[int] = []
+        for i, line in enumerate(text):
+            if round(len(line) / max_len) != 1:
                 pieces = line.split(" , ")
                 arranged_text.append(pieces[0])
+                owners.append(i)
                 for piece in pieces[1:]:
-                    if len(arranged_text[-1]) >= self.max_len:
+                    if len(arranged_text[-1]) >= max_len:
                         arranged_text.append(piece)
+                        owners.append(i)
                     else:
                         arranged_text[-1] = " , ".join([arranged_text[-1], piece])
             else:
                 arranged_text.append(line)
-        return arranged_text
+                owners.append(i)
+        return arranged_text, owners
 
     @staticmethod
     def pack_sequences(sequences: Sequence[Sequence[int]], max_len: int):
@@ -165,29 +175,118 @@ class TTS:
             pos += k + distance
         return out
 
-    def inference_ids(self, sequences: Sequence[Sequence[int]], speaker_id: str, pitch_control: float = 1.0,
-                      energy_control: float = 1.0, duration_control: float = 1.0, silence_distance: float = 0.5) -> np.ndarray:
-        """TTS.inference from phoneme-id sequences (the part after text_to_sequence)."""
-        batches, revert = self.pack_sequences([list(s) for s in sequences], self.max_len)
-        spk = np.array([self.speakers[speaker_id]], dtype=np.int64)  # KeyError for an unknown speaker, as the reference
-        pcms, lengths = [], []
+    @classmethod
+    def plan_requests(cls, sequences: Sequence[Sequence[int]], max_len: int, speaker=0, duration_control=1.0, pitch_control=1.0,
+                      energy_control=1.0):
+        """The batches TTS.inference_ids runs, with per-request parameters: pack_sequences, and for every batch the speaker ids and the
+        controls of its rows.  Pure host function.
+
+        ``speaker`` is one speaker index or a list with one per sequence; each control is a number or a list with one entry per sequence,
+        an entry being a number (per utterance) or an array of len(sequence) values (per phoneme).  An entry follows its sequence through
+        the length sort and the batching.  Within a batch, equal numbers collapse to one (the scalar entry points: all-equal lists plan
+        exactly what scalars plan); different numbers become a [B, 1] array; a batch with a per-phoneme entry gets a [B, L] array, every
+        row padded with its last value (so a padded slot -- and a frame past the row's end at the frame level -- takes the control of the
+        row's last phoneme).  -> ([dict(ids, lens, speaker, rows, duration_control, pitch_control, energy_control)], revert_indices)."""
+        seqs = [list(q) for q in sequences]
+        n = len(seqs)
+        batches, revert = cls.pack_sequences(seqs, max_len)
+        order = np.argsort(revert, kind="stable")
+
+        def per_seq(v, name, arrays_ok):
+            if not isinstance(v, (list, tuple)):
+                return None
+            if len(v) != n:
+                raise ValueError(f"{name}: {len(v)} entries for {n} sequences")
+            out = []
+            for j, x in enumerate(v):
+                if isinstance(x, (list, tuple, np.ndarray)) or hasattr(x, "shape"):
+                    if not arrays_ok:
+                        raise ValueError(f"{name}[{j}]: per-phoneme controls are taken per sequence (inference_ids), not per text")
+                    a = np.asarray(x, np.float32).reshape(-1)
+                    if a.size != len(seqs[j]):
+                        raise ValueError(f"{name}[{j}]: {a.size} values for a sequence of {len(seqs[j])} phonemes")
+                    out.append(a)
+                else:
+                    out.append(float(x))
+            return out
+
+        spk = per_seq(speaker, "speaker", False)
+        ctls = [per_seq(v, name, True) for v, name in ((duration_control, "duration_control"), (pitch_control, "pitch_control"),
+                                                       (energy_control, "energy_control"))]
+        plan, s = [], 0
         for ids, lens in batches:
-            pcm, mel_lens, T = self.engine.synthesize(ids, lens, spk, duration_control, pitch_control, energy_control)
+            rows = order[s:s + len(lens)]
+            s += len(lens)
+            item = dict(ids=ids, lens=lens, rows=rows)
+            if spk is None:
+                item["speaker"] = np.array([int(speaker)], np.int64)
+            else:
+                ks = [int(spk[j]) for j in rows]
+                item["speaker"] = np.array(ks[:1] if len(set(ks)) == 1 else ks, np.int64)
+            for key, scalar, entries in zip(("duration_control", "pitch_control", "energy_control"),
+                                            (duration_control, pitch_control, energy_control), ctls):
+                if entries is None:
+                    item[key] = scalar
+                    continue
+                es = [entries[j] for j in rows]
+                if all(isinstance(x, float) for x in es):
+                    item[key] = es[0] if len(set(es)) == 1 else np.array(es, np.float32)[:, None]
+                    continue
+                L = ids.shape[1]
+                a = np.empty((len(es), L), np.float32)
+                for r, x in enumerate(es):
+                    if isinstance(x, float):
+                        a[r] = x
+                    else:
+                        a[r, :x.size] = x
+                        a[r, x.size:] = x[-1]
+                item[key] = a
+            plan.append(item)
+        return plan, revert
+
+    def inference_ids(self, sequences: Sequence[Sequence[int]], speaker_id, pitch_control=1.0, energy_control=1.0,
+                      duration_control=1.0, silence_distance: float = 0.5) -> np.ndarray:
+        """TTS.inference from phoneme-id sequences (the part after text_to_sequence).  ``speaker_id`` and each control may be a list with
+        one entry per sequence (a control entry may also be an array of per-phoneme values): requests with different settings share
+        batches (plan_requests)."""
+        if isinstance(speaker_id, (list, tuple)):
+            spk = [self.speakers[k] for k in speaker_id]   # KeyError for an unknown speaker, as the reference
+        else:
+            spk = self.speakers[speaker_id]
+        plan, revert = self.plan_requests(sequences, self.max_len, spk, duration_control, pitch_control, energy_control)
+        uv = not self._dims.pitch_no_uv
+        pcms, lengths = [], []
+        for b in plan:
+            p = b["pitch_control"]
+            if uv and isinstance(p, np.ndarray):
+                p = p[..., None]   # the reference's [B, 1, 1] / [B, L, 1]: one factor for the f0 and the uv column
+            pcm, mel_lens, T = self.engine.synthesize(b["ids"], b["lens"], b["speaker"], b["duration_control"], p, b["energy_control"])
             pcms.extend(list(pcm))
             lengths.extend(int(x) for x in mel_lens)
         pcms = [pcms[i] for i in revert.tolist()]
         lengths = [lengths[i] for i in revert.tolist()]
         return self._combine_pcm(pcms, lengths, int(silence_distance * self.sample_rate))
 
-    def inference(self, texts: list, speaker_id: str, pitch_control: float = 1.0, energy_control: float = 1.0,
-                  duration_control: float = 1.0, silence_distance: float = 0.5) -> np.ndarray:
-        """reference API/utils.py:119-160 -> 1-D np.int16."""
+    def inference(self, texts: list, speaker_id, pitch_control=1.0, energy_control=1.0, duration_control=1.0,
+                  silence_distance: float = 0.5) -> np.ndarray:
+        """reference API/utils.py:119-160 -> 1-D np.int16.  ``speaker_id`` and each control may also be a list with one entry (a name /
+        a number) per text: every piece arrange_text cuts from a text inherits that text's entry."""
         if isinstance(texts, str):
             texts = [texts]  # API/inference.py:39-40 passes a bare str, which the reference would iterate per character
         if self.text_to_sequence is None:
             raise RuntimeError("TTS was built without a text front-end: pass text_to_sequence=... or call inference_ids()")
-        seqs = [list(self.text_to_sequence(t)) for t in self.arrange_text(texts)]
-        generated_audio = self.inference_ids(seqs, speaker_id, pitch_control, energy_control, duration_control, silence_distance)
+        pieces, owners = self.arrange_text_owners(texts, self.max_len)
+
+        def follow(v, name):
+            if not isinstance(v, (list, tuple)):
+                return v
+            if len(v) != len(texts):
+                raise ValueError(f"{name}: {len(v)} entries for {len(texts)} texts")
+            return [v[i] for i in owners]
+        seqs = [list(self.text_to_sequence(t)) for t in pieces]
+        generated_audio = self.inference_ids(seqs, follow(speaker_id, "speaker_id"), follow(pitch_control, "pitch_control"),
+                                             follow(energy_control, "energy_control"), follow(duration_control, "duration_control"),
+                                             silence_distance)
         print(f"Audio Saved: {time.strftime('%H:%M:%S', time.gmtime(generated_audio.size / self.sample_rate))}")
         return generated_audio
 

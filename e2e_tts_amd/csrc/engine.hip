@@ -122,6 +122,7 @@ struct e2etts_engine {
   // workspace
   DevBuf ids, lens64, lens32, spk, xa, xb, xs, xp, tmp, qkv, att, hid, p1, p2, attws;
   DevBuf logd, durf, cum, mel64, mel32, posbuf, ppred, epred, pidx, eidx;
+  DevBuf ctlbuf;  // [3][B * L] fp32: the d / p / e controls of the _ctl entry points (grows with B * L only)
   DevBuf dx, dxb, mel, melpost, pn1, pn2;
   DevBuf melin, v0, v1, v2, v3, wav, pcm;
   // small batches: the ResBlocks of a vocoder stage run side by side, ResBlock j > 0 on side stream j - 1 with buffers of its own
@@ -913,8 +914,23 @@ __global__ void lens_to_i32_kernel(const int64_t* in, int32_t* out, int B, int L
   }
 }
 
+// The array controls of e2etts_acoustic_ctl / e2etts_synthesize_ctl: d, p, e (host or device memory; nullptr = the scalar) and their
+// counts, already checked by check_controls.
+struct CtlArgs {
+  const float* v[3] = {nullptr, nullptr, nullptr};
+  int n[3] = {0, 0, 0};
+};
+
+int check_controls(e2etts_engine* e, const CtlArgs& ctl, int B, int L) {
+  static const char* names[3] = {"d_control", "p_control", "e_control"};
+  for (int k = 0; k < 3; ++k)
+    if (ctl.v[k] && ctl.n[k] != 1 && ctl.n[k] != B && (long long)ctl.n[k] != (long long)B * L)
+      return e->fail(E2ETTS_EINVAL, "%s holds %d values: expected 1, B = %d or B * L = %lld", names[k], ctl.n[k], B, (long long)B * L);
+  return E2ETTS_OK;
+}
+
 int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
-                  int n_spk_ids, float d_control, float p_control, float e_control, bool ragged = false) {
+                  int n_spk_ids, float d_control, float p_control, float e_control, bool ragged = false, const CtlArgs* ctl = nullptr) {
   const auto& c = e->cfg;
   if (!e->ac_loaded) return e->fail(E2ETTS_ESTATE, "acoustic weights not loaded");
   if (!ids || !lens || !speaker) return e->fail(E2ETTS_EINVAL, "ids / lens / speaker must not be NULL");
@@ -968,6 +984,20 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   RET(copy_in(e, e->ids.p, ids, BL * 8));
   RET(copy_in(e, e->lens64.p, lens, (size_t)B * 8));
   RET(copy_in(e, e->spk.p, speaker, (size_t)n_spk_ids * 8));
+  // array controls: copied into the engine's control workspace, read there with the stride their count gives (kernels.h: CtlRef)
+  CtlRef cref[3];
+  if (ctl) {
+    RET(ensure(e, e->ctlbuf, 3 * BL * 4));
+    for (int k = 0; k < 3; ++k) {
+      if (!ctl->v[k]) continue;
+      float* dst = ptr<float>(e->ctlbuf) + k * BL;
+      RET(copy_in(e, dst, ctl->v[k], (size_t)ctl->n[k] * 4));
+      cref[k].p = dst;
+      if ((size_t)ctl->n[k] == BL && ctl->n[k] != B) { cref[k].sb = L; cref[k].sl = 1; }   // per phoneme, [B, L] row-major
+      else if (ctl->n[k] == B) { cref[k].sb = 1; cref[k].sl = 0; }                          // per utterance
+      else { cref[k].sb = 0; cref[k].sl = 0; }                                              // one value for the batch
+    }
+  }
   hipLaunchKernelGGL(lens_to_i32_kernel, dim3((B + 63) / 64), dim3(64), 0, e->stream, ptr<int64_t>(e->lens64),
                      ptr<int32_t>(e->lens32), B, L);
   const int32_t* tl = ptr<int32_t>(e->lens32);
@@ -1023,7 +1053,7 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   {
     ProfScope ps(e, "misc", 0, 0);
     KCHK(e, launch_duration(ptr<float>(e->logd), d_control, ptr<float>(e->durf), ptr<int32_t>(e->cum),
-                            ptr<int64_t>(e->mel64), ptr<int32_t>(e->mel32), B, L, e->stream));
+                            ptr<int64_t>(e->mel64), ptr<int32_t>(e->mel32), B, L, e->stream, cref[0]));
   }
   HIPCHK(e, hipMemcpyAsync(e->h_mel, e->mel64.p, (size_t)B * 8, hipMemcpyDeviceToHost, e->stream));
   hipEvent_t mel_ready = get_event(e);
@@ -1049,9 +1079,13 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   }
   if (!p_frame || !e_frame) {
     ProfScope ps(e, "misc", 0, 0);
+    VarCtl vc;   // (the features computed here read their controls by phoneme)
+    vc.p = p_frame ? CtlRef() : cref[1];
+    vc.e = e_frame ? CtlRef() : cref[2];
+    vc.N = L;
     KCHK(e, launch_variance_embed(xs, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
                                   e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
-                                  ptr<int32_t>(e->eidx), B, L, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 0 : 1) | (e_frame ? 0 : 2)));
+                                  ptr<int32_t>(e->eidx), B, L, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 0 : 1) | (e_frame ? 0 : 2), vc));
   }
   // the one host synchronisation of the acoustic model: T = max(mel_lens) sizes everything downstream
   HIPCHK(e, hipEventSynchronize(mel_ready));
@@ -1110,9 +1144,15 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
       RET(predictor(e, e->energy, xpf, ptr<float>(e->epred), nullptr, B, (int)T, nullptr, nullptr, 1.0, true));
     }
     ProfScope ps(e, "misc", 0, 0);
+    VarCtl vc;   // frame level: a per-phoneme control is expanded along the rounded durations (include/e2etts.h: e2etts_acoustic_ctl)
+    vc.p = p_frame ? cref[1] : CtlRef();
+    vc.e = e_frame ? cref[2] : CtlRef();
+    vc.N = (int)T;
+    vc.cum = ptr<int32_t>(e->cum);
+    vc.Lp = L;
     KCHK(e, launch_variance_embed(dx, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
                                   e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
-                                  ptr<int32_t>(e->eidx), B, (int)T, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 1 : 0) | (e_frame ? 2 : 0)));
+                                  ptr<int32_t>(e->eidx), B, (int)T, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 1 : 0) | (e_frame ? 2 : 0), vc));
     KCHK(e, launch_add_positions(dx, dpos, B, (int)T, H, e->stream));
   }
   // Ragged mode (synthesize only).  Decoder: every consumer of a row >= mel_len masks it (keys are masked, the LayerNorm
@@ -2195,15 +2235,16 @@ int e2etts_order_after(e2etts_engine* e, void* caller_stream) {
   return E2ETTS_OK;
 }
 
-int e2etts_acoustic(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
-                    int n_spk_ids, float d_control, float p_control, float e_control, float* dur_out, int64_t* mel_lens_out,
-                    int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out, float* log_dur_out, float* pitch_pred_out,
-                    float* energy_pred_out) {
+static int acoustic_entry(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
+                          int n_spk_ids, float d_control, float p_control, float e_control, const CtlArgs* ctl, float* dur_out,
+                          int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out, float* log_dur_out,
+                          float* pitch_pred_out, float* energy_pred_out) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (B > 4096) return e->fail(E2ETTS_EINVAL, "B > 4096");
-  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control));
+  if (ctl) RET(check_controls(e, *ctl, B, L));
+  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, false, ctl));
   const size_t BL = (size_t)B * L;
   if (dur_out) RET(copy_out(e, dur_out, e->durf.p, BL * 4));
   if (mel_lens_out) RET(copy_out(e, mel_lens_out, e->mel64.p, (size_t)B * 8));
@@ -2217,6 +2258,25 @@ int e2etts_acoustic(e2etts_engine* e, const int64_t* ids, const int64_t* lens, i
   if (T_out) *T_out = e->last_T;
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
+}
+
+int e2etts_acoustic(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
+                    int n_spk_ids, float d_control, float p_control, float e_control, float* dur_out, int64_t* mel_lens_out,
+                    int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out, float* log_dur_out, float* pitch_pred_out,
+                    float* energy_pred_out) {
+  return acoustic_entry(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, nullptr, dur_out, mel_lens_out, T_out,
+                        pitch_idx_out, energy_idx_out, log_dur_out, pitch_pred_out, energy_pred_out);
+}
+
+int e2etts_acoustic_ctl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
+                        int n_spk_ids, const float* d_control, int n_d, const float* p_control, int n_p, const float* e_control,
+                        int n_e, float* dur_out, int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out,
+                        float* log_dur_out, float* pitch_pred_out, float* energy_pred_out) {
+  CtlArgs ctl;
+  ctl.v[0] = d_control; ctl.v[1] = p_control; ctl.v[2] = e_control;
+  ctl.n[0] = n_d; ctl.n[1] = n_p; ctl.n[2] = n_e;
+  return acoustic_entry(e, ids, lens, B, L, speaker, n_spk_ids, 1.0f, 1.0f, 1.0f, &ctl, dur_out, mel_lens_out, T_out, pitch_idx_out,
+                        energy_idx_out, log_dur_out, pitch_pred_out, energy_pred_out);
 }
 
 int e2etts_fetch_mel(e2etts_engine* e, float* mel, float* mel_post) {
@@ -2313,15 +2373,16 @@ int e2etts_vocoder_btc(e2etts_engine* e, const float* mel_btc, int B, int T, flo
   return vocoder_entry(e, mel_btc, false, B, T, wav_out, pcm_out);
 }
 
-int e2etts_synthesize(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker, int n_spk_ids,
-                      float d_control, float p_control, float e_control, int16_t* pcm_out, size_t pcm_capacity,
-                      int64_t* mel_lens_out, int* T_out) {
+static int synthesize_entry(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
+                            int n_spk_ids, float d_control, float p_control, float e_control, const CtlArgs* ctl, int16_t* pcm_out,
+                            size_t pcm_capacity, int64_t* mel_lens_out, int* T_out) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (B > 4096) return e->fail(E2ETTS_EINVAL, "B > 4096");
+  if (ctl) RET(check_controls(e, *ctl, B, L));
   bool ragged = e->ragged != 0;
-  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, ragged));
+  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, ragged, ctl));
   ragged = ragged && e->rag_short;
   if (T_out) *T_out = e->last_T;
   RET(vocoder_impl(e, ptr<float>(e->melpost), B, e->last_T, false, true, ragged ? ptr<int32_t>(e->mel32) : nullptr, ragged ? e->h_mel : nullptr));
@@ -2336,6 +2397,22 @@ int e2etts_synthesize(e2etts_engine* e, const int64_t* ids, const int64_t* lens,
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
+}
+
+int e2etts_synthesize(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker, int n_spk_ids,
+                      float d_control, float p_control, float e_control, int16_t* pcm_out, size_t pcm_capacity,
+                      int64_t* mel_lens_out, int* T_out) {
+  return synthesize_entry(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, nullptr, pcm_out, pcm_capacity,
+                          mel_lens_out, T_out);
+}
+
+int e2etts_synthesize_ctl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
+                          int n_spk_ids, const float* d_control, int n_d, const float* p_control, int n_p, const float* e_control,
+                          int n_e, int16_t* pcm_out, size_t pcm_capacity, int64_t* mel_lens_out, int* T_out) {
+  CtlArgs ctl;
+  ctl.v[0] = d_control; ctl.v[1] = p_control; ctl.v[2] = e_control;
+  ctl.n[0] = n_d; ctl.n[1] = n_p; ctl.n[2] = n_e;
+  return synthesize_entry(e, ids, lens, B, L, speaker, n_spk_ids, 1.0f, 1.0f, 1.0f, &ctl, pcm_out, pcm_capacity, mel_lens_out, T_out);
 }
 
 int e2etts_fetch_pcm(e2etts_engine* e, int16_t* pcm_out, size_t capacity) {

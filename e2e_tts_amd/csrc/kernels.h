@@ -118,9 +118,23 @@ const char* launch_var_positions(const float* x, int32_t* posbuf, const float* t
 // out[row, o] = dot(x[row, :], w[o, :]) + b[o], o < O <= 2; rows >= lens[b] -> 0 when lens != null
 const char* launch_rowdot(const float* x, const float* w, const float* b, float* out, const int32_t* lens, int B, int L,
                           int C, int O, hipStream_t s);
+// Per-utterance / per-phoneme controls of the _ctl entry points (include/e2etts.h): element (b, l) is p[b * sb + l * sl] -- one value
+// for the batch (sb = sl = 0), per utterance (sb = 1, sl = 0) or per phoneme (sb = L, sl = 1).  p == nullptr: the kernel's scalar.
+struct CtlRef {
+  const float* p = nullptr;
+  int sb = 0, sl = 0;
+};
+// The controls of one variance_embed pass over [B, N] rows.  Phoneme level: l = the row's column (N = L).  Frame level (cum != nullptr):
+// l = the phoneme whose repeat span in the inclusive duration scan cum [B, Lp] covers frame t, Lp - 1 for frames at or past mel_len.
+struct VarCtl {
+  CtlRef p, e;
+  int N = 0;
+  const int32_t* cum = nullptr;
+  int Lp = 0;
+};
 // duration_rounded, integer durations, inclusive scan -> mel_lens; one block per utterance
 const char* launch_duration(const float* log_d, float d_control, float* dur, int32_t* cum, int64_t* mel_lens64,
-                            int32_t* mel_lens32, int B, int L, hipStream_t s);
+                            int32_t* mel_lens32, int B, int L, hipStream_t s, CtlRef d_ctl = CtlRef());
 // pitch / energy bucket indices + x += pitch_emb[pidx] + energy_emb[eidx]
 // pitch_mode 0: f0 = pred[0] * std + mean, zeroed where pred[1] > 0 (uv), tensor_f0_to_coarse; 1: the same with f0 = 2 ** pred[0]
 // (pitch_quantization "log"); 2: use_uv False -- ONE prediction per row, bucketize(pred * p_control, pitch_bins) (U/layers.py:136-160)
@@ -128,7 +142,8 @@ const char* launch_variance_embed(float* x, float* pitch_pred /*[B,L,2], scaled 
                                   const float* energy_pred, float p_control, float e_control, float f0_mean,
                                   float f0_std, const float* energy_bins, int n_bins, const float* pitch_emb,
                                   const float* energy_emb, int32_t* pitch_idx, int32_t* energy_idx, int B, int L, int H,
-                                  hipStream_t s, int pitch_mode = 0, const float* pitch_bins = nullptr, int feat = 3 /* bit 0 pitch, bit 1 energy */);
+                                  hipStream_t s, int pitch_mode = 0, const float* pitch_bins = nullptr, int feat = 3 /* bit 0 pitch, bit 1 energy */,
+                                  VarCtl ctl = VarCtl());
 // y[b, t, :] += pos[t, :]
 const char* launch_add_positions(float* y, const float* pos, int B, int T, int H, hipStream_t s);
 // length regulator fused with the decoder position add: y[b, t, :] = (t < mel_len[b] ? x[b, ph(t), :] : 0) + pos[t, :] (pos == nullptr: without it)

@@ -167,8 +167,9 @@ __global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ x
 // duration_rounded = clamp(round(exp(log_d) - 1) * d_control, min = 0)   (reference U/layers.py:218-221;
 // torch.round = half-to-even = rintf).  Repeat count = max(int(d), 0) (U/layers.py:448-449).
 // One wavefront per utterance: __shfl_up inclusive scan over 64 phonemes at a time with a running carry.
-__global__ __launch_bounds__(64) void duration_kernel(const float* __restrict__ log_d, float d_control, float* __restrict__ dur,
-                                                      int32_t* __restrict__ cum, int64_t* __restrict__ mel64,
+// d_ctl != nullptr: the control of phoneme (b, l) is d_ctl[b * ctl.sb + l * ctl.sl] instead of d_control (include/e2etts.h: _ctl entries).
+__global__ __launch_bounds__(64) void duration_kernel(const float* __restrict__ log_d, float d_control, CtlRef ctl,
+                                                      float* __restrict__ dur, int32_t* __restrict__ cum, int64_t* __restrict__ mel64,
                                                       int32_t* __restrict__ mel32, int L) {
   const int b = blockIdx.x, lane = threadIdx.x;
   // Repeat counts are capped at 2^20 frames per phoneme (inf / huge exp(log_d) would overflow the int cast) and the running sum is kept
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(64) void duration_kernel(const float* __restrict__ 
     float d = 0.f;
     if (l < L) {
       const float e = __fsub_rn(expf(log_d[b * L + l]), 1.0f);
-      d = fmaxf(__fmul_rn(rintf(e), d_control), 0.f);
+      d = fmaxf(__fmul_rn(rintf(e), ctl.p ? ctl.p[(long long)b * ctl.sb + (long long)l * ctl.sl] : d_control), 0.f);
       dur[b * L + l] = d;
     }
     int v = d == d ? (int)fminf(d, 1048576.f) : 0;  // <= 2^20 each, 64 lanes: the wave's scan stays below 2^26
@@ -208,8 +209,23 @@ __global__ __launch_bounds__(128) void variance_embed_kernel(float* __restrict__
                                                              const float* __restrict__ pitch_emb, const float* __restrict__ energy_emb,
                                                              int32_t* __restrict__ pitch_idx, int32_t* __restrict__ energy_idx, int H,
                                                              float mel_min, float mel_range, int pitch_mode,
-                                                             const float* __restrict__ pitch_bins, int feat) {
+                                                             const float* __restrict__ pitch_bins, int feat, VarCtl ctl) {
   const int row = blockIdx.x;
+  if (ctl.p.p || ctl.e.p) {  // per-utterance / per-phoneme controls (the _ctl entries); otherwise the scalars as they came
+    const int b = row / ctl.N, t = row - b * ctl.N;
+    int l = t;
+    if (ctl.cum) {  // frame level: the phoneme whose repeat span covers frame t (length_regulate_kernel's search; L - 1 past mel_len)
+      const int32_t* c = ctl.cum + (long long)b * ctl.Lp;
+      int lo = 0, hi = ctl.Lp - 1;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] > t) hi = mid; else lo = mid + 1;
+      }
+      l = lo;
+    }
+    if (ctl.p.p) p_control = ctl.p.p[(long long)b * ctl.p.sb + (long long)l * ctl.p.sl];
+    if (ctl.e.p) e_control = ctl.e.p[(long long)b * ctl.e.sb + (long long)l * ctl.e.sl];
+  }
   float f0 = 0.f, uvl = 0.f;
   int pidx = 0;
   // feat: bit 0 = pitch, bit 1 = energy take part in this pass (the other one lives at the other level: phoneme / frame, U/layers.py:226-257)
@@ -810,18 +826,19 @@ const char* launch_rowdot(const float* x, const float* w, const float* b, float*
 }
 
 const char* launch_duration(const float* log_d, float d_control, float* dur, int32_t* cum, int64_t* mel_lens64,
-                            int32_t* mel_lens32, int B, int L, hipStream_t s) {
+                            int32_t* mel_lens32, int B, int L, hipStream_t s, CtlRef d_ctl) {
   if (!log_d || !dur || !cum || !mel_lens64 || !mel_lens32) return "duration: null pointer";
-  hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, log_d, d_control, dur, cum, mel_lens64, mel_lens32, L);
+  hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, log_d, d_control, d_ctl, dur, cum, mel_lens64, mel_lens32, L);
   return CHECK_LAUNCH("duration");
 }
 
 const char* launch_variance_embed(float* x, float* pitch_pred, const float* energy_pred, float p_control, float e_control,
                                   float f0_mean, float f0_std, const float* energy_bins, int n_bins, const float* pitch_emb,
                                   const float* energy_emb, int32_t* pitch_idx, int32_t* energy_idx, int B, int L, int H,
-                                  hipStream_t s, int pitch_mode, const float* pitch_bins, int feat) {
+                                  hipStream_t s, int pitch_mode, const float* pitch_bins, int feat, VarCtl ctl) {
   if (!x || !pitch_pred || !energy_pred || !energy_bins || !pitch_emb || !energy_emb || !pitch_idx || !energy_idx)
     return "variance_embed: null pointer";
+  if ((ctl.p.p || ctl.e.p) && (ctl.N != L || (ctl.cum && ctl.Lp <= 0))) return "variance_embed: bad control geometry";
   if (feat < 1 || feat > 3) return "variance_embed: bad feature mask";
   if (pitch_mode < 0 || pitch_mode > 2 || (pitch_mode == 2 && !pitch_bins)) return "variance_embed: bad pitch mode";
   if (n_bins != 256) return "variance_embed: the f0 coarse coding is defined for 256 bins (reference U/function.py:9)";
@@ -829,7 +846,7 @@ const char* launch_variance_embed(float* x, float* pitch_pred, const float* ener
   const double mel_min = 1127.0 * log(1.0 + 50.0 / 700.0), mel_max = 1127.0 * log(1.0 + 1100.0 / 700.0);
   hipLaunchKernelGGL(variance_embed_kernel, dim3(B * L), dim3(128), 0, s, x, pitch_pred, energy_pred, p_control, e_control,
                      f0_mean, f0_std, energy_bins, n_bins, pitch_emb, energy_emb, pitch_idx, energy_idx, H, (float)mel_min,
-                     (float)(mel_max - mel_min), pitch_mode, pitch_bins, feat);
+                     (float)(mel_max - mel_min), pitch_mode, pitch_bins, feat, ctl);
   return CHECK_LAUNCH("variance_embed");
 }
 

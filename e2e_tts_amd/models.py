@@ -123,7 +123,12 @@ class UnsupervisedFastSpeech2(_EngineBacked):
                   e_control: float = 1.0):
         """-> ((mel [B, T, n_mel], mel_post [B, T, n_mel], duration_rounded [B, L] fp32), mel_lens [B] int64),
         torch tensors on the engine's GPU (reference U/model.py:155-194).  ``max_txt_len`` is accepted for
-        signature compatibility; like the reference's mask it must equal texts.shape[1]."""
+        signature compatibility; like the reference's mask it must equal texts.shape[1].
+
+        Each control is a number or, as the reference's tensor arithmetic allows (U/layers.py:145,157,168,218-221), a tensor or array
+        (host or GPU) per utterance ([B, 1]; pitch under use_uv [B, 1, 1]) or per phoneme ([B, L], [1, L], [L]; pitch under use_uv
+        [B, L, 1]) -- e2etts_acoustic_ctl, _lib.control_array.  With frame-level features a per-phoneme control is expanded along the
+        rounded durations (include/e2etts.h)."""
         torch = _torch()
         eng = self._ensure_engine()
         dev = torch.device("cuda", self._device)

@@ -162,6 +162,29 @@ E2ETTS_API int e2etts_acoustic(e2etts_engine* engine, const int64_t* ids, const 
                     float* dur_out, int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out,
                     float* log_dur_out, float* pitch_pred_out, float* energy_pred_out);
 
+/* Same, with per-utterance or per-phoneme duration, pitch and energy controls.  The reference applies the controls by plain tensor
+ * arithmetic, so its UnsupervisedFastSpeech2.inference accepts tensors for them and broadcasts:
+ *   duration  torch.round(torch.exp(log_d) - 1) * d_control                     (U/layers.py:218-221)
+ *   pitch     prediction * control  (use_uv: [B, L, 2] * [B, L, 1], :145; else :157)
+ *   energy    prediction * control                                            (U/layers.py:168)
+ * Each control is an fp32 array of n values (host or device memory, ordered like every other input: e2etts_order_after):
+ *   n == 1      one value for the batch;
+ *   n == B      one value per utterance (the reference's [B, 1], or [B, 1, 1] for pitch under use_uv);
+ *   n == B * L  one value per phoneme, row-major [B, L] (the reference's [B, L], or [B, L, 1]).
+ * A NULL pointer means 1.0 (its count is not read).  Any other count returns E2ETTS_EINVAL before anything is enqueued; the engine stays
+ * usable.  The values are used exactly as the scalar entry's are (no validation of values).  Padded phoneme slots are read like any other
+ * element, as the reference reads them.  Under use_uv one control scales both the f0 and the uv column, as a [B, L, 1] tensor does.
+ * Frame-level features (pitch_frame / energy_frame; an EXTENSION: the reference would need a [B, T] control before T is known): a
+ * per-utterance value applies to every frame of its row; a per-phoneme array is expanded along the rounded durations -- frame t of row b
+ * takes the control of the phoneme whose repeat span covers it (the length regulator's mapping: int(dur) repeats, running sum), and frames
+ * at or beyond mel_lens[b] take control[b, L - 1].  So an array that is uniform per row gives exactly the per-utterance bits.
+ * Memory: the controls are copied into an engine-owned workspace of 3 * B * L floats that grows only with B * L; steady state allocates
+ * nothing.  Outputs exactly as e2etts_acoustic. */
+E2ETTS_API int e2etts_acoustic_ctl(e2etts_engine* engine, const int64_t* ids, const int64_t* lens, int B, int L,
+                        const int64_t* speaker, int n_spk_ids, const float* d_control, int n_d, const float* p_control, int n_p,
+                        const float* e_control, int n_e, float* dur_out, int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out,
+                        int32_t* energy_idx_out, float* log_dur_out, float* pitch_pred_out, float* energy_pred_out);
+
 /* Copies of the resident results of the last e2etts_acoustic: mel, mel_post [B, T, n_mel] (either may be NULL). */
 E2ETTS_API int e2etts_fetch_mel(e2etts_engine* engine, float* mel, float* mel_post);
 
@@ -189,6 +212,11 @@ E2ETTS_API int e2etts_vocoder_btc(e2etts_engine* engine, const float* mel_btc, i
 E2ETTS_API int e2etts_synthesize(e2etts_engine* engine, const int64_t* ids, const int64_t* lens, int B, int L,
                       const int64_t* speaker, int n_spk_ids, float d_control, float p_control, float e_control,
                       int16_t* pcm_out, size_t pcm_capacity, int64_t* mel_lens_out, int* T_out);
+/* Same, with the array controls of e2etts_acoustic_ctl (same counts, memory and frame-level rule); a server batches requests that
+ * carry different speakers (n_spk_ids == B) and different controls into one call. */
+E2ETTS_API int e2etts_synthesize_ctl(e2etts_engine* engine, const int64_t* ids, const int64_t* lens, int B, int L,
+                          const int64_t* speaker, int n_spk_ids, const float* d_control, int n_d, const float* p_control, int n_p,
+                          const float* e_control, int n_e, int16_t* pcm_out, size_t pcm_capacity, int64_t* mel_lens_out, int* T_out);
 E2ETTS_API int e2etts_fetch_pcm(e2etts_engine* engine, int16_t* pcm_out, size_t capacity);
 E2ETTS_API int e2etts_fetch_wav(e2etts_engine* engine, float* wav_out, size_t capacity);
 
