@@ -54,6 +54,15 @@ _DEFAULT = {
                     "encoder_dropout": 0.1,
                     "decoder_dropout": 0.1,
                 },
+                # reference config/model_config.yaml:25-31 (selected by block_type: "fastformer", U/model.py:28-29)
+                "fastformer": {
+                    "encoder_head": 2,
+                    "decoder_head": 2,
+                    "conv_filter_size": 1024,
+                    "conv_kernel_size": [9, 1],
+                    "encoder_dropout": 0.2,
+                    "decoder_dropout": 0.2,
+                },
             },
             "variance": {
                 "duration_modelling": {
@@ -139,6 +148,7 @@ def tiny_config() -> dict:
     fs["encoder_hidden"] = 64
     fs["decoder_hidden"] = 64
     fs["building_block"]["transformer"]["conv_filter_size"] = 96
+    fs["building_block"]["fastformer"]["conv_filter_size"] = 96
     fs["building_block"]["conformer"].update(encoder_head=4, decoder_head=4, conv_kernel_size=7)
     fs["variance"]["variance_predictor"]["filter_size"] = 48
     fs["postnet"]["embedding_dim"] = 48
@@ -150,6 +160,10 @@ def tiny_config() -> dict:
 MAX_STAGES = 8
 MAX_RESBLOCK_KERNELS = 4
 MAX_DILATIONS = 4
+# what csrc/fastformer.hip serves (host_logic.h: config_check has the same limits)
+FASTFORMER_HEAD_SIZES = (1, 2, 4, 8)
+FASTFORMER_MAX_HEADS = 512
+FASTFORMER_MAX_HIDDEN = 1024
 
 
 class CEngineConfig(ctypes.Structure):
@@ -256,7 +270,16 @@ class EngineDims:
     energy_frame: int = 0     # output instead of on the phonemes (U/layers.py:226-257)
     cf_ffn_factor: float = 0.5  # Conformer half_step_residual (U/blocks/conformer.py:209-212); folded into the weights by the packer
     block_type: int = 0       # 0: FFT block (U/blocks/transformer.py), 1: Conformer block (U/blocks/conformer.py); then ffn_dim =
-                              # hidden x ffn_expansion_factor and ffn_k1 = the depthwise kernel size
+                              # hidden x ffn_expansion_factor and ffn_k1 = the depthwise kernel size; 2: Fastformer block
+                              # (U/blocks/fastformer.py), which SWAPS heads and head size: see ff_heads()
+
+    def ff_heads(self, side: str = "enc"):
+        """(number of heads, head size) the Fastformer block runs on a side.  FastAttention(d_model, d_head = H / n_head, n_head) sets
+        num_attention_heads = d_head and attention_head_size = H / d_head (U/blocks/fastformer.py:152,190-191): hidden / n_head heads of
+        size n_head -- 192 heads of size 2 for the shipped config (H = 384, encoder_head 2)."""
+        nh = (self.dec_n_head or self.n_head) if side == "dec" else self.n_head
+        heads = self.hidden // nh
+        return heads, self.hidden // heads
 
     @property
     def upsample_total(self) -> int:
@@ -318,10 +341,10 @@ def dims_from_config(config: dict, stats: dict, n_speakers: int, n_symbols: int 
         raise ValueError("vocoder must be 'hifigan' or 'istft'")
     hg = config["models"][vocoder]
     bt = fs["building_block"]["block_type"]
-    if bt not in ("transformer", "conformer"):
+    if bt not in ("transformer", "conformer", "fastformer"):
         raise NotImplementedError(
-            f"building_block.block_type={bt!r}: only the 'transformer' FFT block and the 'conformer' block are implemented "
-            "(reference U/model.py:24-33; SURVEY.md section 8(f))")
+            f"building_block.block_type={bt!r}: only the 'transformer' FFT block, the 'conformer' block and the 'fastformer' block are "
+            "implemented (reference U/model.py:24-33; SURVEY.md section 8(f))")
     tr = fs["building_block"][bt]
     if bt == "conformer":
         # U/blocks/conformer.py:31-36: heads, FFN expansion, depthwise kernel; conv expansion is asserted to be 2 there (:466)
@@ -375,7 +398,7 @@ def dims_from_config(config: dict, stats: dict, n_speakers: int, n_symbols: int 
         hop_length=hop, sample_rate=config["audio"]["signal"]["sampling_rate"],
         pos_table_rows=pos_table_rows,
         f0_mean=float(stats["f0"]["mean"]), f0_std=float(stats["f0"]["std"]),
-        block_type=1 if bt == "conformer" else 0,
+        block_type={"transformer": 0, "conformer": 1, "fastformer": 2}[bt],
         energy_layers=vp["ener_predictor_layers"], energy_kernel=vp["ener_predictor_kernel"],
         dec_n_head=tr["decoder_head"],
         pred_pad_left=0 if vp["ffn_padding"] == "SAME" else 1,
@@ -397,4 +420,12 @@ def dims_from_config(config: dict, stats: dict, n_speakers: int, n_symbols: int 
         raise ValueError(f"product of upsample_rates (x iSTFT hop) ({dims.upsample_total}) != hop_length ({hop})")
     if dims.hidden % dims.n_head or dims.hidden % (dims.dec_n_head or dims.n_head):
         raise ValueError("hidden not divisible by heads")
+    if dims.block_type == 2:
+        if dims.ffn_k1 % 2 != 1:
+            raise ValueError("fastformer conv_kernel_size[0] must be odd ('same' padding, reference U/blocks/fastformer.py:278-283)")
+        for side, nh in (("encoder_head", dims.n_head), ("decoder_head", dims.dec_n_head or dims.n_head)):
+            if nh not in FASTFORMER_HEAD_SIZES or dims.hidden // nh > FASTFORMER_MAX_HEADS or dims.hidden > FASTFORMER_MAX_HIDDEN:
+                raise NotImplementedError(
+                    f"fastformer {side}={nh}: the block runs hidden / {side} heads of size {side} (reference U/blocks/fastformer.py:190-191); "
+                    f"the pooling kernel serves head sizes {FASTFORMER_HEAD_SIZES}, at most {FASTFORMER_MAX_HEADS} heads and hidden <= {FASTFORMER_MAX_HIDDEN}")
     return dims

@@ -81,6 +81,10 @@ __device__ __forceinline__ void split4(const float4 v, uint2& hi, uint2& lo) {
   lo.y = pack_bf16(v.z - hz, v.w - hw);
 }
 
+// GELU in its exact erf form (F.gelu default): 0.5 v (1 + erf(v / sqrt(2))).  ACT_GELU is a template parameter of the kernel (GELU), not a
+// run-time branch of the epilogue: the instantiations every other activation runs on compile to what they were before it existed
+__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+
 __device__ __forceinline__ float act1(float v, int act, float slope) {
   if (act == ACT_RELU) return fmaxf(v, 0.f);
   if (act == ACT_TANH) return tanhf(v);
@@ -113,7 +117,7 @@ __device__ __forceinline__ float act1(float v, int act, float slope) {
 // Same-box A/B on the headline step: k = 11 layers 139.5 -> 141.5 (128 channels) / 139.9 -> 143.7 (256) TFLOP/s, the FFN's k = 9
 // convolution 139 -> 142.8, k = 7 136 -> 140; the class 59.1 -> 58.6 ms/step.  The polyphase upsamplers (structural-zero taps skipped:
 // short, irregular iterations) LOSE 8-15 % at three waves, so launch_cfg keeps them -- and every other tile shape -- at OCC = 2.
-template <int BM, int BN, int WM, int WN, int MODE, bool ACCUM, bool VEC, bool BFRAG, int CPI = 0, int OCC = 2>
+template <int BM, int BN, int WM, int WN, int MODE, bool ACCUM, bool VEC, bool BFRAG, int CPI = 0, int OCC = 2, bool GELU = false>
 __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p, const int tiles_per_block,
                                                                                                       const int gx, const int ny, const RowMap rm) {
   constexpr bool K1 = CPI > 0;
@@ -403,6 +407,7 @@ __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p,
             v.x *= 1.0f / (1.0f + expf(-v.x)); v.y *= 1.0f / (1.0f + expf(-v.y));
             v.z *= 1.0f / (1.0f + expf(-v.z)); v.w *= 1.0f / (1.0f + expf(-v.w));
           }
+          if constexpr (GELU) { v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w); }
           if constexpr (RES) {
             const float4 rv = resv[LEAN ? 0 : hh][ps];
             v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
@@ -440,6 +445,7 @@ __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p,
             const int t = t0 + wm * WM + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
             if (t >= p.T) continue;
             float v = act1(acc[m][n][r] + bias, p.act, p.act_slope);
+            if constexpr (GELU) v = gelu_erf(v);
             if (res_b) v += res_b[(long long)t * p.res_ld + col];
             if (t >= len) v = 0.f;
             float* o = out_b + (long long)t * p.out_ld + col;
@@ -617,7 +623,7 @@ __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p,
 #endif
 }
 
-template <int BM, int BN, int WM, int WN, int MODE, bool ACCUM, bool VEC, bool BFRAG, int CPI = 0, int OCC = 2>
+template <int BM, int BN, int WM, int WN, int MODE, bool ACCUM, bool VEC, bool BFRAG, int CPI = 0, int OCC = 2, bool GELU = false>
 const char* launch_cfg_impl(const ConvParams& p, hipStream_t s) {
   const int halo = p.dil * (p.KW - 1);
   static const int lds_pad = getenv("E2ETTS_LDS_PAD") ? atoi(getenv("E2ETTS_LDS_PAD")) : 0;  // tuning aid: occupancy experiments
@@ -625,7 +631,7 @@ const char* launch_cfg_impl(const ConvParams& p, hipStream_t s) {
   if (lds > 80 * 1024) return "conv_gemm: LDS tile exceeds 80 KiB";
   if (lds > 64 * 1024) {  // the multi-chunk Linear form: opt in once per instantiation (two workgroups per CU still fit)
     static const hipError_t attr = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&conv_gemm_kernel<BM, BN, WM, WN, MODE, ACCUM, VEC, BFRAG, CPI, OCC>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        reinterpret_cast<const void*>(&conv_gemm_kernel<BM, BN, WM, WN, MODE, ACCUM, VEC, BFRAG, CPI, OCC, GELU>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     if (attr != hipSuccess) return "conv_gemm: cannot raise the dynamic LDS limit";
   }
   const int mtiles = (p.T + BM - 1) / BM;
@@ -662,7 +668,7 @@ const char* launch_cfg_impl(const ConvParams& p, hipStream_t s) {
   const long long groups8 = (groups + 7) / 8;                     // row groups per XCD
   if (groups8 * 8 * ntiles >= (1LL << 31)) return "conv_gemm: grid too large";
   dim3 grid((unsigned)(groups8 * 8 * ntiles));
-  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, MODE, ACCUM, VEC, BFRAG, CPI, OCC>), grid, dim3(256), lds, s, p, tpb, gx, ntiles, rm);
+  hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, WM, WN, MODE, ACCUM, VEC, BFRAG, CPI, OCC, GELU>), grid, dim3(256), lds, s, p, tpb, gx, ntiles, rm);
   return hipGetLastError() == hipSuccess ? nullptr : "conv_gemm: launch failed";
 }
 
@@ -699,6 +705,17 @@ const char* launch_cfg(const ConvParams& p, hipStream_t s) {
   }
   return p.accumulate ? launch_cfg_impl<BM, BN, WM, WN, MODE, true, true, false>(p, s)
                       : launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, false>(p, s);
+}
+
+// ACT_GELU launches (the Fastformer FFN's first convolution): the same tiles on instantiations of their own, without the variants that
+// only other layers use (accumulate, the multi-chunk Linear form, the three-wave 128 x 128 form: same bits, a k = 9 convolution
+// takes none of them)
+template <int BM, int BN, int WM, int WN, int MODE>
+const char* launch_cfg_gelu(const ConvParams& p, hipStream_t s) {
+  if constexpr (BN == 128 || (BM == 64 && BN == 64)) {
+    if (p.wfrag) return launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, true, 0, 2, true>(p, s);
+  }
+  return launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, false, 0, 2, true>(p, s);
 }
 
 // Tile choice for Cout > 64.  few: so few rows (small batches, the B = 1 latency path, the encoder) that 128 x 128 tiles would leave
@@ -791,6 +808,25 @@ const char* launch_conv_gemm(const ConvParams& p, hipStream_t s) {
   if (p.in_slope < 0.f || p.in_slope > 1.f) return "conv_gemm: in_slope must lie in [0, 1]";
   if ((long long)p.T * p.in_ld * 4 >= (1LL << 31) || (long long)p.Cout * p.KW * ((p.Cin + 31) / 32 * 32) * 4 >= (1LL << 31))
     return "conv_gemm: one utterance / the weight matrix must stay below 2 GiB (32-bit buffer offsets)";
+  if (p.act == ACT_GELU) {
+    if (p.accumulate || p.x3 == 2 || p.zero_tap_split != 0) return "conv_gemm: ACT_GELU serves fp32 / bf16x3 launches without accumulate";
+    if (!epilogue_vec_ok(p))
+      return p.x3 ? launch_cfg_impl<128, 128, 64, 64, 1, false, false, false, 0, 2, true>(p, s)
+                  : launch_cfg_impl<128, 128, 64, 64, 0, false, false, false, 0, 2, true>(p, s);
+    const bool few = few_rows(p), half = half_rows(p);
+    if (p.x3) {
+      if (few) return launch_cfg_gelu<64, 64, 32, 32, 1>(p, s);
+      if (half) return launch_cfg_gelu<64, 128, 64, 32, 1>(p, s);
+      if (p.Cout > 64) return launch_cfg_gelu<128, 128, 64, 64, 1>(p, s);
+      return p.Cout > 32 ? launch_cfg_gelu<256, 64, 64, 64, 1>(p, s) : launch_cfg_gelu<256, 32, 64, 32, 1>(p, s);
+    }
+    if (p.Cout > 64) {
+      if (few) return launch_cfg_gelu<64, 64, 32, 32, 0>(p, s);
+      if (half) return launch_cfg_gelu<64, 128, 64, 32, 0>(p, s);
+      return launch_cfg_gelu<128, 128, 64, 64, 0>(p, s);
+    }
+    return p.Cout > 32 ? launch_cfg_gelu<256, 64, 64, 64, 0>(p, s) : launch_cfg_gelu<256, 32, 64, 32, 0>(p, s);
+  }
   if (!epilogue_vec_ok(p)) {  // odd channel counts / strides: one tile shape per arithmetic mode, scalar epilogue
     if (p.x3 == 1) return launch_cfg_impl<128, 128, 64, 64, 1, false, false, false>(p, s);
     if (p.x3 == 2) return launch_cfg_impl<128, 128, 64, 64, 2, false, false, false>(p, s);

@@ -277,6 +277,7 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const ConvParams p, cons
         else if (p.act == ACT_TANH) v = tanhf(v);
         else if (p.act == ACT_LRELU) v = v >= 0.f ? v : v * p.act_slope;
         else if (p.act == ACT_SWISH) v = v * (1.0f / (1.0f + expf(-v)));
+        else if (p.act == ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
         if (t < p.T && col_ok) {
           if (res_b) v += res_b[(long long)t * p.res_ld + col];
           if (t >= len) v = 0.f;
@@ -300,6 +301,7 @@ __global__ __launch_bounds__(256) void conv_rows_kernel(const ConvParams p, cons
       v = fmaxf(v, v * eslope);
       if (p.act == ACT_TANH) v = tanhf(v);
       if (p.act == ACT_SWISH) v *= 1.0f / (1.0f + expf(-v));
+      if (p.act == ACT_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
       if (t < p.T && col_ok) {
         if (res_b) v += res_b[(long long)t * p.res_ld + col];
         if (t >= len) v = 0.f;

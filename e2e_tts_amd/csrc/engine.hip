@@ -54,6 +54,16 @@ struct CfLayer {
   CfGemm pw1, pw2;
   const float *lng, *lnb;
 };
+// Fastformer layer (U/blocks/fastformer.py:144-175), as packed by packer._pack_fastformer
+struct FfLayer {
+  const float *att_lng, *att_lnb, *ffn_lng, *ffn_lnb;
+  CfGemm qk, wt, w1, w2;  // query | key (H -> 2H), transform, FFN conv k -> GELU -> conv 1
+};
+struct FfSide {
+  std::vector<FfLayer> layers;
+  const float *wql = nullptr, *bql = nullptr, *wkl = nullptr, *bkl = nullptr;  // the logit layers, tied across the layers (:161-165); [H][heads]
+  int head_size = 0;  // = n_head / dec_n_head of the config: the block runs hidden / n_head heads of that size (:190-191)
+};
 struct PredLayer {
   const float *w, *b, *g, *beta;
 };
@@ -102,6 +112,7 @@ struct e2etts_engine {
   bool ac_loaded = false, voc_loaded = false;
   std::vector<FFTLayer> enc, dec;
   std::vector<CfLayer> cf_enc, cf_dec;  // cfg.block_type == 1
+  FfSide ff_enc, ff_dec;                // cfg.block_type == 2
   Predictor dur, pitch, energy;
   const float *emb = nullptr, *enc_pos = nullptr, *dec_pos = nullptr, *pos_regen = nullptr, *spk_emb = nullptr;
   const float *var_pos = nullptr, *pitch_emb = nullptr, *energy_emb = nullptr, *energy_bins = nullptr, *pitch_bins = nullptr;
@@ -121,6 +132,7 @@ struct e2etts_engine {
 
   // workspace
   DevBuf ids, lens64, lens32, spk, xa, xb, xs, xp, tmp, qkv, att, hid, p1, p2, attws;
+  DevBuf ffpool;  // Fastformer: pooled query | pooled key [2][B, H]
   DevBuf logd, durf, cum, mel64, mel32, posbuf, ppred, epred, pidx, eidx;
   DevBuf ctlbuf;  // [3][B * L] fp32: the d / p / e controls of the _ctl entry points (grows with B * L only)
   DevBuf dx, dxb, mel, melpost, pn1, pn2;
@@ -562,6 +574,45 @@ int bind_conformer(e2etts_engine* e, const char* side, int layers, std::vector<C
   return E2ETTS_OK;
 }
 
+int bind_ff_gemm(e2etts_engine* e, const std::string& name, const std::string& bias, uint64_t cout, uint64_t kw, uint64_t cin, CfGemm& g) {
+  RET(get_tensor(e, name, cout * kw * cin, &g.w));
+  RET(make_frag32(e, g.w, cout, kw, cin));
+  RET(get_tensor(e, bias, cout, &g.b));
+  g.wx3 = nullptr;
+  if (e->tensors.count(name + ".x3")) {
+    RET(get_tensor(e, name + ".x3", cout * kw * ((cin + 31) / 32 * 32), &g.wx3));
+    RET(make_frag(e, g.wx3, cout, kw, cin));
+  }
+  return E2ETTS_OK;
+}
+
+int bind_fastformer(e2etts_engine* e, const char* side, int layers, FfSide& v, int n_head) {
+  const auto& c = e->cfg;
+  const uint64_t H = c.hidden, F = c.ffn_dim, heads = H / n_head;
+  v.head_size = n_head;
+  v.layers.resize(layers);
+  if (layers > 0) {
+    const std::string p = std::string(side) + ".ff.";
+    RET(get_tensor(e, p + "wql", H * heads, &v.wql));
+    RET(get_tensor(e, p + "bql", heads, &v.bql));
+    RET(get_tensor(e, p + "wkl", H * heads, &v.wkl));
+    RET(get_tensor(e, p + "bkl", heads, &v.bkl));
+  }
+  for (int l = 0; l < layers; ++l) {
+    const std::string p = std::string(side) + "." + std::to_string(l) + ".";
+    FfLayer& f = v.layers[l];
+    RET(get_tensor(e, p + "att.ln.g", H, &f.att_lng));
+    RET(get_tensor(e, p + "att.ln.b", H, &f.att_lnb));
+    RET(bind_ff_gemm(e, p + "att.wqk", p + "att.bqk", 2 * H, 1, H, f.qk));
+    RET(bind_ff_gemm(e, p + "att.wt", p + "att.bt", H, 1, H, f.wt));
+    RET(get_tensor(e, p + "ffn.ln.g", H, &f.ffn_lng));
+    RET(get_tensor(e, p + "ffn.ln.b", H, &f.ffn_lnb));
+    RET(bind_ff_gemm(e, p + "ffn.w1", p + "ffn.b1", F, c.ffn_k1, H, f.w1));
+    RET(bind_ff_gemm(e, p + "ffn.w2", p + "ffn.b2", H, 1, F, f.w2));
+  }
+  return E2ETTS_OK;
+}
+
 int bind_pred(e2etts_engine* e, const char* name, int layers, int kernel, int chans, int odim, bool alpha, Predictor& pr) {
   const uint64_t H = e->cfg.hidden;
   pr.layers.resize(layers);
@@ -594,6 +645,9 @@ int bind_acoustic(e2etts_engine* e) {
   if (c.block_type == 1) {
     RET(bind_conformer(e, "enc", c.enc_layers, e->cf_enc, c.n_head));
     RET(bind_conformer(e, "dec", c.dec_layers, e->cf_dec, c.dec_n_head ? c.dec_n_head : c.n_head));
+  } else if (c.block_type == 2) {
+    RET(bind_fastformer(e, "enc", c.enc_layers, e->ff_enc, c.n_head));
+    RET(bind_fastformer(e, "dec", c.dec_layers, e->ff_dec, c.dec_n_head ? c.dec_n_head : c.n_head));
   } else {
     RET(bind_fft(e, "enc", c.enc_layers, e->enc));
     RET(bind_fft(e, "dec", c.dec_layers, e->dec));
@@ -858,6 +912,67 @@ int conformer_stack(e2etts_engine* e, const std::vector<CfLayer>& layers, int n_
   return E2ETTS_OK;
 }
 
+// n x [PreNorm(FastAttention), PreNorm(PositionwiseFeedForward)] (reference U/blocks/fastformer.py:167-175), in place on x ([B, N, H]).
+// Both sub-blocks are pre-norm residual units followed by masked_fill (:169-173); there is no LayerNorm after them.  Every one of the N
+// rows is computed: the attention's mask is inverted (:223-225, see fastformer.hip), so the padded positions of a row carry practically
+// all the pooling weight, and the FFN convolution reads LayerNorm(0) = beta in the padding.  Logits, softmax and pooling are fp32 in every
+// precision mode; x3 moves the four GEMMs of a layer to the split-precision path (decoder only).
+int fastformer_stack(e2etts_engine* e, const FfSide& side, float* x, float* xalt, const int32_t* lens, int B, int N, bool x3) {
+  const auto& c = e->cfg;
+  const int H = c.hidden, F = c.ffn_dim, hs = side.head_size, heads = H / hs;
+  float* qk = ptr<float>(e->qkv);   // q | k, [B, N, 2H]
+  float* att = ptr<float>(e->att);
+  float* tmp = ptr<float>(e->tmp);
+  float* hid = ptr<float>(e->hid);
+  float *cur = x, *oth = xalt;
+  const size_t ws_bytes = ff_pool_workspace_bytes(B, N, H, hs);
+  RET(ensure(e, e->attws, ws_bytes));
+  RET(ensure(e, e->ffpool, (size_t)2 * B * H * 4));
+  float* ws = ptr<float>(e->attws);
+  float* gq = ptr<float>(e->ffpool);
+  float* gk = gq + (size_t)B * H;
+  auto gemm = [&](const CfGemm& g, const float* in, float* out, int cin, int cout, int kw, const float* res, const int32_t* mask, int act) -> int {
+    ConvParams p;
+    p.B = B; p.T = N; p.in = in; p.out = out; p.Cin = cin; p.Cout = cout; p.KW = kw; p.pad = (kw - 1) / 2; p.bias = g.b; p.res = res; p.lens = mask;
+    p.act = act;
+    const bool sx = x3 && g.wx3;
+    p.w = sx ? g.wx3 : g.w; p.x3 = sx;
+    return conv(e, p);
+  };
+  auto ln = [&](const float* in, float* out, const float* g, const float* b) -> int {
+    ProfScope ps(e, "layernorm", 0, 8.0 * B * N * H);
+    KCHK(e, launch_layernorm(in, out, g, b, nullptr, B, N, H, 1e-5f, e->stream));
+    return E2ETTS_OK;
+  };
+  // one pass over [B, N, H] (+ the logit weights per workgroup, from L2); 2 N H heads FLOP of logits + the pooling
+  const double pool_fl = 2.0 * B * (double)N * H * heads + 4.0 * B * (double)N * H;
+  const double pool_by = 4.0 * B * (double)N * H + 4.0 * H * heads;
+  for (const FfLayer& f : side.layers) {
+    RET(ln(cur, tmp, f.att_lng, f.att_lnb));                                     // PreNorm (:139-141)
+    RET(gemm(f.qk, tmp, qk, H, 2 * H, 1, nullptr, nullptr, ACT_NONE));            // query | key (:229-230)
+    {
+      ProfScope ps(e, "ff_pool", pool_fl, pool_by);                              // pooled query (:232-243)
+      KCHK(e, launch_ff_pool(qk, 2 * H, nullptr, side.wql, side.bql, lens, gq, ws, ws_bytes, B, N, H, hs, e->stream));
+    }
+    {
+      ProfScope ps(e, "ff_pool", pool_fl, pool_by + 4.0 * B * H);                // pooled key over k * pooled query (:248-259)
+      KCHK(e, launch_ff_pool(qk + H, 2 * H, gq, side.wkl, side.bkl, lens, gk, ws, ws_bytes, B, N, H, hs, e->stream));
+    }
+    {
+      ProfScope ps(e, "ff_scale", 2.0 * B * (double)N * H, 16.0 * B * (double)N * H);
+      KCHK(e, launch_ff_scale(qk, 2 * H, gk, cur, att, tmp, B, N, H, e->stream));  // pooled key * query (:262); q + x for the epilogue below
+    }
+    RET(gemm(f.wt, att, oth, H, H, 1, tmp, lens, ACT_NONE));                     // transform + bias + (q + x), masked_fill (:265, :169-170)
+    std::swap(cur, oth);
+    RET(ln(cur, tmp, f.ffn_lng, f.ffn_lnb));
+    RET(gemm(f.w1, tmp, hid, H, F, c.ffn_k1, nullptr, nullptr, ACT_GELU));         // conv k -> GELU (erf form, :296)
+    RET(gemm(f.w2, hid, oth, F, H, 1, cur, lens, ACT_NONE));                      // conv 1 + x, masked_fill (:172-173)
+    std::swap(cur, oth);
+  }
+  if (cur != x) HIPCHK(e, hipMemcpyAsync(x, cur, (size_t)B * N * H * 4, hipMemcpyDeviceToDevice, e->stream));
+  return E2ETTS_OK;
+}
+
 // conv -> ReLU -> channel LayerNorm(eps 1e-12) [-> x (1 - mask)] stack + small Linear
 // (reference DurationPredictor U/layers.py:410-420, VariancePredictor :499-503)
 int predictor(e2etts_engine* e, const Predictor& pr, const float* x, float* out, const int32_t* mask_lens, int B, int L,
@@ -1041,6 +1156,7 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
     frac_var = sv / ((double)B * L);
   }
   if (c.block_type == 1) RET(conformer_stack(e, e->cf_enc, c.n_head, x, ptr<float>(e->xb), tl, B, L, false));
+  else if (c.block_type == 2) RET(fastformer_stack(e, e->ff_enc, x, ptr<float>(e->xb), tl, B, L, false));
   else RET(fft_stack(e, e->enc, c.n_head, x, ptr<float>(e->xb), tl, B, L, false, act_enc, frac_enc, true, act_enc_h));  // encoder: always exact fp32, K-split kernel
 
   // Variance adaptor, inference branch (U/layers.py:195-258)
@@ -1188,9 +1304,11 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
     e->rag_frac_post = sp / ((double)B * T);
     e->rag_frac_voc = sv / ((double)B * T);
   }
-  // (a Conformer decoder computes every row: its attention is unmasked and its depthwise convolution crosses into the padding)
+  // (a Conformer decoder computes every row: its attention is unmasked and its depthwise convolution crosses into the padding; so does a
+  // Fastformer decoder: its inverted mask puts the pooling weight ON the padding)
   const int dec_heads = c.dec_n_head ? c.dec_n_head : c.n_head;
   if (c.block_type == 1) RET(conformer_stack(e, e->cf_dec, dec_heads, dx, ptr<float>(e->dxb), ml, B, (int)T, e->dec_precision == 1));
+  else if (c.block_type == 2) RET(fastformer_stack(e, e->ff_dec, dx, ptr<float>(e->dxb), ml, B, (int)T, e->dec_precision == 1));
   else RET(fft_stack(e, e->dec, dec_heads, dx, ptr<float>(e->dxb), ml, B, (int)T, e->dec_precision == 1, act_dec, act_dec ? e->rag_frac_dec : 1.0, false, act_dec_h));
   // mel_linear (U/model.py:186)
   ConvParams p;
@@ -2669,7 +2787,7 @@ int e2etts_debug_poison_workspace(e2etts_engine* e) {
   // what the workspaces held is gone: taps, fetches and vocoder(NULL) must say so instead of handing out the pattern
   e->have_acoustic = false;
   e->have_wav = false;
-  DevBuf* bufs[] = {&e->xa, &e->xb, &e->xs, &e->xp, &e->tmp, &e->qkv, &e->att, &e->hid, &e->p1, &e->p2, &e->attws, &e->dx, &e->dxb, &e->mel,
+  DevBuf* bufs[] = {&e->xa, &e->xb, &e->xs, &e->xp, &e->tmp, &e->qkv, &e->att, &e->hid, &e->p1, &e->p2, &e->attws, &e->ffpool, &e->dx, &e->dxb, &e->mel,
                     &e->melpost, &e->pn1, &e->pn2, &e->melin, &e->v0, &e->v1, &e->v2, &e->v3, &e->wav, &e->pcm, &e->istft_q, &e->istft_ri, &e->istft_sp};
   for (DevBuf* b : bufs)
     if (b->p) HIPCHK(e, hipMemsetAsync(b->p, 0x4B, b->cap, e->stream));

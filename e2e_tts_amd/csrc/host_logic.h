@@ -100,13 +100,22 @@ inline const char* config_check(const e2etts_config& c) {
     const int n = c.voc_istft_nfft;
     if (n < 4 || n > 256 || (n & (n - 1)) || !in(c.voc_istft_hop, 1, 256) || n % c.voc_istft_hop) return "iSTFT: n_fft must be a power of two in [4, 256] and a multiple of the hop";
   }
-  if (c.block_type != 0 && c.block_type != 1) return "block_type must be 0 (FFT block) or 1 (Conformer block)";
+  if (c.block_type != 0 && c.block_type != 1 && c.block_type != 2) return "block_type must be 0 (FFT block), 1 (Conformer block) or 2 (Fastformer block)";
   if (c.dec_n_head != 0 && (!in(c.dec_n_head, 1, BIG) || c.hidden % c.dec_n_head)) return "hidden must be a multiple of dec_n_head";
   if (c.block_type == 1) {
     const int dh = c.hidden / c.n_head, dhd = c.hidden / (c.dec_n_head ? c.dec_n_head : c.n_head);
     for (int d : {dh, dhd})
       if (d != 8 && d != 16 && d != 32 && d != 48 && d != 64 && d != 96) return "Conformer head dim must be one of 8, 16, 32, 48, 64, 96";
     if (c.ffn_dim < 2 * c.hidden) return "Conformer ffn_expansion_factor must be at least 2";
+  }
+  if (c.block_type == 2) {
+    // U/blocks/fastformer.py:190-191: hidden / n_head heads of size n_head; fastformer.hip keeps one head's running sums in registers
+    if (c.hidden > 1024) return "Fastformer: hidden must be at most 1024";
+    for (int hs : {c.n_head, c.dec_n_head ? c.dec_n_head : c.n_head}) {
+      if (c.hidden % hs) return "Fastformer: hidden must be a multiple of n_head and dec_n_head";
+      if (hs != 1 && hs != 2 && hs != 4 && hs != 8) return "Fastformer: n_head / dec_n_head (the head SIZE of this block) must be 1, 2, 4 or 8";
+      if (c.hidden / hs > 512) return "Fastformer: at most 512 heads (hidden / n_head)";
+    }
   }
   if (c.n_bins != 256) return "n_bins must be 256";
   if (c.pitch_emb_rows != 0 && !in(c.pitch_emb_rows, c.n_bins, BIG)) return "pitch_emb_rows must cover n_bins";

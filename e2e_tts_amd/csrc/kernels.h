@@ -7,7 +7,8 @@
 
 namespace e2etts {
 
-enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LRELU = 3, ACT_SWISH = 4 /* v * sigmoid(v), Conformer FFN */ };
+enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2, ACT_LRELU = 3, ACT_SWISH = 4 /* v * sigmoid(v), Conformer FFN */,
+           ACT_GELU = 5 /* 0.5 v (1 + erf(v / sqrt 2)), Fastformer FFN */ };
 
 // Compact grid of a RAGGED batch.  A launch whose utterances need different numbers of rows must not contain workgroups that find nothing
 // to do: the hardware places workgroups on CUs in a fixed rotation, not by load, so runs of workgroups that exit at once leave some
@@ -318,6 +319,19 @@ const char* launch_dwconv_glu_swish(const float* in, const float* w, const float
 // pos_x3 (optional): the same table as bf16 hi | lo halves per row (packer: `att.pos.x3`) -> the split-precision kernel (decoder, bf16x3 mode).
 const char* launch_rel_attention(const float* qkv, const float* pos, int pos_rows, const float* u, const float* v, float* out, int B, int N,
                                  int H, int n_head, hipStream_t s, const float* pos_x3 = nullptr);
+
+// Fastformer additive attention (reference U/blocks/fastformer.py:218-267; fastformer.hip).  One sequence-axis softmax-and-pool:
+// out[b, h * hs + d] = sum_n softmax_n(s[b, h, :])[n] * v'[b, n, h * hs + d], with v' = v (scale == null) or v * scale[b, :] formed on the
+// fly, s = fl(fl((v'[b, n, :] . W[h, :] + bl[h]) / sqrt(hs)) + (n < lens[b] ? -10000 : 0)) -- the reference's inverted mask (:223-225).
+// v [B, N, >= H] with row stride v_ld (batch stride N * v_ld); wl the logit weights TRANSPOSED, [H][H / hs]; bl [H / hs]; out [B, H].
+// hs in {1, 2, 4, 8}, H <= 1024, H / hs <= 512.  ws: ff_pool_workspace_bytes() of scratch for the partial (max, sum, weighted sum) triples
+// of the ff_pool_splits() row runs per utterance, merged in run order (no atomics: bit-identical from run to run).
+const char* launch_ff_pool(const float* v, int v_ld, const float* scale, const float* wl, const float* bl, const int32_t* lens, float* out, float* ws,
+                           size_t ws_bytes, int B, int N, int H, int head_size, hipStream_t s);
+size_t ff_pool_workspace_bytes(int B, int N, int H, int head_size);
+int ff_pool_splits(int B, int N, int H, int head_size);
+// wv[b, n, :] = gk[b, :] * q[b, n, :] (:262) and qx[b, n, :] = q[b, n, :] + x[b, n, :]; q with row stride q_ld, the others dense [B, N, H]
+const char* launch_ff_scale(const float* q, int q_ld, const float* gk, const float* x, float* wv, float* qx, int B, int N, int H, hipStream_t s);
 
 // tempo change without pitch change (WSOLA; small_kernels.hip): x int16 [n_in] -> out int16 [n_out <= n_frames * n / 2 + n / 2]
 const char* launch_wsola(const int16_t* x, long long n_in, int16_t* out, long long n_out, double speed, int n, int delta, int n_frames,

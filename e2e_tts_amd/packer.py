@@ -210,6 +210,45 @@ def _pack_conformer(dims: EngineDims, A, out) -> None:
                     out[q + nm + ".x3"] = pack_x3(np.ascontiguousarray(out[q + nm]), 1, cin)
 
 
+def _pack_fastformer(dims: EngineDims, A, out) -> None:
+    """Fastformer stacks (reference U/blocks/fastformer.py:144-298) -> engine tensors `enc.N.*` / `dec.N.*` (bind_fastformer()).
+
+    query | key stacked into one [2H, H] projection; the two logit layers stored ONCE per side (`enc.ff.wql` ...), transposed to [H, NH] so
+    that the pooling kernel's threads -- one per head -- read consecutive words: every layer's `to_*_attn_logits` are layer 0's modules
+    (:161-165), state_dict() repeats them under each layer's name, and a checkpoint whose later copy differs is not one this module wrote."""
+    H, F = dims.hidden, dims.ffn_dim
+    need = _need
+    for side, short, n in (("encoder", "enc", dims.enc_layers), ("decoder", "dec", dims.dec_layers)):
+        NH, _ = dims.ff_heads(short)
+        for l in range(n):
+            p = f"{side}.layer_stack.layers.{l}"
+            q = f"{short}.{l}."
+            for w, nm in (("to_q_attn_logits", "ql"), ("to_k_attn_logits", "kl")):
+                wl = need(A, f"{p}.0.fn.{w}.weight", (NH, H))
+                bl = need(A, f"{p}.0.fn.{w}.bias", (NH,))
+                if l == 0:
+                    out[f"{short}.ff.w{nm}"] = np.ascontiguousarray(wl.T)
+                    out[f"{short}.ff.b{nm}"] = bl
+                elif not (np.array_equal(wl.T, out[f"{short}.ff.w{nm}"]) and np.array_equal(bl, out[f"{short}.ff.b{nm}"])):
+                    raise ValueError(f"{p}.0.fn.{w} differs from layer 0's: the Fastformer stack ties these projections across layers "
+                                     "(reference U/blocks/fastformer.py:161-165)")
+            out[q + "att.ln.g"] = need(A, f"{p}.0.norm.weight", (H,))
+            out[q + "att.ln.b"] = need(A, f"{p}.0.norm.bias", (H,))
+            out[q + "att.wqk"] = np.concatenate([need(A, f"{p}.0.fn.{w}.weight", (H, H)) for w in ("query", "key")], 0)
+            out[q + "att.bqk"] = np.concatenate([need(A, f"{p}.0.fn.{w}.bias", (H,)) for w in ("query", "key")], 0)
+            out[q + "att.wt"] = need(A, f"{p}.0.fn.transform.weight", (H, H))
+            out[q + "att.bt"] = need(A, f"{p}.0.fn.transform.bias", (H,))
+            out[q + "ffn.ln.g"] = need(A, f"{p}.1.norm.weight", (H,))
+            out[q + "ffn.ln.b"] = need(A, f"{p}.1.norm.bias", (H,))
+            out[q + "ffn.w1"] = conv_rows(need(A, f"{p}.1.fn.w_1.weight", (F, H, dims.ffn_k1)))
+            out[q + "ffn.b1"] = need(A, f"{p}.1.fn.w_1.bias", (F,))
+            out[q + "ffn.w2"] = conv_rows(need(A, f"{p}.1.fn.w_2.weight", (H, F, dims.ffn_k2)))
+            out[q + "ffn.b2"] = need(A, f"{p}.1.fn.w_2.bias", (H,))
+            if short == "dec":  # as for the FFT blocks: only the decoder's GEMMs may run split-precision; logits and pooling never do
+                for nm, kw, cin in (("att.wqk", 1, H), ("att.wt", 1, H), ("ffn.w1", dims.ffn_k1, H), ("ffn.w2", dims.ffn_k2, F)):
+                    out[q + nm + ".x3"] = pack_x3(np.ascontiguousarray(out[q + nm]), kw, cin)
+
+
 def _pack_acoustic(dims: EngineDims, A, out) -> None:
     H = dims.hidden
     need = _need
@@ -220,6 +259,8 @@ def _pack_acoustic(dims: EngineDims, A, out) -> None:
     out["spk.emb"] = need(A, "speaker_emb.weight", (dims.n_speakers, H))
     if dims.block_type == 1:
         _pack_conformer(dims, A, out)
+    if dims.block_type == 2:
+        _pack_fastformer(dims, A, out)
     for side, short, n in (("encoder", "enc", dims.enc_layers), ("decoder", "dec", dims.dec_layers)):
         for l in range(n if dims.block_type == 0 else 0):
             p = f"{side}.layer_stack.{l}"

@@ -95,7 +95,28 @@ def acoustic_manifest(config: dict, n_speakers: int, n_symbols: int = N_SYMBOLS)
             add(f"{q}.7.conv.bias", (H,), "b")
             add(f"{p}.4.weight", (H,), "gamma")
             add(f"{p}.4.bias", (H,), "beta")
-        for l in range(0 if bt == "conformer" else layers):
+        for l in range(layers if bt == "fastformer" else 0):
+            # FFTBlock.state_dict() of U/blocks/fastformer.py:144-165: PreNorm(FastAttention), PreNorm(PositionwiseFeedForward) per layer.
+            # hidden / n_head heads of size n_head (:152,190-191); the two logit layers of every layer ARE layer 0's modules (:161-165), and
+            # state_dict() lists them under each layer's name: "tied" entries repeat layer 0's values
+            p = f"{side}.layer_stack.layers.{l}"
+            NH = H // tr[f"{side}_head"]
+            add(f"{p}.0.norm.weight", (H,), "gamma")
+            add(f"{p}.0.norm.bias", (H,), "beta")
+            for w in ("query", "key", "transform"):
+                add(f"{p}.0.fn.{w}.weight", (H, H), "w")
+                add(f"{p}.0.fn.{w}.bias", (H,), "b")
+            for w, kind in (("to_q_attn_logits", "ff_qlogit"), ("to_k_attn_logits", "ff_klogit")):
+                first = f"{side}.layer_stack.layers.0.0.fn.{w}"
+                add(f"{p}.0.fn.{w}.weight", (NH, H), kind if l == 0 else f"tied:{first}.weight")
+                add(f"{p}.0.fn.{w}.bias", (NH,), "b" if l == 0 else f"tied:{first}.bias")
+            add(f"{p}.1.norm.weight", (H,), "gamma")
+            add(f"{p}.1.norm.bias", (H,), "beta")
+            add(f"{p}.1.fn.w_1.weight", (F, H, k1), "w")
+            add(f"{p}.1.fn.w_1.bias", (F,), "b")
+            add(f"{p}.1.fn.w_2.weight", (H, F, k2), "w")
+            add(f"{p}.1.fn.w_2.bias", (H,), "b")
+        for l in range(0 if bt in ("conformer", "fastformer") else layers):
             p = f"{side}.layer_stack.{l}"
             for w in ("w_qs", "w_ks", "w_vs", "fc"):
                 add(f"{p}.slf_attn.{w}.weight", (H, H), "w")
@@ -215,6 +236,13 @@ def _draw(rng: np.random.Generator, name: str, shape: Shape, kind: str, *, stats
     if kind in ("w", "wn"):
         fan_in = int(np.prod(shape[1:]))
         return (rng.standard_normal(shape) * (1.0 / math.sqrt(fan_in))).astype(f32)
+    if kind in ("ff_qlogit", "ff_klogit"):
+        # Fastformer logit layers: scaled so that the logits are of order 1 and the sequence softmaxes are far from uniform (the module's own
+        # init, std 0.02, would leave them flat and a parity test blind).  The key logits see k * pooled_query, a few times smaller than q
+        fan_in = shape[-1]
+        return (rng.standard_normal(shape) * ((2.0 if kind == "ff_qlogit" else 6.0) / math.sqrt(fan_in))).astype(f32)
+    if kind.startswith("tied:"):
+        return None  # copied from the named tensor after the draw (no random numbers consumed)
     if kind == "wn_t":  # ConvTranspose1d weight [Cin, Cout, k]; each output sees Cin * k / stride taps
         fan_in = shape[0] * 2
         return (rng.standard_normal(shape) * (1.0 / math.sqrt(fan_in))).astype(f32)
@@ -276,6 +304,9 @@ def _fill(manifest, seed: int, **kw) -> Dict[str, np.ndarray]:
     for name in sorted(manifest):
         shape, kind = manifest[name]
         out[name] = _draw(rng, name, shape, kind, **kw)
+    for name in manifest:
+        if manifest[name][1].startswith("tied:"):
+            out[name] = out[manifest[name][1][len("tied:"):]].copy()
     # weight_g = ||v|| * (1 + 0.1 N) over all dims but 0 (weight_norm dim=0; V/generator.py:18,23,33)
     for name in sorted(manifest):
         if manifest[name][1] == "wn_g":

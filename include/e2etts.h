@@ -99,7 +99,10 @@ typedef struct e2etts_config {
   int32_t voc_istft_hop;  /* iSTFT hop; prod(voc_up_rate) * voc_istft_hop == hop_length */
   int32_t block_type;     /* encoder / decoder block: 0 = FFT block (U/blocks/transformer.py:178-189); 1 = Conformer block
                              (U/blocks/conformer.py:171-255): n_head relative-position heads, ffn_dim = hidden x ffn_expansion_factor,
-                             ffn_k1 = depthwise kernel size */
+                             ffn_k1 = depthwise kernel size; 2 = Fastformer block (U/blocks/fastformer.py:144-298): additive attention with
+                             heads and head size SWAPPED -- FastAttention is built with dim_head = hidden / n_head and runs
+                             hidden / n_head heads of size n_head (:152,190-191; hidden 384, n_head 2: 192 heads of size 2); n_head
+                             (and dec_n_head) must be 1, 2, 4 or 8 with hidden / n_head <= 512 and hidden <= 1024; FFN conv ffn_k1 -> GELU -> 1 */
   int32_t energy_layers;  /* energy predictor depth / kernel (U/layers.py:92,96: ener_predictor_layers / ener_predictor_kernel); 0 = the pitch */
   int32_t energy_kernel;  /* predictor's (var_layers / var_kernel, U/layers.py:54,58), which is what the shipped model_config.yaml has */
   int32_t dec_n_head;     /* attention heads of the decoder's blocks (decoder_head, U/blocks/transformer.py:105, conformer.py:108); 0 = n_head, which then
