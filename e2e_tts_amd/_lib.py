@@ -22,6 +22,8 @@ ABI_VERSION = 4   # E2ETTS_ABI_VERSION of the include/e2etts.h this binding mirr
 # E2ETTS_PRECISION_* of include/e2etts.h: 'bf16' and 'bf16_act' are vocoder-only ('bf16': plain bf16 operands, the long-form streaming
 # config's arithmetic; 'bf16_act': every activation bf16, rounded where the reference's module run with .bfloat16() rounds)
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2, "bf16_act": 3}
+# what the vocoder accepts: the above and "fp16_act" (E2ETTS_PRECISION_FP16_ACT: fp16 activations, as the reference's HifiGan.half())
+VOCODER_PRECISIONS = {**PRECISIONS, "fp16_act": 4}
 
 E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM, E_KEY = 0, -1, -2, -3, -4, -5
 
@@ -476,9 +478,11 @@ class Engine:
         """'fp32' (exact fp32 MFMA: the engine's default and the reference's arithmetic) or 'bf16x3' (split-precision bf16 MFMA: the
         opt-in fast mode, PCM within 1 LSB of the reference's) for the vocoder and for the decoder + mel_linear + postnet (defaults
         to the vocoder's choice).  Encoder / variance adaptor: always fp32.  Vocoder only: 'bf16' (plain bf16 operands, fp32 activations) and
-        'bf16_act' (bf16 activations rounded where the reference's .bfloat16() module rounds; HiFi-GAN tail, widths multiple of 32)."""
-        dec = decoder if decoder is not None else ("bf16x3" if vocoder in ("bf16", "bf16_act") else vocoder)
-        self._check(self.lib.e2etts_set_precision(self._h, PRECISIONS[vocoder], PRECISIONS[dec]), "e2etts_set_precision")
+        'bf16_act' (bf16 activations rounded where the reference's .bfloat16() module rounds; HiFi-GAN tail, widths multiple of 32) and
+        'fp16_act' (the same with fp16 activations, as the reference's .half() module: ~1e-4 from the fp32 waveform instead of 6e-4 .. 9e-4)."""
+        dec = decoder if decoder is not None else ("bf16x3" if vocoder in ("bf16", "bf16_act", "fp16_act") else vocoder)
+        # the engine refuses a vocoder-only mode as the decoder precision, and says so
+        self._check(self.lib.e2etts_set_precision(self._h, VOCODER_PRECISIONS[vocoder], VOCODER_PRECISIONS[dec]), "e2etts_set_precision")
 
     @_locked
     def set_ragged(self, on: bool = True):

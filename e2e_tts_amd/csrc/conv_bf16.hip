@@ -66,25 +66,59 @@ __device__ __forceinline__ unsigned bc_pack(float a, float b) {
   return __builtin_bit_cast(unsigned, r);
 }
 
-// ---- precision "bf16_act" (E2ETTS_PRECISION_BF16_ACT, include/e2etts.h): bf16 tensors at the kernels' global edges, every elementwise
-// step computed in fp32 on bf16 values and rounded to nearest-even (the A16 template parameter; A16 = false is the mode-2 code, untouched)
-__device__ __forceinline__ float bc_rnd(float x) { return (float)(__bf16)x; }
-__device__ __forceinline__ float4 bc_rnd4(float4 v) { return make_float4(bc_rnd(v.x), bc_rnd(v.y), bc_rnd(v.z), bc_rnd(v.w)); }
-__device__ __forceinline__ float4 bc_unpack4(uint2 u) {   // four bf16 -> fp32 (exact)
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+// ---- precisions "bf16_act" / "fp16_act" (E2ETTS_PRECISION_BF16_ACT / _FP16_ACT, include/e2etts.h): 16-bit tensors at the kernels' global
+// edges, every elementwise step computed in fp32 on 16-bit values and rounded to nearest-even.  The A16 template parameter is the element
+// kind: A16_OFF is the mode-2 code, untouched; A16_BF16 unpacks with a shift; A16_FP16 (IEEE binary16) needs real conversions --
+// v_cvt_f32_f16 / v_cvt_pk_f16_f32 (a plain _Float16 cast: nearest-even, overflow to infinity, subnormals kept; never the
+// round-toward-zero pack) -- and the fp16 MFMA.
+constexpr int A16_OFF = 0, A16_BF16 = 1, A16_FP16 = 2;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
+template <int K>
+__device__ __forceinline__ unsigned bc_pack(float a, float b) {   // two fp32 -> two elements of kind K (A16_OFF: bf16, mode 2's operands)
+  if constexpr (K == A16_FP16) {
+    const f16x2 r = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(unsigned, r);
+  } else {
+    return bc_pack(a, b);
+  }
 }
-// utterance `off` elements into a bf16 addend tensor (typed const float* as BConvParams::in_add is), or null
+template <int K>
+__device__ __forceinline__ float bc_lo(unsigned u) {   // the low / high element of a packed pair -> fp32 (exact)
+  if constexpr (K == A16_FP16) return (float)__builtin_bit_cast(f16x2, u)[0];
+  else return __uint_as_float(u << 16);
+}
+template <int K>
+__device__ __forceinline__ float bc_hi(unsigned u) {
+  if constexpr (K == A16_FP16) return (float)__builtin_bit_cast(f16x2, u)[1];
+  else return __uint_as_float(u & 0xffff0000u);
+}
+template <int K>
+__device__ __forceinline__ float bc_rnd(float x) {
+  if constexpr (K == A16_FP16) return (float)(_Float16)x;
+  else return (float)(__bf16)x;
+}
+template <int K>
+__device__ __forceinline__ float4 bc_rnd4(float4 v) { return make_float4(bc_rnd<K>(v.x), bc_rnd<K>(v.y), bc_rnd<K>(v.z), bc_rnd<K>(v.w)); }
+template <int K>
+__device__ __forceinline__ float4 bc_unpack4(uint2 u) {   // four 16-bit elements -> fp32 (exact)
+  return make_float4(bc_lo<K>(u.x), bc_hi<K>(u.x), bc_lo<K>(u.y), bc_hi<K>(u.y));
+}
+// utterance `off` elements into a 16-bit addend tensor (typed const float* as BConvParams::in_add is), or null.  (Here and below, 16-bit
+// tensors of either kind are addressed through __bf16*: only the element size matters.)
 __device__ __forceinline__ const float* bc_addend16(const float* a, long long off) {
   return a ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(a) + off) : nullptr;
 }
-__device__ __forceinline__ uint2 bc_pack4(float4 v) { return make_uint2(bc_pack(v.x, v.y), bc_pack(v.z, v.w)); }
-// bf16(lrelu(x)) of eight bf16 values
+template <int K>
+__device__ __forceinline__ uint2 bc_pack4(float4 v) { return make_uint2(bc_pack<K>(v.x, v.y), bc_pack<K>(v.z, v.w)); }
+// round(lrelu(x)) of eight 16-bit values
+template <int K>
 __device__ __forceinline__ uint4 bc_lrelu8(uint4 u, float slope) {
   unsigned w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const float lo = __uint_as_float(w[i] << 16), hi = __uint_as_float(w[i] & 0xffff0000u);
-    w[i] = bc_pack(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
+    const float lo = bc_lo<K>(w[i]), hi = bc_hi<K>(w[i]);
+    w[i] = bc_pack<K>(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
   }
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -113,8 +147,9 @@ __device__ __forceinline__ void bc_pipeline() {
 // batch is a round trip to L2 / HBM with the CU otherwise idle: 6-piece batches took 8 600 cycles for a 178-row x 256-channel slab).
 // in_add / in_div (fp32 input only): further tensors summed into the input while staging -- x = (((in + a0) + a1) + a2) / div, the order and
 // operations of accum_div_kernel (small_kernels.hip), whose launch and whose pass over the tensors this replaces.
-// A16 (bf16 input only): bf16(lrelu(x)) with the slope, the activation of precision "bf16_act" (a slope of 1 copies).
-template <bool IN_BF16, int SB, int NTHR = 256, bool A16 = false>
+// A16 (element kind; 16-bit input): round(lrelu(x)) with the slope, the activation of precisions "bf16_act" / "fp16_act" (a slope of 1
+// copies); an fp32 input (the mel) is rounded to the kind's elements.
+template <bool IN_BF16, int SB, int NTHR = 256, int A16 = A16_OFF>
 __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt, const int T, const int Cin, const int NCH, const int RS,
                                          const int t_first, const int srows, const float slope, const int tid,
                                          const float* a0 = nullptr, const float* a1 = nullptr, const float* a2 = nullptr, const float div = 1.0f) {
@@ -123,8 +158,8 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
   constexpr int esz = IN_BF16 ? 2 : 4;
   const __amdgpu_buffer_rsrc_t in_rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(in_utt), 0, (int)((long long)T * Cin * esz), 0x00020000);
-  if constexpr (IN_BF16 && A16) {
-    if (a0) {   // precision "bf16_act", joined: x = bf16(bf16(bf16(in + a0) + a1) + a2), bf16(x / div), then bf16(lrelu(x)); bf16 addends
+  if constexpr (IN_BF16 && A16 != A16_OFF) {
+    if (a0) {   // 16-bit activations, joined: x = r(r(r(in + a0) + a1) + a2), r(x / div), then r(lrelu(x)); 16-bit addends
       constexpr int SJ = 4;
       const int bytes = (int)((long long)T * Cin * 2);
       const __amdgpu_buffer_rsrc_t r0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a0), 0, bytes, 0x00020000);
@@ -154,12 +189,12 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
           unsigned o[4];
 #pragma unroll
           for (int h = 0; h < 4; ++h) {
-            float lo = __uint_as_float(xv[h] << 16), hi = __uint_as_float(xv[h] & 0xffff0000u);
-            lo = bc_rnd(lo + __uint_as_float(u0[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u0[h] & 0xffff0000u));
-            if (a1) { lo = bc_rnd(lo + __uint_as_float(u1[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u1[h] & 0xffff0000u)); }
-            if (a2) { lo = bc_rnd(lo + __uint_as_float(u2[h] << 16)); hi = bc_rnd(hi + __uint_as_float(u2[h] & 0xffff0000u)); }
-            if (div != 1.0f) { lo = bc_rnd(lo / div); hi = bc_rnd(hi / div); }
-            o[h] = bc_pack(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
+            float lo = bc_lo<A16>(xv[h]), hi = bc_hi<A16>(xv[h]);
+            lo = bc_rnd<A16>(lo + bc_lo<A16>(u0[h])); hi = bc_rnd<A16>(hi + bc_hi<A16>(u0[h]));
+            if (a1) { lo = bc_rnd<A16>(lo + bc_lo<A16>(u1[h])); hi = bc_rnd<A16>(hi + bc_hi<A16>(u1[h])); }
+            if (a2) { lo = bc_rnd<A16>(lo + bc_lo<A16>(u2[h])); hi = bc_rnd<A16>(hi + bc_hi<A16>(u2[h])); }
+            if (div != 1.0f) { lo = bc_rnd<A16>(lo / div); hi = bc_rnd<A16>(hi / div); }
+            o[h] = bc_pack<A16>(fmaxf(lo, lo * slope), fmaxf(hi, hi * slope));
           }
           uint4 r = make_uint4(o[0], o[1], o[2], o[3]);
           if (!ok[i]) r = make_uint4(0, 0, 0, 0);
@@ -242,14 +277,14 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
       uint4 v;
       if constexpr (IN_BF16) {
         v = __builtin_bit_cast(uint4, ra[i]);
-        if constexpr (A16) {
-          if (slope != 1.0f) v = bc_lrelu8(v, slope);
+        if constexpr (A16 != A16_OFF) {
+          if (slope != 1.0f) v = bc_lrelu8<A16>(v, slope);
         }
       } else {
         float4 a = ra[i], c = rb[i];
         a.x = fmaxf(a.x, a.x * slope); a.y = fmaxf(a.y, a.y * slope); a.z = fmaxf(a.z, a.z * slope); a.w = fmaxf(a.w, a.w * slope);
         c.x = fmaxf(c.x, c.x * slope); c.y = fmaxf(c.y, c.y * slope); c.z = fmaxf(c.z, c.z * slope); c.w = fmaxf(c.w, c.w * slope);
-        v.x = bc_pack(a.x, a.y); v.y = bc_pack(a.z, a.w); v.z = bc_pack(c.x, c.y); v.w = bc_pack(c.z, c.w);
+        v.x = bc_pack<A16>(a.x, a.y); v.y = bc_pack<A16>(a.z, a.w); v.z = bc_pack<A16>(c.x, c.y); v.w = bc_pack<A16>(c.z, c.w);
       }
       if (!ok[i]) v = make_uint4(0, 0, 0, 0);
       if (dst[i] >= 0) *reinterpret_cast<uint4*>(smem + dst[i]) = v;
@@ -259,7 +294,8 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
 
 // ---- the K loop, shared by both kernels (macros: the ring slots and register sets must be compile-time constants, and counters updated
 // inside lambdas ended up in scratch memory -- conv_ksplit.hip).  Expects in scope: D, MT, NT, lane, wr[D][2][NT], xb[2][2][MT],
-// acc[MT][NT], RS, and the lambdas request(slot, rsrc, nt0, NU, u), readx(par, a_lane, off), compute(slot).
+// acc[MT][NT], RS, A16 (the element kind: picks the MFMA; xb is typed bf16x8 for either kind, it only carries the bits), and the lambdas
+// request(slot, rsrc, nt0, NU, u), readx(par, a_lane, off), compute(slot).
 //
 // The main loop walks whole groups of D units with NO condition around a unit: hipcc's s_waitcnt insertion is path-insensitive, and with
 // an `if (unit exists)` around each slot it assumed the path on which only slot 0 ran and waited for vmcnt(3) at the head of every group
@@ -340,8 +376,12 @@ __device__ __forceinline__ void bc_stage(unsigned char* smem, const void* in_utt
     _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                                                   \
       _Pragma("unroll") for (int n = 0; n < NT; ++n) {                                                                                 \
         const bf16x8 w = __builtin_bit_cast(bf16x8, wr[S][ks][n]);                                                                     \
-        _Pragma("unroll") for (int m = 0; m < MT; ++m)                                                                                 \
-          acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, xb[P][ks][m], acc[m][n], 0, 0, 0);                                    \
+        _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                                               \
+          if constexpr (A16 == A16_FP16)                                                                                               \
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, xb[P][ks][m]), acc[m][n], 0, 0, 0); \
+          else                                                                                                                         \
+            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w, xb[P][ks][m], acc[m][n], 0, 0, 0);                                  \
+        }                                                                                                                              \
       }                                                                                                                                \
   };
 
@@ -359,7 +399,7 @@ struct BPairGroup {
   PairParams p[BC_GROUP_MAX];
 };
 
-template <int MT, int NT, int WGM, int WGN, int D, bool IN_BF16, bool A16 = false>
+template <int MT, int NT, int WGM, int WGN, int D, bool IN_BF16, int A16 = A16_OFF>
 __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp) {
   static_assert(WGM * WGN == 4, "four wavefronts per workgroup");
   // the member this workgroup serves (uniform): its parameters stay in the kernel-argument segment, read through scalar loads
@@ -439,7 +479,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
   if (p.bias) bias4 = *reinterpret_cast<const float4*>(p.bias + ecol);
   const long long ob = (long long)b * p.T * p.Cout;
   float4 resv[MT][PASSES], accv[MT][PASSES];
-  if constexpr (A16) {   // bf16 residual and running sum (the sum is the bf16 output itself)
+  if constexpr (A16 != A16_OFF) {   // bf16 residual and running sum (the sum is the bf16 output itself)
     const __bf16* res16 = reinterpret_cast<const __bf16*>(p.res);
     const __bf16* out16 = reinterpret_cast<const __bf16*>(p.out_b);
 #pragma unroll
@@ -447,8 +487,8 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
 #pragma unroll
       for (int ps = 0; ps < PASSES; ++ps) {
         const int t = min(t0 + (wm * MT + m) * 32 + ps * RPP + prow, p.T - 1);
-        if (p.res) resv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(res16 + ob + (long long)t * p.Cout + ecol));
-        if (p.accumulate) accv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(out16 + ob + (long long)t * p.Cout + ecol));
+        if (p.res) resv[m][ps] = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(res16 + ob + (long long)t * p.Cout + ecol));
+        if (p.accumulate) accv[m][ps] = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(out16 + ob + (long long)t * p.Cout + ecol));
       }
   } else if (p.res) {
 #pragma unroll
@@ -483,26 +523,26 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
       const int row = ps * RPP + prow;
       const int t = tb + row;
       float4 v = *reinterpret_cast<const float4*>(patch + row * ELD + pc4);
-      if constexpr (A16) {   // bias -> round -> (act -> round) -> (+ residual -> round) -> (+ sum -> round -> / div -> round)
+      if constexpr (A16 != A16_OFF) {   // bias -> round -> (act -> round) -> (+ residual -> round) -> (+ sum -> round -> / div -> round)
         v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-        v = bc_rnd4(v);
+        v = bc_rnd4<A16>(v);
         if (p.act_slope != 1.0f) {
           v.x = fmaxf(v.x, v.x * p.act_slope); v.y = fmaxf(v.y, v.y * p.act_slope);
           v.z = fmaxf(v.z, v.z * p.act_slope); v.w = fmaxf(v.w, v.w * p.act_slope);
-          v = bc_rnd4(v);
+          v = bc_rnd4<A16>(v);
         }
         if (p.res) {
           const float4 rv = resv[m][ps];
           v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-          v = bc_rnd4(v);
+          v = bc_rnd4<A16>(v);
         }
         if (p.accumulate) {
           const float4 ov = accv[m][ps];
           v.x += ov.x; v.y += ov.y; v.z += ov.z; v.w += ov.w;
-          v = bc_rnd4(v);
-          if (p.out_div != 1.0f) v = bc_rnd4(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
+          v = bc_rnd4<A16>(v);
+          if (p.out_div != 1.0f) v = bc_rnd4<A16>(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
         }
-        if (t < p.T) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p.out_b) + ob + (long long)t * p.Cout + ecol) = bc_pack4(v);
+        if (t < p.T) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(p.out_b) + ob + (long long)t * p.Cout + ecol) = bc_pack4<A16>(v);
         continue;
       }
       v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
@@ -549,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void conv_bf16_kernel(const BConvGroup grp)
 // half of what the L1 can deliver), the weights of conv2's first D units requested before conv1's epilogue.
 // A16 (precision "bf16_act"): x, the residual, the running sum and out are bf16; intermediate = bf16(lrelu(bf16(conv1 + b1))) -- rounded
 // twice --, out = bf16(bf16(conv2 + b2) + x) (then bf16(+ sum), bf16(/ div)).
-template <int MT, int WGM, int WGN, int D, bool ACCUM, bool A16 = false>
+template <int MT, int WGM, int WGN, int D, bool ACCUM, int A16 = A16_OFF>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPairGroup grp) {
   static_assert(WGM * WGN == 4 || WGM * WGN == 8, "four or eight wavefronts per workgroup (eight: 256 channels, one workgroup per CU)");
   constexpr int NTHR = 64 * WGM * WGN;
@@ -589,7 +629,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
   // (A16: bf16 elements; the fp32 form is written as before so that the mode-2 instantiations compile as they did)
   const float* x_b = A16 ? reinterpret_cast<const float*>(reinterpret_cast<const __bf16*>(p.x) + (long long)b * p.x_bs) : p.x + (long long)b * p.x_bs;
   float* out_b = A16 ? reinterpret_cast<float*>(reinterpret_cast<__bf16*>(p.out) + (long long)b * p.out_bs) : p.out + (long long)b * p.out_bs;
-  bc_stage<A16, (NTHR == 512 ? 8 : 12), NTHR, A16>(smem, x_b, p.T, C, NCH, RS, i0 - pad1, BMI + halo1, p.slope, tid);
+  bc_stage<(A16 != A16_OFF), (NTHR == 512 ? 8 : 12), NTHR, A16>(smem, x_b, p.T, C, NCH, RS, i0 - pad1, BMI + halo1, p.slope, tid);
   BC_STAMP(st1);
   __syncthreads();   // slab visible
   BC_STAMP(st2);
@@ -627,14 +667,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
         float v[4] = {acc[m][0][4 * q] + bq[q].x, acc[m][0][4 * q + 1] + bq[q].y, acc[m][0][4 * q + 2] + bq[q].z, acc[m][0][4 * q + 3] + bq[q].w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          if constexpr (A16) v[i] = bc_rnd(v[i]);   // the conv's own rounding, before the activation's
+          if constexpr (A16 != A16_OFF) v[i] = bc_rnd<A16>(v[i]);   // the conv's own rounding, before the activation's
           v[i] = fmaxf(v[i], v[i] * p.slope);
           v[i] = ok ? v[i] : 0.f;
           acc[m][0][4 * q + i] = 0.f;
         }
         uint2 h;
-        h.x = bc_pack(v[0], v[1]);
-        h.y = bc_pack(v[2], v[3]);
+        h.x = bc_pack<A16>(v[0], v[1]);
+        h.y = bc_pack<A16>(v[2], v[3]);
         *reinterpret_cast<uint2*>(dst + q * 16) = h;
       }
     }
@@ -660,9 +700,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
 #pragma unroll
     for (int ps = 0; ps < PASSES; ++ps) {
       const int t = min(max(o0 + wm * (32 * MT) + m * 32 + ps * RPP + prow, 0), p.T - 1);
-      if constexpr (A16) {
-        resv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)t * C + ecol));
-        if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)t * C + ecol)); }
+      if constexpr (A16 != A16_OFF) {
+        resv[m][ps] = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)t * C + ecol));
+        if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)t * C + ecol)); }
       } else {
         resv[m][ps] = *reinterpret_cast<const float4*>(x_b + (long long)t * C + ecol);
         if constexpr (ACCUM) { if (p.accumulate) accv[m][ps] = *reinterpret_cast<const float4*>(out_b + (long long)t * C + ecol); }
@@ -686,19 +726,19 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void pair_bf16_kernel(const BPai
       const int row = ps * RPP + prow;
       const int t = o0 + rb + row;
       float4 v = *reinterpret_cast<const float4*>(patch + row * ELD + pc4);
-      if constexpr (A16) {
+      if constexpr (A16 != A16_OFF) {
         v.x += bias2.x; v.y += bias2.y; v.z += bias2.z; v.w += bias2.w;
-        v = bc_rnd4(v);
+        v = bc_rnd4<A16>(v);
         const float4 rv = resv[m][ps];
         v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-        v = bc_rnd4(v);
+        v = bc_rnd4<A16>(v);
         if (ACCUM && p.accumulate) {
           const float4 ov = accv[m][ps];
           v.x += ov.x; v.y += ov.y; v.z += ov.z; v.w += ov.w;
-          v = bc_rnd4(v);
-          if (p.out_div != 1.0f) v = bc_rnd4(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
+          v = bc_rnd4<A16>(v);
+          if (p.out_div != 1.0f) v = bc_rnd4<A16>(make_float4(v.x / p.out_div, v.y / p.out_div, v.z / p.out_div, v.w / p.out_div));
         }
-        if (t < t_end && rb + row < BMO) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)t * C + ecol) = bc_pack4(v);
+        if (t < t_end && rb + row < BMO) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)t * C + ecol) = bc_pack4<A16>(v);
         continue;
       }
       v.x += bias2.x; v.y += bias2.y; v.z += bias2.z; v.w += bias2.w;
@@ -752,7 +792,7 @@ struct BRbGroup {
 // staging) -- which is what the 32-channel stage of a 48 kHz window (35 MB per tensor) spends its time on.
 // A16 (precision "bf16_act"): x and out are bf16; I = bf16(lrelu(bf16(c1 + b1))), x_{m+1} = bf16(bf16(c2 + b2) + x_m) -- the residual stream
 // stays in registers, as bf16 values --, the stage sum S = bf16(S + x_n) in member order and bf16(S / n).
-template <int MT, int WGM, int WGN, int D, bool ACCUM, bool STAGE, bool A16 = false>
+template <int MT, int WGM, int WGN, int D, bool ACCUM, bool STAGE, int A16 = A16_OFF>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kernel(const BRbGroup grp) {
   constexpr int NT = 1;
   constexpr int NWAVE = WGM * WGN, NTHR = 64 * NWAVE;
@@ -838,7 +878,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
       for (int ps = 0; ps < PASSES; ++ps) {
         const int g = origin + wm * (32 * MT) + m * 32 + ps * RPP + prow;
         float4 v;
-        if constexpr (A16) v = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
+        if constexpr (A16 != A16_OFF) v = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(x_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
         else v = *reinterpret_cast<const float4*>(x_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
         rowv[m][ps] = (g >= 0 && g < T) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -880,7 +920,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
           float v[4] = {src[m][4 * q], src[m][4 * q + 1], src[m][4 * q + 2], src[m][4 * q + 3]};
           if (bias) {
             v[0] += bq[q].x; v[1] += bq[q].y; v[2] += bq[q].z; v[3] += bq[q].w;
-            if constexpr (A16) { v[0] = bc_rnd(v[0]); v[1] = bc_rnd(v[1]); v[2] = bc_rnd(v[2]); v[3] = bc_rnd(v[3]); }   // the conv's rounding
+            if constexpr (A16 != A16_OFF) { v[0] = bc_rnd<A16>(v[0]); v[1] = bc_rnd<A16>(v[1]); v[2] = bc_rnd<A16>(v[2]); v[3] = bc_rnd<A16>(v[3]); }   // the conv's rounding
           }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
@@ -888,8 +928,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
             v[i] = ok ? v[i] : 0.f;
           }
           uint2 h;
-          h.x = bc_pack(v[0], v[1]);
-          h.y = bc_pack(v[2], v[3]);
+          h.x = bc_pack<A16>(v[0], v[1]);
+          h.y = bc_pack<A16>(v[2], v[3]);
           *reinterpret_cast<uint2*>(dst + q * 16) = h;
         }
       }
@@ -954,11 +994,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
         const float4 bv = *reinterpret_cast<const float4*>(p.b2[pm] + wn * 32 + 8 * q + 4 * lh);
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-          if constexpr (A16) {
-            xres[m][4 * q + 0] = bc_rnd(bc_rnd(acc[m][0][4 * q + 0] + bv.x) + xres[m][4 * q + 0]);
-            xres[m][4 * q + 1] = bc_rnd(bc_rnd(acc[m][0][4 * q + 1] + bv.y) + xres[m][4 * q + 1]);
-            xres[m][4 * q + 2] = bc_rnd(bc_rnd(acc[m][0][4 * q + 2] + bv.z) + xres[m][4 * q + 2]);
-            xres[m][4 * q + 3] = bc_rnd(bc_rnd(acc[m][0][4 * q + 3] + bv.w) + xres[m][4 * q + 3]);
+          if constexpr (A16 != A16_OFF) {
+            xres[m][4 * q + 0] = bc_rnd<A16>(bc_rnd<A16>(acc[m][0][4 * q + 0] + bv.x) + xres[m][4 * q + 0]);
+            xres[m][4 * q + 1] = bc_rnd<A16>(bc_rnd<A16>(acc[m][0][4 * q + 1] + bv.y) + xres[m][4 * q + 1]);
+            xres[m][4 * q + 2] = bc_rnd<A16>(bc_rnd<A16>(acc[m][0][4 * q + 2] + bv.z) + xres[m][4 * q + 2]);
+            xres[m][4 * q + 3] = bc_rnd<A16>(bc_rnd<A16>(acc[m][0][4 * q + 3] + bv.w) + xres[m][4 * q + 3]);
           } else {
           xres[m][4 * q + 0] = (acc[m][0][4 * q + 0] + bv.x) + xres[m][4 * q + 0];
           xres[m][4 * q + 1] = (acc[m][0][4 * q + 1] + bv.y) + xres[m][4 * q + 1];
@@ -976,11 +1016,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
     if constexpr (STAGE) {   // the running sum over the ResBlocks, in the join's order: (S_0 + S_1) + S_2 ...
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
-        if constexpr (A16) {
+        if constexpr (A16 != A16_OFF) {
           if (mem == 0) sum[m] = xres[m];
           else
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sum[m][r] = bc_rnd(sum[m][r] + xres[m][r]);
+            for (int r = 0; r < 16; ++r) sum[m][r] = bc_rnd<A16>(sum[m][r] + xres[m][r]);
         } else {
           sum[m] = mem == 0 ? xres[m] : sum[m] + xres[m];
         }
@@ -1004,8 +1044,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
           const int g = origin + wm * (32 * MT) + m * 32 + ps * RPP + prow;
-          if constexpr (A16) {
-            const float4 u = bc_unpack4(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
+          if constexpr (A16 != A16_OFF) {
+            const float4 u = bc_unpack4<A16>(*reinterpret_cast<const uint2*>(reinterpret_cast<const __bf16*>(out_b) + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4));
             ov[ps] = f32x4_t{u.x, u.y, u.z, u.w};
           } else {
             ov[ps] = *reinterpret_cast<const f32x4_t*>(out_b + (long long)min(max(g, 0), T - 1) * C + wn * 32 + pc4);
@@ -1022,16 +1062,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN) / 4) void rb_bf16_kerne
         const int g = origin + row;
         const float4 pv = *reinterpret_cast<const float4*>(patch + (ps * RPP + prow) * ELD + pc4);
         f32x4_t v = {pv.x, pv.y, pv.z, pv.w};
-        if constexpr (A16) {
+        if constexpr (A16 != A16_OFF) {
           float4 w = pv;
           if (STAGE) {
-            if (grp.n > 1) w = bc_rnd4(make_float4(w.x / sdiv, w.y / sdiv, w.z / sdiv, w.w / sdiv));
+            if (grp.n > 1) w = bc_rnd4<A16>(make_float4(w.x / sdiv, w.y / sdiv, w.z / sdiv, w.w / sdiv));
           } else if (ACCUM && p.accumulate) {
             w.x += ov[ps][0]; w.y += ov[ps][1]; w.z += ov[ps][2]; w.w += ov[ps][3];
-            w = bc_rnd4(w);
-            if (p.out_div != 1.0f) w = bc_rnd4(make_float4(w.x / p.out_div, w.y / p.out_div, w.z / p.out_div, w.w / p.out_div));
+            w = bc_rnd4<A16>(w);
+            if (p.out_div != 1.0f) w = bc_rnd4<A16>(make_float4(w.x / p.out_div, w.y / p.out_div, w.z / p.out_div, w.w / p.out_div));
           }
-          if (row >= H && row < R - H && g < g_end) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)g * C + wn * 32 + pc4) = bc_pack4(w);
+          if (row >= H && row < R - H && g < g_end) *reinterpret_cast<uint2*>(reinterpret_cast<__bf16*>(out_b) + (long long)g * C + wn * 32 + pc4) = bc_pack4<A16>(w);
           continue;
         }
         if (STAGE) {
@@ -1067,6 +1107,26 @@ __global__ void bf16_image_kernel(const uint4* __restrict__ x3, uint4* __restric
   const int j = js + ((tap_split > 0 && t * 32 >= tap_split) ? 1 : 0);
   // one x3 row = 64 bf16 = 8 groups of 16 bytes: [hi k 0-7, 8-15, 16-23, 24-31 | lo ...]
   img[g] = x3[(((long long)n * KW + j) * nchunk + c) * 8 + ks * 2 + (lane >> 5)];
+}
+
+// the same image in fp16, for precision "fp16_act": straight from the fp32 weights [Cout][KW][Cin] (the weight-norm fold), rounded ONCE to
+// nearest-even (not from the bf16 hi + lo halves); channels >= Cin of the last chunk are zero.  One thread writes one lane's 16 bytes.
+__global__ void f16_image_kernel(const float* __restrict__ w, uint4* __restrict__ img, int Cout, int KW, int KWe, int Cin, int nchunk, int tap_split,
+                                 long long groups) {
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= groups) return;
+  const int lane = (int)(g & 63), ks = (int)((g >> 6) & 1);
+  long long r = g >> 7;
+  const int js = (int)(r % KWe); r /= KWe;
+  const int c = (int)(r % nchunk);
+  const int t = (int)(r / nchunk);
+  const int n = t * 32 + (lane & 31);
+  const int j = js + ((tap_split > 0 && t * 32 >= tap_split) ? 1 : 0);
+  const int c0 = c * 32 + ks * 16 + (lane >> 5) * 8;
+  float v[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) v[i] = (n < Cout && c0 + i < Cin) ? w[((long long)n * KW + j) * Cin + c0 + i] : 0.f;
+  img[g] = make_uint4(bc_pack<A16_FP16>(v[0], v[1]), bc_pack<A16_FP16>(v[2], v[3]), bc_pack<A16_FP16>(v[4], v[5]), bc_pack<A16_FP16>(v[6], v[7]));
 }
 
 struct BcCfg {
@@ -1125,12 +1185,16 @@ const char* bc_launch(const BConvParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, true, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (p0.act16 && p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
-  else if (p0.act16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  if (p0.act16 == A16_FP16 && p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true, A16_FP16>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  else if (p0.act16 == A16_FP16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false, A16_FP16>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  else if (p0.act16 && p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true, A16_BF16>), dim3((unsigned)nwg), dim3(256), lds, s, g);
+  else if (p0.act16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false, A16_BF16>), dim3((unsigned)nwg), dim3(256), lds, s, g);
   else if (p0.in_bf16) hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(256), lds, s, g);
   else hipLaunchKernelGGL((conv_bf16_kernel<MT, NT, WGM, WGN, D, false>), dim3((unsigned)nwg), dim3(256), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "conv_bf16: launch failed";
@@ -1167,8 +1231,9 @@ const char* conv_bf16_class(const BConvParams& p) {
 static const char* bc_check(const BConvParams& p) {
   if (!p.in || !p.wimg || (!p.out && !p.out_b)) return "conv_bf16: null pointer";
   if (!conv_bf16_supported(p)) return "conv_bf16: unsupported shape";
+  if (p.act16 < A16_OFF || p.act16 > A16_FP16) return "conv_bf16: act16 is 0 (off), 1 (bf16) or 2 (fp16)";
   if (p.act16 && (p.out || !p.out_b || p.outb_slope != 1.0f || (p.in_add[0] && !p.in_bf16)))
-    return "conv_bf16: bf16 activations write the bf16 output alone (and join bf16 inputs only)";
+    return "conv_bf16: 16-bit activations write the 16-bit output alone (and join 16-bit inputs only)";
   if (p.accumulate && !p.out && !p.act16) return "conv_bf16: accumulate needs the fp32 output";
   if (p.in_add[0] && p.in_bf16 && !p.act16) return "conv_bf16: in_add needs an fp32 input (or bf16 activations)";
   if ((p.in_add[1] && !p.in_add[0]) || (p.in_add[2] && !p.in_add[1])) return "conv_bf16: in_add must be filled from the front";
@@ -1238,12 +1303,16 @@ const char* pb_launch(const PairParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, false, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_bf16_kernel<MT, WGM, WGN, D, true, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (ps[0].mode == 3 && any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
-  else if (ps[0].mode == 3) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].mode == 4 && any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true, A16_FP16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].mode == 4) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false, A16_FP16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].mode == 3 && any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true, A16_BF16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].mode == 3) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false, A16_BF16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else if (any_acc) hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else hipLaunchKernelGGL((pair_bf16_kernel<MT, WGM, WGN, D, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "pair_bf16: launch failed";
@@ -1264,7 +1333,7 @@ int pb_mt(long long tiles4) {
 
 bool pair_bf16_supported(const PairParams& p) {
   static const bool on = !(getenv("E2ETTS_BPAIR") && atoi(getenv("E2ETTS_BPAIR")) == 0);   // tuning aid: 0 keeps resblock_pair.hip
-  if (!on || (p.mode != 2 && p.mode != 3) || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
+  if (!on || (p.mode != 2 && p.mode != 3 && p.mode != 4) || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
   if (!(p.C == 32 || p.C == 64 || p.C == 128 || p.C == 256) || !(p.KW & 1) || p.KW < 3 || p.KW > 15 || p.dil < 1 || p.dil * (p.KW - 1) > BC_MAX_HALO) return false;
   static const bool on256 = !(getenv("E2ETTS_BPAIR256") && atoi(getenv("E2ETTS_BPAIR256")) == 0);   // tuning aid
   if (p.C == 256 && !on256) return false;
@@ -1337,12 +1406,16 @@ const char* rb_launch(const RbParams* ps, int n, hipStream_t s) {
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, false, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, true, false, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (ps[0].act16 && any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
-  else if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].act16 == A16_FP16 && any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false, A16_FP16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].act16 == A16_FP16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false, A16_FP16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].act16 && any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false, A16_BF16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false, A16_BF16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else if (any_acc) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, true, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, false>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "rb_bf16: launch failed";
@@ -1372,10 +1445,12 @@ const char* rb_launch_stage(const RbParams* ps, int n, hipStream_t s) {
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true, A16_BF16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rb_bf16_kernel<MT, WGM, WGN, D, false, true, A16_FP16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_done = true;
   }
-  if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  if (ps[0].act16 == A16_FP16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true, A16_FP16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
+  else if (ps[0].act16) hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true, A16_BF16>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   else hipLaunchKernelGGL((rb_bf16_kernel<MT, WGM, WGN, D, false, true>), dim3((unsigned)nwg), dim3(64 * WGM * WGN), lds, s, g);
   return hipGetLastError() == hipSuccess ? nullptr : "rb_bf16: launch failed";
 }
@@ -1406,6 +1481,7 @@ const char* launch_rb_bf16_group(const RbParams* ps, int n, hipStream_t s) {
     if (!p.x || !p.out) return "rb_bf16: null pointer";
     if (p.B <= 0 || p.T <= 0) return "rb_bf16: bad dims";
     if (!rb_bf16_supported(p)) return "rb_bf16: unsupported launch";
+    if (p.act16 < A16_OFF || p.act16 > A16_FP16) return "rb_bf16: act16 is 0 (off), 1 (bf16) or 2 (fp16)";
     if (p.slope < 0.f || p.slope > 1.f) return "rb_bf16: slope must lie in [0, 1]";
     if (p.out_div != 1.0f && !p.accumulate) return "rb_bf16: out_div needs accumulate";
     if (((uintptr_t)p.x | (uintptr_t)p.out) & 15) return "rb_bf16: pointers must be 16-byte aligned";
@@ -1463,6 +1539,17 @@ const char* launch_bf16_image(const float* x3, void* img, int Cout, int KW, int 
   hipLaunchKernelGGL(bf16_image_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4*>(x3),
                      reinterpret_cast<uint4*>(img), Cout, KW, KWe, (Cin + 31) / 32, tap_split, groups);
   return hipGetLastError() == hipSuccess ? nullptr : "bf16_image: launch failed";
+}
+
+const char* launch_f16_image(const float* w, void* img, int Cout, int KW, int Cin, int tap_split, hipStream_t s) {
+  if (!w || !img) return "f16_image: null pointer";
+  if (Cout <= 0 || (Cout % 32) || KW <= 0 || Cin <= 0) return "f16_image: Cout must be a positive multiple of 32";
+  if (tap_split > 0 && (KW != 3 || (tap_split % 32))) return "f16_image: a polyphase image needs KW == 3 and tap_split % 32 == 0";
+  const int KWe = tap_split > 0 ? 2 : KW;
+  const long long groups = (long long)(bf16_image_bytes(Cout, KW, Cin, tap_split) / 16);
+  hipLaunchKernelGGL(f16_image_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, s, w, reinterpret_cast<uint4*>(img), Cout, KW, KWe, Cin,
+                     (Cin + 31) / 32, tap_split, groups);
+  return hipGetLastError() == hipSuccess ? nullptr : "f16_image: launch failed";
 }
 
 }  // namespace e2etts

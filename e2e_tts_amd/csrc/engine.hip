@@ -108,6 +108,11 @@ struct e2etts_engine {
   // copies (as fp32) of every vocoder bias and of conv_post's weights, keyed by the fp32 tensor; both built once at load
   std::map<const float*, std::pair<void*, int>> bimg_act;
   std::map<const float*, float*> r16_of;
+  // precision "fp16_act" only, built at the FIRST selection of the mode (an engine that never selects it owns none of this): the fp16
+  // images of every vocoder convolution, keyed by the fp32 weight tensor they are rounded from (launch_f16_image), and the fp16-rounded
+  // copies (as fp32) of the biases and of conv_post's weights
+  std::map<const float*, std::pair<void*, int>> himg_of;
+  std::map<const float*, float*> r16h_of;
   size_t frag_bytes = 0;
   bool ac_loaded = false, voc_loaded = false;
   std::vector<FFTLayer> enc, dec;
@@ -149,7 +154,8 @@ struct e2etts_engine {
   int64_t* h_mel = nullptr;  // pinned
   int last_B = 0, last_L = 0, last_T = 0, voc_B = 0, voc_T = 0;
   bool have_acoustic = false, have_wav = false;
-  int voc_precision = 0;  // 0: fp32 MFMA (default: the reference's arithmetic), 1: bf16x3 split-precision MFMA, 2: plain bf16 (E2ETTS_PRECISION_*)
+  int voc_precision = 0;  // 0: fp32 MFMA (default: the reference's arithmetic), 1: bf16x3 split-precision MFMA, 2: plain bf16, 3 / 4: bf16 / fp16
+                          // activations (E2ETTS_PRECISION_*)
   // streaming vocoder (e2etts_vocoder_stream_*): trailing mel frames kept as context / not yet emitted
   DevBuf st_carry, st_win;
   int st_B = 0, st_carry_n = 0, st_halo = 0;
@@ -397,6 +403,10 @@ void free_frags(e2etts_engine* e) {
   e->bimg_act.clear();
   for (auto& kv : e->r16_of) (void)hipFree(kv.second);
   e->r16_of.clear();
+  for (auto& kv : e->himg_of) (void)hipFree(kv.second.first);
+  e->himg_of.clear();
+  for (auto& kv : e->r16h_of) (void)hipFree(kv.second);
+  e->r16h_of.clear();
   for (float* f : e->rb_frag_base)
     if (f) (void)hipFree(f);
   e->rb_frag_base.clear();
@@ -450,13 +460,38 @@ int make_bimg(e2etts_engine* e, const float* wx3, uint64_t cout, uint64_t kw, ui
   return E2ETTS_OK;
 }
 
+// fp32 -> the nearest IEEE binary16 value (ties to even), as fp32: overflow (>= 65520) to infinity, subnormals (multiples of 2^-24) kept
+static float round_to_f16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint32_t sign = u & 0x80000000u;
+  uint32_t a = u & 0x7fffffffu;
+  if (a >= 0x7f800000u) return f;   // infinity, NaN
+  if (a < 0x38800000u) {            // below 2^-14: the quantum is 2^-24, which is fp32's in [0.5, 1)
+    float af;
+    memcpy(&af, &a, 4);
+    volatile float t = af + 0.5f;
+    af = t - 0.5f;
+    memcpy(&a, &af, 4);
+  } else {
+    a = (a + 0xfffu + ((a >> 13) & 1u)) & ~0x1fffu;
+    if (a >= 0x47800000u) a = 0x7f800000u;
+  }
+  a |= sign;
+  memcpy(&f, &a, 4);
+  return f;
+}
+
 // precision "bf16_act": a copy of n fp32 values rounded to bf16 (nearest-even), kept as fp32, made once at load
-int make_r16(e2etts_engine* e, const float* src, size_t n) {
-  if (!src || e->r16_of.count(src)) return E2ETTS_OK;
+// (fp16 = true: rounded to fp16 into r16h_of, for precision "fp16_act", made at the first selection of that mode)
+int make_r16(e2etts_engine* e, const float* src, size_t n, bool fp16 = false) {
+  auto& dst = fp16 ? e->r16h_of : e->r16_of;
+  if (!src || dst.count(src)) return E2ETTS_OK;
   std::vector<float> h(n);
   HIPCHK(e, hipMemcpyAsync(h.data(), src, n * 4, hipMemcpyDefault, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   for (float& f : h) {
+    if (fp16) { f = round_to_f16(f); continue; }
     uint32_t u;
     memcpy(&u, &f, 4);
     if ((u & 0x7f800000u) != 0x7f800000u) u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
@@ -466,9 +501,23 @@ int make_r16(e2etts_engine* e, const float* src, size_t n) {
   HIPCHK(e, hipMalloc(&d, n * 4));
   e->dev_bytes += n * 4;
   e->frag_bytes += n * 4;
-  e->r16_of[src] = d;
+  dst[src] = d;
   HIPCHK(e, hipMemcpyAsync(d, h.data(), n * 4, hipMemcpyDefault, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
+  return E2ETTS_OK;
+}
+
+// precision "fp16_act": a vocoder convolution's fp32 weights [cout][kw][cin] as the fp16 image in conv_bf16.hip's order
+int make_himg(e2etts_engine* e, const float* w, uint64_t cout, uint64_t kw, uint64_t cin, int tap_split = 0) {
+  if (!w || (cout % 32) || e->himg_of.count(w)) return E2ETTS_OK;
+  if (tap_split > 0 && (kw != 3 || (tap_split % 32))) tap_split = 0;
+  void* img = nullptr;
+  const size_t bytes = bf16_image_bytes((int)cout, (int)kw, (int)cin, tap_split);
+  HIPCHK(e, hipMalloc(&img, bytes));
+  e->dev_bytes += bytes;
+  e->frag_bytes += bytes;
+  e->himg_of[w] = {img, tap_split};
+  KCHK(e, launch_f16_image(w, img, (int)cout, (int)kw, (int)cin, tap_split, e->stream));
   return E2ETTS_OK;
 }
 
@@ -699,6 +748,37 @@ int bind_conv(e2etts_engine* e, const std::string& name, uint64_t cout, uint64_t
   return E2ETTS_OK;
 }
 
+// Precision "fp16_act": the fp16 image of every vocoder convolution and the fp16-rounded biases / conv_post weights of the bound vocoder
+// (HiFi-GAN tail).  Called at the first selection of the mode, and by bind_vocoder when new weights arrive under it; what exists is kept.
+int make_fp16_act_params(e2etts_engine* e) {
+  const auto& c = e->cfg;
+  if (c.voc_istft_nfft) return E2ETTS_OK;
+  uint64_t ch = c.voc_init_ch;
+  RET(make_himg(e, e->voc_pre.w, ch, 7, c.n_mel));
+  RET(make_r16(e, e->voc_pre.b, ch, true));
+  for (int i = 0; i < c.voc_stages; ++i) {
+    const uint64_t cin = ch, cout = ch / 2, s = c.voc_up_rate[i];
+    RET(make_himg(e, e->voc_up[i].w, s * cout, 3, cin, (int)(s * cout / 2)));
+    RET(make_r16(e, e->voc_up[i].b, s * cout, true));
+    ch = cout;
+    for (int j = 0; j < c.voc_n_kernels; ++j) {
+      const int idx = i * c.voc_n_kernels + j;
+      const uint64_t k = c.voc_rb_kernel[j];
+      for (int m = 0; m < c.voc_n_dil; ++m) {
+        RET(make_himg(e, e->rb_c1[idx][m].w, ch, k, ch));
+        RET(make_r16(e, e->rb_c1[idx][m].b, ch, true));
+        if (c.voc_resblock == 2) continue;
+        RET(make_himg(e, e->rb_c2[idx][m].w, ch, k, ch));
+        RET(make_r16(e, e->rb_c2[idx][m].b, ch, true));
+      }
+    }
+  }
+  RET(make_r16(e, e->voc_post.w, 7 * ch, true));
+  RET(make_r16(e, e->voc_post.b, 1, true));
+  HIPCHK(e, hipStreamSynchronize(e->stream));   // the stream slots' passes run on streams of their own
+  return E2ETTS_OK;
+}
+
 int bind_vocoder(e2etts_engine* e) {
   const auto& c = e->cfg;
   const uint64_t C0 = c.voc_init_ch;
@@ -793,6 +873,7 @@ int bind_vocoder(e2etts_engine* e) {
     RET(make_r16(e, e->voc_post.w, 7 * ch));
     RET(make_r16(e, e->voc_post.b, 1));
   }
+  if (e->voc_precision == E2ETTS_PRECISION_FP16_ACT) RET(make_fp16_act_params(e));   // new weights under a mode selected earlier
   return E2ETTS_OK;
 }
 
@@ -1346,8 +1427,13 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
 // in the ResBlocks' epilogues (S = bf16(S + rb_j), then bf16(S / num_kernels)) or, at small windows, in the next upsampler's staging (see
 // small_window below) -- and conv_post_bf16.  Every level gives the same bits.  The
 // padded batch is computed in full (no ragged row limits).  Everything the call needs is checked before the first launch.
+// Precision "fp16_act" (E2ETTS_PRECISION_FP16_ACT, the module after .half()) is the same walk with element kind 2: fp16 tensors, the fp16
+// images and fp16-rounded parameters of make_fp16_act_params, the fp16 MFMA; profile classes *_fp16_act*.
 int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& WAV, DevBuf& PCM, bool own_out) {
   const auto& c = e->cfg;
+  const int kind = e->voc_precision == E2ETTS_PRECISION_FP16_ACT ? 2 : 1;
+  const char* tag = kind == 2 ? "fp16" : "bf16";
+  const char* conv_nm = kind == 2 ? "conv_fp16_act" : "conv_bf16_act";
   const int nk = c.voc_n_kernels, nd = c.voc_n_dil;
   long long len = T, ch = c.voc_init_ch, maxv = len * ch;
   for (int i = 0; i < c.voc_stages; ++i) {
@@ -1359,6 +1445,12 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
   if (len > 0x7fffffffLL / 2) return e->fail(E2ETTS_EINVAL, "utterance too long");
   // ---- parameters, and every launch's geometry, before anything is launched
   auto img = [&](const ConvW& w, int* split) -> const void* {
+    if (kind == 2) {
+      auto ih = e->himg_of.find(w.w);
+      if (ih == e->himg_of.end()) return nullptr;
+      if (split) *split = ih->second.second;
+      return ih->second.first;
+    }
     if (!w.wx3) return nullptr;
     auto it = e->bimg_of.find(w.wx3);
     if (it == e->bimg_of.end()) {
@@ -1369,8 +1461,9 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
     return it->second.first;
   };
   auto r16 = [&](const float* p) -> const float* {
-    auto it = e->r16_of.find(p);
-    return it == e->r16_of.end() ? nullptr : it->second;
+    const auto& tab = kind == 2 ? e->r16h_of : e->r16_of;
+    auto it = tab.find(p);
+    return it == tab.end() ? nullptr : it->second;
   };
   auto conv_q = [&](const ConvW& w, const void* in, int in_bf16, float in_slope, void* out, int Tn, int Cin, int Cout, int KW, int dil,
                     int pad, BConvParams& q) -> bool {
@@ -1378,7 +1471,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
     int split = 0;
     q.wimg = img(w, &split);
     q.in = in; q.in_bf16 = in_bf16; q.in_slope = in_slope; q.tap_split = split; q.KWe = split > 0 ? 2 : KW;
-    q.bias = r16(w.b); q.out_b = out; q.act16 = 1;
+    q.bias = r16(w.b); q.out_b = out; q.act16 = kind;
     q.B = B; q.T = Tn; q.Cin = Cin; q.Cout = Cout; q.KW = KW; q.dil = dil; q.pad = pad;
     return q.wimg && q.bias && conv_bf16_supported(q);
   };
@@ -1399,7 +1492,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
         }
     }
     if (!ok || !r16(e->voc_post.w) || !r16(e->voc_post.b) || ch > 128 || (ch % 4))
-      return e->fail(E2ETTS_EINVAL, "precision bf16_act: this vocoder (weights without bf16 images, or a geometry conv_bf16 does not serve at T = %d) has no bf16-activation route", T);
+      return e->fail(E2ETTS_EINVAL, "precision %s_act: this vocoder (weights without %s images, or a geometry conv_bf16 does not serve at T = %d) has no %s-activation route", tag, tag, T, tag);
   }
   const size_t vb = (size_t)B * maxv * 2;
   RET(ensure(e, e->v0, vb));
@@ -1426,7 +1519,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
   float pend_div = 1.0f;
   BConvParams q;
   conv_q(e->voc_pre, mel_btc, 0, 1.0f, S, T, c.n_mel, c.voc_init_ch, 7, 1, 3, q);   // bf16(conv_pre(bf16(mel)) + b)
-  RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)T * c.voc_init_ch * 7 * c.n_mel));
+  RET(run_conv(conv_nm, q, 2.0 * B * (double)T * c.voc_init_ch * 7 * c.n_mel));
   long long n = T;
   ch = c.voc_init_ch;
   for (int i = 0; i < c.voc_stages; ++i) {
@@ -1436,7 +1529,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
     for (int k = 0; k < 3; ++k) q.in_add[k] = pend_add[k];   // the previous stage's sum, formed while staging
     q.in_div = pend_div;
     pend_add[0] = pend_add[1] = pend_add[2] = nullptr; pend_div = 1.0f;
-    RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * s * co * 2 * ch));
+    RET(run_conv(conv_nm, q, 2.0 * B * (double)n * s * co * 2 * ch));
     n *= s;
     ch = co;
     bool stage_done = false;
@@ -1444,7 +1537,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
       const int idx = i * nk + j;
       r = RbParams();
       r.x = reinterpret_cast<const float*>(XU); r.out = reinterpret_cast<float*>(S); r.n_pairs = nd; r.B = B; r.T = (int)n; r.C = co;
-      r.KW = c.voc_rb_kernel[j]; r.x_bs = r.out_bs = n * co; r.slope = 0.1f; r.act16 = 1;
+      r.KW = c.voc_rb_kernel[j]; r.x_bs = r.out_bs = n * co; r.slope = 0.1f; r.act16 = kind;
       if (c.voc_resblock != 1 || nd > RB_MAX_PAIRS) return false;
       for (int m = 0; m < nd; ++m) {
         r.bimg[m][0] = img(e->rb_c1[idx][m], nullptr); r.bimg[m][1] = img(e->rb_c2[idx][m], nullptr);
@@ -1462,7 +1555,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
       }
       if (ok && rb_bf16_stage_supported(rq, nk)) {   // the whole stage and its sum in one launch
         char nm[48];
-        snprintf(nm, sizeof nm, "rb_bf16_act_stage_%d", co);
+        snprintf(nm, sizeof nm, "rb_%s_act_stage_%d", tag, co);
         ProfScope ps(e, nm, fl, 2.0 * 2.0 * B * (double)n * co);
         KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
         stage_done = true;
@@ -1479,7 +1572,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           by += rb_bf16_bytes(gq[t]) / 2;
         }
         char nm[48];
-        snprintf(nm, sizeof nm, "rb_bf16_act_group_%d", co);
+        snprintf(nm, sizeof nm, "rb_%s_act_group_%d", tag, co);
         ProfScope ps(e, nm, fl, by);
         KCHK(e, launch_rb_bf16_group(gq, nk, e->stream));
         for (int j = 1; j < nk; ++j) pend_add[j - 1] = reinterpret_cast<const float*>(Sj[j]);
@@ -1490,7 +1583,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           rq[j].accumulate = j > 0;
           if (j > 0 && j == nk - 1) rq[j].out_div = (float)nk;
           char nm[48];
-          snprintf(nm, sizeof nm, "rb_bf16_act_%d", co);
+          snprintf(nm, sizeof nm, "rb_%s_act_%d", tag, co);
           ProfScope ps(e, nm, rb_bf16_flops(rq[j]), rb_bf16_bytes(rq[j]) / 2);
           KCHK(e, launch_rb_bf16(rq[j], e->stream));
         }
@@ -1516,7 +1609,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
         pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
         pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
         pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = c.voc_rb_kernel[j]; pq.dil = c.voc_rb_dil[j][m]; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
-        pq.mode = 3;
+        pq.mode = kind == 2 ? 4 : 3;
       };
       for (int j = 0; j < nk && ok; ++j)   // every member of every launch servable: decided before anything is launched
         for (int m = 0; m < nd && ok; ++m) {
@@ -1531,7 +1624,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           fl += resblock_pair_flops(gq[t]); by += resblock_pair_bytes(gq[t]) / 2;
         }
         char nm[48];
-        snprintf(nm, sizeof nm, "pair_bf16_act_group_%d", co);
+        snprintf(nm, sizeof nm, "pair_%s_act_group_%d", tag, co);
         ProfScope ps(e, nm, fl, by);
         KCHK(e, launch_pair_bf16_group(gq, nk, e->stream));
         for (int t = 0; t < nk; ++t) curj[order[t]] = gq[t].out;
@@ -1554,7 +1647,7 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           void* out = last ? S : (cur == CUR ? T1 : CUR);
           conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, out, (int)n, co, co, k, d, (k * d - d) / 2, q);
           q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
-          RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+          RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
           cur = out;
           continue;
         }
@@ -1564,11 +1657,11 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
           pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
           pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = k; pq.dil = d; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
-          pq.mode = 3; pq.accumulate = acc; pq.out_div = div;
+          pq.mode = kind == 2 ? 4 : 3; pq.accumulate = acc; pq.out_div = div;
         }
         if (e->fuse_pairs >= 1 && pair_bf16_supported(pq)) {
           char nm[48];
-          snprintf(nm, sizeof nm, "pair_bf16_act_%d", co);
+          snprintf(nm, sizeof nm, "pair_%s_act_%d", tag, co);
           ProfScope ps(e, nm, resblock_pair_flops(pq), resblock_pair_bytes(pq) / 2);
           KCHK(e, launch_pair_bf16(pq, e->stream));
           cur = pq.out;
@@ -1580,17 +1673,17 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
         void* out = last ? S : (cur == XU ? (mid == T1 ? CUR : T1) : const_cast<void*>(cur));
         conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, mid, (int)n, co, co, k, d, (k * d - d) / 2, q);
         q.act_slope = 0.1f;
-        RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+        RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
         conv_q(e->rb_c2[idx][m], mid, 1, 1.0f, out, (int)n, co, co, k, 1, (k - 1) / 2, q);
         q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
-        RET(run_conv("conv_bf16_act", q, 2.0 * B * (double)n * co * k * co));
+        RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
         cur = out;
       }
     }
   }
   {
-    ProfScope ps(e, "conv_post_bf16", 2.0 * B * (double)n * 7 * ch, (double)B * n * (ch * 2.0 + 6.0));
-    KCHK(e, launch_conv_post_bf16(S, r16(e->voc_post.w), r16(e->voc_post.b), ptr<float>(WAV), ptr<int16_t>(PCM), B, n, (int)ch, 7, e->stream));
+    ProfScope ps(e, kind == 2 ? "conv_post_fp16_act" : "conv_post_bf16", 2.0 * B * (double)n * 7 * ch, (double)B * n * (ch * 2.0 + 6.0));
+    KCHK(e, launch_conv_post_bf16(S, r16(e->voc_post.w), r16(e->voc_post.b), ptr<float>(WAV), ptr<int16_t>(PCM), B, n, (int)ch, 7, e->stream, kind == 2));
   }
   if (!own_out) {
     e->voc_B = B; e->voc_T = T;
@@ -1609,7 +1702,7 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
   const auto& c = e->cfg;
   if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
   if (B <= 0 || T <= 0) return e->fail(E2ETTS_EINVAL, "B and T must be positive");
-  if (e->voc_precision == E2ETTS_PRECISION_BF16_ACT) return vocoder_act16(e, mel_btc, B, T, WAV, PCM, own_out);   // (ragged limits unused)
+  if (e->voc_precision == E2ETTS_PRECISION_BF16_ACT || e->voc_precision == E2ETTS_PRECISION_FP16_ACT) return vocoder_act16(e, mel_btc, B, T, WAV, PCM, own_out);   // (ragged limits unused)
   // largest activation of any stage, in floats per utterance
   long long len = T, ch = c.voc_init_ch;
   long long maxv = len * ch;
@@ -2749,13 +2842,15 @@ int e2etts_set_precision(e2etts_engine* e, int vocoder_precision, int decoder_pr
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   if (vocoder_precision != E2ETTS_PRECISION_FP32 && vocoder_precision != E2ETTS_PRECISION_BF16X3 &&
-      vocoder_precision != E2ETTS_PRECISION_BF16 && vocoder_precision != E2ETTS_PRECISION_BF16_ACT)
+      vocoder_precision != E2ETTS_PRECISION_BF16 && vocoder_precision != E2ETTS_PRECISION_BF16_ACT && vocoder_precision != E2ETTS_PRECISION_FP16_ACT)
     return e->fail(E2ETTS_EINVAL, "unknown vocoder precision %d", vocoder_precision);
   if (decoder_precision != E2ETTS_PRECISION_FP32 && decoder_precision != E2ETTS_PRECISION_BF16X3)
-    return e->fail(E2ETTS_EINVAL, "decoder precision must be fp32 or bf16x3 (got %d; bf16 and bf16_act are vocoder-only)", decoder_precision);
-  if (vocoder_precision == E2ETTS_PRECISION_BF16_ACT) {   // the geometries it serves, decided here rather than in the middle of a call
+    return e->fail(E2ETTS_EINVAL, "decoder precision must be fp32 or bf16x3 (got %d; bf16, bf16_act and fp16_act are vocoder-only)", decoder_precision);
+  if (vocoder_precision == E2ETTS_PRECISION_BF16_ACT || vocoder_precision == E2ETTS_PRECISION_FP16_ACT) {   // the geometries they serve, decided here rather than in the middle of a call
     const auto& c = e->cfg;
-    if (c.voc_istft_nfft) return e->fail(E2ETTS_EINVAL, "precision bf16_act serves the HiFi-GAN tail only, not the iSTFT tail");
+    const char* mode = vocoder_precision == E2ETTS_PRECISION_FP16_ACT ? "fp16_act" : "bf16_act";
+    const char* el = vocoder_precision == E2ETTS_PRECISION_FP16_ACT ? "fp16" : "bf16";
+    if (c.voc_istft_nfft) return e->fail(E2ETTS_EINVAL, "precision %s serves the HiFi-GAN tail only, not the iSTFT tail", mode);
     long long ch = c.voc_init_ch;
     bool ok = ch >= 32 && ch % 32 == 0 && c.n_mel >= 8 && c.n_mel % 8 == 0 && (c.voc_resblock == 1 || c.voc_resblock == 2);
     for (int i = 0; i < c.voc_stages && ok; ++i) {
@@ -2765,8 +2860,13 @@ int e2etts_set_precision(e2etts_engine* e, int vocoder_precision, int decoder_pr
     for (int j = 0; j < c.voc_n_kernels && ok; ++j)
       for (int m = 0; m < c.voc_n_dil && ok; ++m) ok = c.voc_rb_dil[j][m] * (c.voc_rb_kernel[j] - 1) <= 64;
     if (!ok || ch > 128)
-      return e->fail(E2ETTS_EINVAL, "precision bf16_act needs every vocoder width a multiple of 32 (>= 32; final <= 128) and ResBlock reaches <= 64 rows: "
-                                    "init width %d over %d stages has no bf16-I/O route", c.voc_init_ch, c.voc_stages);
+      return e->fail(E2ETTS_EINVAL, "precision %s needs every vocoder width a multiple of 32 (>= 32; final <= 128) and ResBlock reaches <= 64 rows: "
+                                    "init width %d over %d stages has no %s-I/O route", mode, c.voc_init_ch, c.voc_stages, el);
+    // the fp16 images and parameters, at the first selection (the previous mode stays selected if this fails)
+    if (vocoder_precision == E2ETTS_PRECISION_FP16_ACT && e->voc_loaded) {
+      HIPCHK(e, hipSetDevice(e->device));
+      RET(make_fp16_act_params(e));
+    }
   }
   e->voc_precision = vocoder_precision;
   e->dec_precision = decoder_precision;

@@ -172,7 +172,8 @@ struct PairParams {
   int accumulate = 0;            // out = out_old + result
   float out_div = 1.0f;          // then / out_div (needs accumulate)
   int mode = 1;                  // 0: exact fp32, 1: bf16x3 split precision, 2: plain bf16; 3: bf16 activations (precision "bf16_act", launch_pair_bf16
-                                 // only: x, out and the running sum are bf16 [B, T, C]; pair_bf16_kernel lists the rounding points)
+                                 // only: x, out and the running sum are bf16 [B, T, C]; pair_bf16_kernel lists the rounding points); 4: the same
+                                 // with fp16 elements and fp16 weight images (precision "fp16_act")
   double act_frac = 1.0;         // host-side bookkeeping only (see ConvParams::act_frac)
   const void* bimg1 = nullptr;   // mode 2, optional: conv1's and conv2's weights in conv_bf16.hip's order (launch_bf16_image): the pair then
   const void* bimg2 = nullptr;   // may run on launch_pair_bf16 (same bits as launch_resblock_pair in mode 2)
@@ -204,7 +205,8 @@ struct RbParams {
   float slope = 0.1f;
   int accumulate = 0;            // out = out_old + result
   float out_div = 1.0f;          // then / out_div (needs accumulate)
-  int act16 = 0;                 // precision "bf16_act": x and out (and the running sum) are bf16; see rb_bf16_kernel for the rounding points
+  int act16 = 0;                 // element kind, 1: precision "bf16_act": x and out (and the running sum) are bf16; see rb_bf16_kernel for the
+                                 // rounding points.  2: precision "fp16_act": the same with fp16 elements, images from launch_f16_image
 };
 bool rb_bf16_supported(const RbParams& p);
 const char* launch_rb_bf16_group(const RbParams* p, int n, hipStream_t s);   // members share B, T, C, n_pairs; KW / dilations / buffers per member
@@ -275,7 +277,8 @@ struct BConvParams {
   int rows_hint = 0;              // 0: tile shape by B x T; tuning aid otherwise (bench)
   int act16 = 0;                  // precision "bf16_act": `res` and the result (out_b, also the running sum of accumulate) are bf16; the
                                   // epilogue rounds after the bias, the activation, the residual, the sum and the division; a bf16 input is
-                                  // staged as bf16(max(x, x * in_slope)).  out must be null, outb_slope 1, in_add empty
+                                  // staged as bf16(max(x, x * in_slope)).  out must be null, outb_slope 1; in_add joins bf16 inputs only.
+                                  // 2 (precision "fp16_act"): the same with IEEE binary16 elements, the fp16 MFMA and wimg from launch_f16_image
 };
 bool conv_bf16_supported(const BConvParams& p);
 const char* launch_conv_bf16(const BConvParams& p, hipStream_t s);
@@ -291,6 +294,9 @@ const char* conv_bf16_class(const BConvParams& p);
 // tile contiguous).  tap_split != 0 (KW == 3): tap slot s of tile t is tap s + (32 t >= tap_split ? 1 : 0), KWe = 2.
 size_t bf16_image_bytes(int Cout, int KW, int Cin, int tap_split);
 const char* launch_bf16_image(const float* x3, void* img, int Cout, int KW, int Cin, int tap_split, hipStream_t s);
+// precision "fp16_act": the image in the same order and of the same size with fp16 elements, made from the fp32 weights w [Cout][KW][Cin]
+// (rounded once, to nearest-even)
+const char* launch_f16_image(const float* w, void* img, int Cout, int KW, int Cin, int tap_split, hipStream_t s);
 
 // split-precision weight image -> MFMA-fragment order (ConvParams::wfrag)
 const char* launch_x3_to_frag(const float* x3, float* frag, int Cout, int KW, int Cin, hipStream_t s);
@@ -346,7 +352,8 @@ const char* launch_conv_post(const float* x, const float* w, const float* bias, 
                              long long N, int C, int KW, hipStream_t s, const int32_t* act_rows = nullptr, const int32_t* act_rows_host = nullptr,
                              const float* const* x_add = nullptr, float x_div = 1.0f);
 // precision "bf16_act": x bf16 [B, N, C]; w16 / bias16 hold bf16-rounded values (fp32); every step rounded (small_kernels.hip)
+// fp16 = true (precision "fp16_act"): x fp16, w16 / bias16 hold fp16-rounded values, every step rounded to fp16
 const char* launch_conv_post_bf16(const void* x, const float* w16, const float* bias16, float* wav, int16_t* pcm, int B, long long N, int C, int KW,
-                                  hipStream_t s);
+                                  hipStream_t s, bool fp16 = false);
 
 }  // namespace e2etts

@@ -730,8 +730,14 @@ __global__ __launch_bounds__(TPB) void conv_post_kernel(const float* __restrict_
 
 // The same tail in precision "bf16_act" (include/e2etts.h): x bf16 [B, N, C]; x = bf16(lrelu_0.01(x)); y = bf16(conv + b) with the bf16-rounded
 // weights and bias the engine keeps (fp32 accumulation in conv_post_kernel's order); wav = bf16(tanh(y)); pcm from that rounded wav.
-__device__ __forceinline__ float cp_rnd(float x) { return (float)(__bf16)x; }
-template <int TPB>
+// FP16: the same with IEEE binary16 elements (precision "fp16_act"): a plain _Float16 cast rounds to nearest-even, overflows to infinity and
+// keeps subnormals.
+template <bool FP16>
+__device__ __forceinline__ float cp_rnd(float x) {
+  if constexpr (FP16) return (float)(_Float16)x;
+  else return (float)(__bf16)x;
+}
+template <int TPB, bool FP16 = false>
 __global__ __launch_bounds__(TPB) void conv_post_bf16_kernel(const __bf16* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ bias, float* __restrict__ wav,
                                                              int16_t* __restrict__ pcm, long long N, int C, int KW) {
@@ -751,11 +757,17 @@ __global__ __launch_bounds__(TPB) void conv_post_bf16_kernel(const __bf16* __res
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (t >= 0 && t < N) {
       const uint2 u = *reinterpret_cast<const uint2*>(xb + t * C + c);
-      v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
-      v.x = cp_rnd(v.x >= 0.f ? v.x : v.x * 0.01f);
-      v.y = cp_rnd(v.y >= 0.f ? v.y : v.y * 0.01f);
-      v.z = cp_rnd(v.z >= 0.f ? v.z : v.z * 0.01f);
-      v.w = cp_rnd(v.w >= 0.f ? v.w : v.w * 0.01f);
+      if constexpr (FP16) {
+        typedef _Float16 cp_f16x2 __attribute__((ext_vector_type(2)));
+        const cp_f16x2 a = __builtin_bit_cast(cp_f16x2, u.x), c2 = __builtin_bit_cast(cp_f16x2, u.y);
+        v = make_float4((float)a[0], (float)a[1], (float)c2[0], (float)c2[1]);
+      } else {
+        v = make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16), __uint_as_float(u.y & 0xffff0000u));
+      }
+      v.x = cp_rnd<FP16>(v.x >= 0.f ? v.x : v.x * 0.01f);
+      v.y = cp_rnd<FP16>(v.y >= 0.f ? v.y : v.y * 0.01f);
+      v.z = cp_rnd<FP16>(v.z >= 0.f ? v.z : v.z * 0.01f);
+      v.w = cp_rnd<FP16>(v.w >= 0.f ? v.w : v.w * 0.01f);
     }
     *reinterpret_cast<float4*>(xs + r * ldx + c) = v;
   }
@@ -773,7 +785,7 @@ __global__ __launch_bounds__(TPB) void conv_post_bf16_kernel(const __bf16* __res
       acc += (a.x * ww.x + a.y * ww.y) + (a.z * ww.z + a.w * ww.w);
     }
   }
-  const float v = cp_rnd(tanhf(cp_rnd(acc + bias[0])));
+  const float v = cp_rnd<FP16>(tanhf(cp_rnd<FP16>(acc + bias[0])));
   if (wav) wav[(long long)b * N + t] = v;
   if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)__fmul_rn(v, 32768.0f);
 }
@@ -1035,15 +1047,19 @@ const char* launch_conv_post(const float* x, const float* w, const float* bias, 
 }
 
 const char* launch_conv_post_bf16(const void* x, const float* w16, const float* bias16, float* wav, int16_t* pcm, int B, long long N, int C, int KW,
-                                  hipStream_t s) {
+                                  hipStream_t s, bool fp16) {
   if (!x || !w16 || !bias16) return "conv_post_bf16: null pointer";
   if (C % 4 || C <= 0 || C > 128 || KW <= 0 || KW > 15 || !(KW & 1) || B <= 0 || N <= 0) return "conv_post_bf16: bad dims";
   if ((uintptr_t)x & 7) return "conv_post_bf16: x must be 8-byte aligned";
   constexpr int TPB = 256;
   const size_t lds = ((size_t)(TPB + KW - 1) * (C + 4) + (size_t)KW * C) * sizeof(float);
   if (lds > 64 * 1024) return "conv_post_bf16: LDS tile exceeds 64 KiB";
-  hipLaunchKernelGGL(conv_post_bf16_kernel<TPB>, dim3((unsigned)((N + TPB - 1) / TPB), B), dim3(TPB), lds, s, reinterpret_cast<const __bf16*>(x), w16,
-                     bias16, wav, pcm, N, C, KW);
+  if (fp16)
+    hipLaunchKernelGGL((conv_post_bf16_kernel<TPB, true>), dim3((unsigned)((N + TPB - 1) / TPB), B), dim3(TPB), lds, s, reinterpret_cast<const __bf16*>(x), w16,
+                       bias16, wav, pcm, N, C, KW);
+  else
+    hipLaunchKernelGGL(conv_post_bf16_kernel<TPB>, dim3((unsigned)((N + TPB - 1) / TPB), B), dim3(TPB), lds, s, reinterpret_cast<const __bf16*>(x), w16,
+                       bias16, wav, pcm, N, C, KW);
   return CHECK_LAUNCH("conv_post_bf16");
 }
 

@@ -192,14 +192,22 @@ class HifiGan(_EngineBacked):
         module rounds; include/e2etts.h).  ``forward`` then takes a bf16 or fp32 mel and returns a bf16 tensor.  Returns self."""
         if self._engine is not None:
             self._engine.set_precision("bf16_act")   # ValueError for a geometry it does not serve; the engine keeps its mode
-        self._bf16 = True
+        self._bf16, self._fp16 = True, False
+        return self
+
+    def half(self):
+        """The reference module's ``.half()``: the engine's vocoder precision "fp16_act" (every activation fp16, rounded where that module
+        rounds; include/e2etts.h).  ``forward`` then takes an fp16 or fp32 mel and returns a ``torch.float16`` tensor.  Returns self."""
+        if self._engine is not None:
+            self._engine.set_precision("fp16_act")   # ValueError for a geometry it does not serve; the engine keeps its mode
+        self._bf16, self._fp16 = False, True
         return self
 
     def float(self):
         """Back to the reference's fp32 arithmetic (precision "fp32").  Returns self."""
         if self._engine is not None:
             self._engine.set_precision("fp32")
-        self._bf16 = False
+        self._bf16 = self._fp16 = False
         return self
 
     def _ensure_engine(self) -> Engine:
@@ -207,15 +215,17 @@ class HifiGan(_EngineBacked):
         eng = super()._ensure_engine()
         if fresh and getattr(self, "_bf16", False):
             eng.set_precision("bf16_act")
+        if fresh and getattr(self, "_fp16", False):
+            eng.set_precision("fp16_act")
         return eng
 
     def forward(self, x):
         """x [B, 80, T] (torch tensor, any device, or numpy) -> wav [B, 1, T * hop] on the GPU (V/generator.py:37-53); after ``bfloat16()``
-        the wav is a bf16 tensor (the engine's wav values are bf16 values: the cast is exact)."""
+        the wav is a bf16 tensor, after ``half()`` an fp16 one (the engine's wav values are bf16 / fp16 values: the cast is exact)."""
         torch = _torch()
         eng = self._ensure_engine()
         dev = torch.device("cuda", self._device)
-        x = torch.as_tensor(x).to(torch.float32).contiguous()   # a bf16 mel widens exactly
+        x = torch.as_tensor(x).to(torch.float32).contiguous()   # a bf16 or fp16 mel widens exactly
         if x.dim() != 3 or x.shape[1] != self._dims_cache.n_mel:
             raise ValueError(f"expected mel of shape [B, {self._dims_cache.n_mel}, T], got {tuple(x.shape)}")
         B, _, T = x.shape
@@ -223,6 +233,8 @@ class HifiGan(_EngineBacked):
         eng.vocoder(x, B, T, channels_first=True, out_wav=wav)
         if getattr(self, "_bf16", False):
             wav = wav.to(torch.bfloat16)
+        if getattr(self, "_fp16", False):
+            wav = wav.to(torch.float16)
         return wav.unsqueeze(1)
 
     __call__ = forward
@@ -248,6 +260,9 @@ class iSTFT(HifiGan):
 
     def bfloat16(self):
         raise NotImplementedError("bf16 activations (precision 'bf16_act') serve the HiFi-GAN tail only, not the iSTFT tail")
+
+    def half(self):
+        raise NotImplementedError("fp16 activations (precision 'fp16_act') serve the HiFi-GAN tail only, not the iSTFT tail")
 
     def _run(self, x):
         torch = _torch()

@@ -28,6 +28,8 @@
  *      E2ETTS_PRECISION_BF16      fp32 activations, residuals and stage sums (a bf16 copy of a conv's input where two launches hand one
  *                                 over), bf16 weight images;
  *      E2ETTS_PRECISION_BF16_ACT  bf16 activations, residuals and stage sums (2 bytes per element), bf16 weight images, bf16-rounded biases;
+ *      E2ETTS_PRECISION_FP16_ACT  fp16 (IEEE binary16) activations, residuals and stage sums (2 bytes per element), fp16 weight images,
+ *                                 fp16-rounded biases (both built when the mode is first selected);
  *    the acoustic model's activations are fp32 in every mode.  Weights come packed by e2e_tts_amd/packer.py (weight-norm and BatchNorm
  *    folded, conv weights tap-major).
  */
@@ -285,6 +287,31 @@ E2ETTS_API int e2etts_tempo(e2etts_engine* engine, const int16_t* pcm_in, size_t
  * E2ETTS_EINVAL up front for the iSTFT tail, narrower widths, and this value as the decoder precision.  Ragged batches: the vocoder
  * computes the padded rows (valid samples are the same with ragged on or off).  All fusion levels give the same bits. */
 #define E2ETTS_PRECISION_BF16_ACT 3
+/* E2ETTS_PRECISION_FP16_ACT (vocoder only): the arithmetic of the reference's HifiGan cast with .half() and fed an fp16 mel.  It is the
+ * table above with "bf16" read as IEEE binary16 (fp16): every tensor the vocoder keeps in HBM is fp16 [B, N, C]; each convolution multiplies
+ * fp16 operands on the fp16 MFMA (v_mfma_f32_32x32x16_f16: the bf16 instruction's shape and rate), accumulates in fp32, adds the bias in
+ * fp32 and rounds once; each elementwise step is computed in fp32 on fp16 values and rounded once:
+ *   input            mel staged as fp16(mel)
+ *   conv_pre         x = fp16(acc + b)
+ *   per upsampler    x = fp16(lrelu_0.1(x)); x = fp16(acc + b)
+ *   ResBlock1 pair   xt = fp16(lrelu(x)); xt = fp16(c1 + b1); xt = fp16(lrelu(xt)); xt = fp16(c2 + b2); x = fp16(xt + x)
+ *   ResBlock2 step   xt = fp16(lrelu(x)); xt = fp16(c + b); x = fp16(xt + x)
+ *   stage sum        xs = rb_0; xs = fp16(xs + rb_j) in j order; x = fp16(xs / num_kernels)
+ *   tail             x = fp16(lrelu_0.01(x)); y = fp16(conv_post + b); wav = fp16(tanh(y))
+ *   PCM              trunc(wav * 32768) of the rounded wav
+ * (the double rounding fp16(lrelu(fp16(c1 + b1))) is kept).  Conversions: round to nearest-even; overflow goes to infinity, as torch's
+ * cast does; subnormal results are kept (the fp16 denormal mode is "preserve"); a plain _Float16 cast (v_cvt_pk_f16_f32), never a
+ * round-toward-zero pack.  Subnormal MFMA operands are read as they are, not as zero (measured on the MI355X with
+ * tools/mfma_f16_subnormal.hip: 2^-20 x 2^10 gives 2^-10 from either operand, sixteen products 2^-24 x 2^12 sum to 2^-8), as torch's CPU kernels do.
+ * Weights: fp16 of the fp32 weight-norm fold, rounded ONCE from the fp32 weights of the blob (not from the bf16 hi + lo images); biases
+ * and conv_post's weights rounded to fp16 once.  These images and copies are built when the mode is first selected: an engine that never
+ * selects it owns no more HBM than before.  Difference from the reference's module: it evaluates the weight norm in fp16 from fp16
+ * weight_g / weight_v (several roundings); the engine rounds the fp32 fold once.  Accumulation order differs from torch's CPU kernels, so
+ * single outputs may differ by one fp16 ulp, and such flips spread through later layers.  Against the fp32 result the waveform lies ~1e-4
+ * mean-L1 (bf16_act: 6e-4 .. 9e-4) at the same bytes and matrix rate.
+ * Served geometries, refusals (E2ETTS_EINVAL up front for the iSTFT tail, narrower widths, and this value as the decoder precision),
+ * ragged batches (padded rows computed), streaming and fusion levels: exactly as E2ETTS_PRECISION_BF16_ACT. */
+#define E2ETTS_PRECISION_FP16_ACT 4
 E2ETTS_API int e2etts_set_precision(e2etts_engine* engine, int vocoder_precision, int decoder_precision);
 
 /* Ragged batches (default on).  e2etts_synthesize hands back, per utterance, only mel_lens[b] * hop valid samples; with
@@ -295,7 +322,7 @@ E2ETTS_API int e2etts_set_precision(e2etts_engine* engine, int vocoder_precision
  * The frame level (decoder, postnet, vocoder) is skipped from the mel lengths the engine computes itself; the phoneme level (encoder,
  * predictors) additionally when `lens` is HOST memory (the launch grids are built from the lengths on the host; with `lens` in device
  * memory the phoneme level computes the padded batch -- same results).  Batches of up to 64 utterances launch grids without idle
- * workgroups; larger ones still skip the rows but keep the padded grid.  With vocoder precision E2ETTS_PRECISION_BF16_ACT the vocoder
+ * workgroups; larger ones still skip the rows but keep the padded grid.  With vocoder precision E2ETTS_PRECISION_BF16_ACT or _FP16_ACT the vocoder
  * computes the padded rows in either case (the decoder and postnet still skip them); valid samples are identical with ragged on or off. */
 E2ETTS_API int e2etts_set_ragged(e2etts_engine* engine, int enable);
 

@@ -3,7 +3,7 @@
 through the streaming vocoder in chunks.  Prints audio-seconds per wall-second for each arithmetic mode.  (Correctness of this
 path: tests/test_gpu_longform.py.)
 
-    python tools/longform_bench.py [chunk_frames] [modes, comma separated: bf16,bf16x3,fp32] [timed passes]
+    python tools/longform_bench.py [chunk_frames] [modes, comma separated, any of _lib.VOCODER_PRECISIONS: bf16,bf16x3,fp32,bf16_act,fp16_act] [timed passes]
 
 With E2ETTS_PROFILE_FINE=1 in the environment one more pass per mode runs under the engine's event profile and prints the per-layer table."""
 import os
