@@ -51,7 +51,8 @@ struct ConvParams {
   const float* res = nullptr;    // optional residual, same indexing as out
   float* out = nullptr;          // [B, T, Cout]
   const int32_t* lens = nullptr; // optional [B]: output rows t >= lens[b] are written as 0
-  const int32_t* act_rows = nullptr; // optional [B]: only output rows < act_rows[b] are computed at all (ragged batches)
+  const int32_t* act_rows = nullptr; // optional [B]: only output rows < act_rows[b] are needed (ragged batches): whole row TILES past them are
+                                     // skipped and keep their old contents; the rows of the last tile past act_rows[b] may still be written
   const int32_t* act_rows_host = nullptr;  // the same B values in HOST memory (launcher only): with them the grid holds no workgroup
                                      // without rows (RowMap above) and the tile shape is chosen on the tiles that really run
   int B = 0, T = 0, Cin = 0, Cout = 0, KW = 1, dil = 1, pad = 0;
@@ -94,7 +95,8 @@ const char* launch_conv_rows(const ConvParams& p, hipStream_t s);
 // qkv [B, N, 3H] (q | k | v, head h at columns h*dk .. (h+1)*dk of each third); keys >= lens[b] masked (-inf);
 // out [B, N, H]; query rows >= lens[b] are written as 0 (they are zeroed after the LayerNorm anyway).
 // lens_host: the same B lengths in host memory (optional): the grid then holds only the query blocks that exist (RowMap), and the output
-// rows of queries >= lens[b] beyond the last block keep their old contents instead of being zeroed.
+// rows of queries >= lens[b] beyond the last block keep their old contents instead of being zeroed (a block is 64, 128 or 256 queries,
+// by the kernel the launch picks).
 // ws (optional, attention_workspace_bytes(B, N, H, n_head) bytes, 16-byte aligned): lets small padded fp32 grids compute the key segments
 // of a query block in workgroups of their own and merge them in a second launch (same bits as the in-register merge).
 const char* launch_attention(const float* qkv, float* out, const int32_t* lens, int B, int N, int H, int n_head, int x3,
@@ -345,7 +347,8 @@ const char* launch_wsola(const int16_t* x, long long n_in, int16_t* out, long lo
 
 const char* launch_transpose_bct_btc(const float* in, float* out, int B, int C, int T, hipStream_t s);
 // wav = tanh(conv7(lrelu_0.01(x))) with Cout = 1; pcm = (int16)(int32)(wav * 32768)
-// act_rows / act_rows_host (optional, device / host copies of the same B values): only samples < act_rows[b] are written (ragged batches)
+// act_rows / act_rows_host (optional, device / host copies of the same B values): only samples < act_rows[b] are needed (ragged batches):
+// whole 256-sample blocks past them are skipped; the samples of the last block past act_rows[b] are still written
 // x_add (optional, up to 3 more tensors like x) / x_div: x = (((x + x_add[0]) + x_add[1]) + x_add[2]) / x_div, formed while staging (the
 // join of the last stage's parallel ResBlocks, see BConvParams::in_add)
 const char* launch_conv_post(const float* x, const float* w, const float* bias, float* wav, int16_t* pcm, int B,

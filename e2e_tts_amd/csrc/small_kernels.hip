@@ -1026,7 +1026,13 @@ const char* launch_conv_post(const float* x, const float* w, const float* bias, 
   if (C % 4 || C <= 0 || C > 128 || KW <= 0 || KW > 15 || !(KW & 1)) return "conv_post: bad dims";
   constexpr int TPB = 256;
   const size_t lds = ((size_t)(TPB + KW - 1) * (C + 4) + (size_t)KW * C) * sizeof(float);
-  if (lds > 64 * 1024) return "conv_post: LDS tile exceeds 64 KiB";
+  // the engine's tails (32 channels: 35 KB) fit the default limit; wider ones (128 channels, k = 7: 139 KB) opt in to the CU's 160 KiB once
+  if (lds > 160 * 1024) return "conv_post: LDS tile exceeds the CU's 160 KiB";
+  if (lds > 64 * 1024) {
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_post_kernel<TPB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (attr != hipSuccess) return "conv_post: cannot raise the dynamic LDS limit";
+  }
   dim3 grid((unsigned)((N + TPB - 1) / TPB), B);
   RowMap rm;
   if (act_rows && act_rows_host && B <= ROWMAP_MAX) {
