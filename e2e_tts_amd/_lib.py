@@ -109,6 +109,16 @@ def load_library() -> C.CDLL:
     lib.e2etts_vocoder_stream_fetch.argtypes = [P, P, P, SZ]
     lib.e2etts_tempo.restype = I
     lib.e2etts_tempo.argtypes = [P, P, SZ, C.c_double, I, P, SZ, C.POINTER(SZ)]
+    lib.e2etts_denoiser_load.restype = I
+    lib.e2etts_denoiser_load.argtypes = [P, P, P, P, I, I]
+    lib.e2etts_denoiser_set_bias.restype = I
+    lib.e2etts_denoiser_set_bias.argtypes = [P, P, I]
+    lib.e2etts_denoiser_calibrate.restype = I
+    lib.e2etts_denoiser_calibrate.argtypes = [P, P, I, P]
+    lib.e2etts_denoise.restype = I
+    lib.e2etts_denoise.argtypes = [P, P, P, I, C.c_int64, F, P, P]
+    lib.e2etts_set_denoise.restype = I
+    lib.e2etts_set_denoise.argtypes = [P, F]
     lib.e2etts_set_precision.restype = I
     lib.e2etts_set_precision.argtypes = [P, I, I]
     lib.e2etts_set_ragged.restype = I
@@ -143,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "e2etts_fetch_wav", "e2etts_vocoder_stream_begin", "e2etts_vocoder_stream_push", "e2etts_vocoder_stream_fetch",
     "e2etts_set_precision", "e2etts_set_ragged", "e2etts_set_fused_resblocks", "e2etts_profile_enable", "e2etts_profile_filter", "e2etts_profile_read", "e2etts_device_bytes", "e2etts_stream", "e2etts_sync",
     "e2etts_load_weights_bcast", "e2etts_order_after", "e2etts_tempo", "e2etts_acoustic_ctl", "e2etts_synthesize_ctl",
+    "e2etts_denoiser_load", "e2etts_denoiser_set_bias", "e2etts_denoiser_calibrate", "e2etts_denoise", "e2etts_set_denoise",
 ]
 
 
@@ -262,6 +273,9 @@ class Engine:
             self._h = C.c_void_p()
             raise (ValueError if rc == E_INVAL else RuntimeError)(f"e2etts_create: {msg}")
         self.device = device
+        # api.TTS's note of the geometry it calibrated the denoiser for; None after new weights or bases (the engine keeps a bias across
+        # e2etts_load_weights: whoever loads another vocoder calibrates again)
+        self.denoiser_calibrated = None
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -308,6 +322,7 @@ class Engine:
         _expect(blob, "blob", "uint8", n)
         self._order(blob)
         self._check(self.lib.e2etts_load_weights(self._h, _addr(blob), n), "e2etts_load_weights")
+        self.denoiser_calibrated = None   # a bias taken from other vocoder weights says nothing about these (see denoiser_calibrate)
 
     @_locked
     def load_weights_bcast(self, blob, nbytes: int, rccl_comm: int, root: int = 0) -> None:
@@ -318,6 +333,7 @@ class Engine:
             self._order(blob)
         self._check(self.lib.e2etts_load_weights_bcast(self._h, _addr(blob), int(nbytes), C.c_void_p(rccl_comm), int(root)),
                     "e2etts_load_weights_bcast")
+        self.denoiser_calibrated = None
 
     def _controls(self, d_control, p_control, e_control, B: int, L: int):
         """None when all three controls are numbers (the scalar entry points), else [(values or None, n)] for d, p, e as
@@ -472,6 +488,71 @@ class Engine:
         self._check(self.lib.e2etts_tempo(self._h, _addr(pcm), pcm.size, float(speed), int(sample_rate), _addr(out), out.size, C.byref(n_out)),
                     "e2etts_tempo")
         return out
+
+    # ---- vocoder-bias denoiser (include/e2etts.h: e2etts_denoiser_*, e2etts_denoise; reference V/denoiser.py)
+    @_locked
+    def denoiser_load(self, fwd_basis, inv_basis, filter_length: int, hop: int, win_sq=None) -> None:
+        """The STFT bases [filter_length + 2, filter_length] float32 (denoiser.stft_bases) and, optionally, the squared centre-padded
+        window [filter_length] float32 (None: periodic Hann).  ValueError for a geometry the engine does not serve."""
+        n = (int(filter_length) + 2) * int(filter_length)
+        _expect(fwd_basis, "fwd_basis", "float32", n)
+        _expect(inv_basis, "inv_basis", "float32", n)
+        _expect(win_sq, "win_sq", "float32", int(filter_length))
+        for x in (fwd_basis, inv_basis, win_sq):   # the engine reads these with blocking copies
+            if _is_cuda(x):
+                import torch
+                torch.cuda.current_stream(x.device).synchronize()
+        self._check(self.lib.e2etts_denoiser_load(self._h, _addr(fwd_basis), _addr(inv_basis), _addr(win_sq), int(filter_length), int(hop)),
+                    "e2etts_denoiser_load")
+        self.denoiser_geometry = (int(filter_length), int(hop))
+        self.denoiser_calibrated = None   # the engine drops the bias with the old bases
+
+    @_locked
+    def denoiser_set_bias(self, bias) -> None:
+        """An explicit bias spectrum [filter_length / 2 + 1] float32."""
+        n = bias.size if isinstance(bias, np.ndarray) else bias.numel()
+        _expect(bias, "bias", "float32", n)
+        self._order(bias)
+        self._check(self.lib.e2etts_denoiser_set_bias(self._h, _addr(bias), int(n)), "e2etts_denoiser_set_bias")
+
+    @_locked
+    def denoiser_calibrate(self, mel=None, T: int = 88) -> np.ndarray:
+        """The engine's own vocoder on one utterance of T frames (mel [T, n_mel] channels-last, None = zeros: the reference's
+        mode='zeros'); frame 0's magnitudes become the bias.  Returns them, [filter_length / 2 + 1]."""
+        if not hasattr(self, "denoiser_geometry"):
+            raise RuntimeError("e2etts_denoiser_calibrate: no denoiser bases loaded (denoiser_load)")
+        if mel is not None:
+            T = int(mel.shape[0])
+            _expect(mel, "mel", "float32", T * self.dims.n_mel)
+            self._order(mel)
+        out = np.empty((self.denoiser_geometry[0] // 2 + 1,), np.float32)
+        self._check(self.lib.e2etts_denoiser_calibrate(self._h, _addr(mel), int(T), _addr(out)), "e2etts_denoiser_calibrate")
+        return out
+
+    @_locked
+    def denoise(self, wav, n_valid=None, strength: float = 0.1, B: Optional[int] = None, n: Optional[int] = None, out_wav=None,
+                out_pcm=None, want_wav: bool = True, want_pcm: bool = False):
+        """wav [B, n] float32 (None: the resident wav of the last vocoder / synthesize call, with B and n given), n_valid [B] int64 or
+        None.  Returns (wav [B, n] float32 or None, pcm [B, n] int16 or None); rows are denoised alone over their valid samples."""
+        if wav is not None:
+            B, n = int(wav.shape[0]), int(wav.shape[1])
+            _expect(wav, "wav", "float32", B * n)
+        elif B is None or n is None:
+            raise ValueError("wav is None (the resident wav): B and n must be given")
+        B, n = int(B), int(n)
+        _expect(n_valid, "n_valid", "int64", B)
+        w = out_wav if out_wav is not None else (np.empty((B, n), np.float32) if want_wav else None)
+        p = out_pcm if out_pcm is not None else (np.empty((B, n), np.int16) if want_pcm else None)
+        _expect(w, "out_wav", "float32", B * n)
+        _expect(p, "out_pcm", "int16", B * n)
+        self._order(wav, n_valid, w, p)
+        self._check(self.lib.e2etts_denoise(self._h, _addr(wav), _addr(n_valid), B, n, float(strength), _addr(w), _addr(p)), "e2etts_denoise")
+        return w, p
+
+    @_locked
+    def set_denoise(self, strength: float = 0.0) -> None:
+        """strength > 0: synthesize() denoises each row's valid samples before the int16 conversion; 0 (default): off."""
+        self._check(self.lib.e2etts_set_denoise(self._h, float(strength)), "e2etts_set_denoise")
 
     @_locked
     def set_precision(self, vocoder: str = "fp32", decoder: Optional[str] = None):

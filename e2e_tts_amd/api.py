@@ -244,11 +244,31 @@ class TTS:
             plan.append(item)
         return plan, revert
 
+    # the denoiser behind ``denoise_strength``: the reference's defaults (V/denoiser.py:159-160: filter_length, n_overlap, win_length; Hann,
+    # mode='zeros' = 88 zero frames); a subclass or an instance may set another geometry before the first denoised call
+    denoiser_geometry = (1024, 4, 1024)
+
+    def _prepare_denoiser(self) -> None:
+        """Bases loaded and bias calibrated on the engine's own vocoder, at first use and again whenever the engine has been given other
+        weights or other bases since (Engine.denoiser_calibrated).  Called under the engine's lock."""
+        if getattr(self.engine, "denoiser_calibrated", None) == self.denoiser_geometry:
+            return
+        from .denoiser import engine_window, stft_bases
+        N, V, W = self.denoiser_geometry
+        fwd, inv, win_sq = stft_bases(N, N // V, W)
+        self.engine.denoiser_load(fwd, inv, N, N // V, engine_window(win_sq, N, W, "hann"))
+        self.engine.denoiser_calibrate(None, 88)
+        self.engine.denoiser_calibrated = self.denoiser_geometry
+
     def inference_ids(self, sequences: Sequence[Sequence[int]], speaker_id, pitch_control=1.0, energy_control=1.0,
-                      duration_control=1.0, silence_distance: float = 0.5) -> np.ndarray:
+                      duration_control=1.0, silence_distance: float = 0.5, denoise_strength: float = 0.0) -> np.ndarray:
         """TTS.inference from phoneme-id sequences (the part after text_to_sequence).  ``speaker_id`` and each control may be a list with
         one entry per sequence (a control entry may also be an array of per-phoneme values): requests with different settings share
-        batches (plan_requests)."""
+        batches (plan_requests).  ``denoise_strength > 0`` subtracts that much of the vocoder's bias spectrum from every utterance
+        (_prepare_denoiser: the reference's defaults, calibrated on the engine's own vocoder); 0, the default, is the path without a denoiser."""
+        denoise_strength = float(denoise_strength)
+        if denoise_strength < 0:
+            raise ValueError("denoise_strength must be >= 0")
         if isinstance(speaker_id, (list, tuple)):
             spk = [self.speakers[k] for k in speaker_id]   # KeyError for an unknown speaker, as the reference
         else:
@@ -256,19 +276,29 @@ class TTS:
         plan, revert = self.plan_requests(sequences, self.max_len, spk, duration_control, pitch_control, energy_control)
         uv = not self._dims.pitch_no_uv
         pcms, lengths = [], []
-        for b in plan:
-            p = b["pitch_control"]
-            if uv and isinstance(p, np.ndarray):
-                p = p[..., None]   # the reference's [B, 1, 1] / [B, L, 1]: one factor for the f0 and the uv column
-            pcm, mel_lens, T = self.engine.synthesize(b["ids"], b["lens"], b["speaker"], b["duration_control"], p, b["energy_control"])
-            pcms.extend(list(pcm))
-            lengths.extend(int(x) for x in mel_lens)
+        # the strength is engine-wide state: it is set, used and cleared under the engine's lock, so that another thread's call on this TTS
+        # (or on the engine itself) with another strength cannot fall between set_denoise and synthesize
+        with self.engine.lock:
+            if denoise_strength > 0:
+                self._prepare_denoiser()
+                self.engine.set_denoise(denoise_strength)
+            try:
+                for b in plan:
+                    p = b["pitch_control"]
+                    if uv and isinstance(p, np.ndarray):
+                        p = p[..., None]   # the reference's [B, 1, 1] / [B, L, 1]: one factor for the f0 and the uv column
+                    pcm, mel_lens, T = self.engine.synthesize(b["ids"], b["lens"], b["speaker"], b["duration_control"], p, b["energy_control"])
+                    pcms.extend(list(pcm))
+                    lengths.extend(int(x) for x in mel_lens)
+            finally:
+                if denoise_strength > 0:
+                    self.engine.set_denoise(0.0)
         pcms = [pcms[i] for i in revert.tolist()]
         lengths = [lengths[i] for i in revert.tolist()]
         return self._combine_pcm(pcms, lengths, int(silence_distance * self.sample_rate))
 
     def inference(self, texts: list, speaker_id, pitch_control=1.0, energy_control=1.0, duration_control=1.0,
-                  silence_distance: float = 0.5) -> np.ndarray:
+                  silence_distance: float = 0.5, denoise_strength: float = 0.0) -> np.ndarray:
         """reference API/utils.py:119-160 -> 1-D np.int16.  ``speaker_id`` and each control may also be a list with one entry (a name /
         a number) per text: every piece arrange_text cuts from a text inherits that text's entry."""
         if isinstance(texts, str):
@@ -286,7 +316,7 @@ class TTS:
         seqs = [list(self.text_to_sequence(t)) for t in pieces]
         generated_audio = self.inference_ids(seqs, follow(speaker_id, "speaker_id"), follow(pitch_control, "pitch_control"),
                                              follow(energy_control, "energy_control"), follow(duration_control, "duration_control"),
-                                             silence_distance)
+                                             silence_distance, denoise_strength)
         print(f"Audio Saved: {time.strftime('%H:%M:%S', time.gmtime(generated_audio.size / self.sample_rate))}")
         return generated_audio
 
@@ -378,8 +408,8 @@ class Synthesizer:
         return self.synthesis(text, file_path, speed)
 
     def synthesis(self, text: str, save_filepath: str = None, speed: float = 1, speaker_id: str = "hn_minhphuong", sr: int = 22050,
-                  speed_mode: str = "duration"):
-        """reference API/inference.py:24-50.  ``speed != 1``: the reference synthesises at normal tempo and then runs ffmpeg's
+                  speed_mode: str = "duration", denoise_strength: float = 0.0):
+        """reference API/inference.py:24-50.  ``denoise_strength``: see ``TTS.inference_ids`` (0 = off).  ``speed != 1``: the reference synthesises at normal tempo and then runs ffmpeg's
         ``atempo`` on the file (API/utils.py:163-172).  Here, by default (``speed_mode="duration"``), the tempo goes into the
         model instead -- ``duration_control = 1 / speed`` (U/layers.py:218-221), i.e. the phonemes are simply generated shorter
         or longer on the GPU path, with no vocoded-audio artefacts; ``speed_mode="wsola"`` post-processes the file like the
@@ -394,7 +424,9 @@ class Synthesizer:
             save_filepath = os.path.join(self.output_dir, datetime.now().strftime("%m_%d_%Y_%H_%M_%S") + ".wav")
         in_model = speed != 1 and speed_mode == "duration"
         audio = self.model.inference(texts=[text], speaker_id=speaker_id, pitch_control=1.0, energy_control=1.0,
-                                     duration_control=(1.0 / float(speed)) if in_model else 1.0, silence_distance=0.5)
+                                     duration_control=(1.0 / float(speed)) if in_model else 1.0, silence_distance=0.5,
+                                     # (handed on only when set: self.model may be any object with the reference's TTS.inference signature)
+                                     **({"denoise_strength": denoise_strength} if denoise_strength else {}))
         write_wav(save_filepath, audio, sr)
         if in_model:
             file_type = save_filepath.split(".")[-1]

@@ -193,6 +193,19 @@ struct e2etts_engine {
   double rag_frac_dec = 1.0, rag_frac_post = 1.0, rag_frac_voc = 1.0;  // fraction of the padded rows those limits leave (profile FLOP counts)
   int dec_precision = 0;  // same choice for decoder + mel_linear + postnet (encoder / variance adaptor: always fp32)
 
+  // vocoder-bias denoiser (e2etts_denoiser_*, e2etts_denoise; denoiser.hip).  The bases are not part of the weight blob: they and
+  // the bias stay across e2etts_load_weights (a caller that loads another vocoder calibrates again).
+  struct {
+    int nfft = 0, hop = 0, nov = 0, cpad = 0;  // filter_length, hop, n_overlap, filter_length + 2 padded to a multiple of 32
+    bool loaded = false, have_bias = false;
+    float strength = 0.f;                      // e2etts_set_denoise: > 0 denoises e2etts_synthesize[_ctl]'s rows
+  } dn;
+  DevBuf dn_wf, dn_wi, dn_wf_frag, dn_wi_frag;  // forward basis, tap-major [Cout][KW * Cin], the inverse basis as one [hop][cpad] matrix per tap, and their fragment-order copies
+  DevBuf dn_win, dn_bias;                       // squared window [filter_length] float64; bias spectrum [filter_length / 2 + 1]
+  DevBuf dn_in, dn_lens, dn_pad, dn_spec, dn_ola, dn_out, dn_pcm;
+  DevBuf dn_mel, dn_cwav, dn_cpcm, dn_iq, dn_iri, dn_isp;  // calibration: mel, the vocoder's outputs, stand-ins for the iSTFT tail's tap buffers
+  std::vector<int32_t> dn_h;                    // host copy of dn_lens: [2 + n_overlap][B] = valid samples, frames, rows of the overlap-add per inverse launch
+
   // profiling
   bool prof_on = false;
   std::string prof_filter;  // non-empty: only launches of this class are bracketed by events (e2etts_profile_filter)
@@ -2237,6 +2250,107 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
   return E2ETTS_OK;
 }
 
+// ---- vocoder-bias denoiser (reference V/denoiser.py; kernels and the convolution view: denoiser.hip)
+
+// The per-utterance table of one pass: nv[b] valid samples (checked by the caller: 0 <= nv[b] <= n, multiples of hop) -> e->dn_h / dn_lens
+// [2 + n_overlap][B] = samples, frames F_b = nv / hop + 1, then for s = 0 .. n_overlap - 1 the rows F_b + n_overlap - 1 - s of the overlap-add that
+// the inverse launch shifted by s rows computes; all 0 for a row too short to reflect.
+// *F_max: the largest frame count; *ragged: the counts differ.  Returns a status.
+int denoise_table(e2etts_engine* e, const long long* nv, int B, int* F_max, bool* ragged) {
+  const auto& d = e->dn;
+  const size_t nt = (size_t)(2 + d.nov) * B;
+  e->dn_h.assign(nt, 0);
+  int fmax = 0, fmin = 0x7fffffff;
+  for (int b = 0; b < B; ++b) {
+    const int F = nv[b] > d.nfft / 2 ? (int)(nv[b] / d.hop) + 1 : 0;
+    e->dn_h[b] = (int32_t)nv[b];
+    e->dn_h[(size_t)B + b] = F;
+    for (int s = 0; s < d.nov; ++s) e->dn_h[(size_t)(2 + s) * B + b] = F ? F + d.nov - 1 - s : 0;
+    fmax = std::max(fmax, F);
+    fmin = std::min(fmin, F);
+  }
+  RET(ensure(e, e->dn_lens, nt * 4));
+  HIPCHK(e, hipMemcpyAsync(e->dn_lens.p, e->dn_h.data(), nt * 4, hipMemcpyHostToDevice, e->stream));
+  *F_max = fmax;
+  *ragged = fmin != fmax;
+  return E2ETTS_OK;
+}
+
+// reflect-pad + forward transform of in [B] rows (stride in_bs) into e->dn_spec [B, R, cpad], R = F_max + n_overlap - 1; the table is in place
+int denoise_forward(e2etts_engine* e, const float* in, long long in_bs, int B, int F_max, bool ragged) {
+  const auto& d = e->dn;
+  const int R = F_max + d.nov - 1;
+  const int32_t* lens = ptr<int32_t>(e->dn_lens);
+  RET(ensure(e, e->dn_pad, (size_t)B * R * d.hop * 4));
+  RET(ensure(e, e->dn_spec, (size_t)B * R * d.cpad * 4));
+  {
+    ProfScope ps(e, "denoise_pad", 0, (double)B * R * d.hop * 8.0);
+    KCHK(e, launch_stft_pad(in, in_bs, lens, ptr<float>(e->dn_pad), B, R, d.nfft, d.hop, e->stream));
+  }
+  ConvParams p;
+  p.B = B; p.T = R; p.in = ptr<float>(e->dn_pad); p.w = ptr<float>(e->dn_wf); p.wfrag = ptr<float>(e->dn_wf_frag); p.out = ptr<float>(e->dn_spec);
+  p.Cin = d.hop; p.Cout = d.cpad; p.KW = d.nov; p.pad = 0; p.x3 = 0;
+  p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
+  double rows = 0;
+  for (int b = 0; b < B; ++b) rows += e->dn_h[(size_t)B + b];
+  p.act_frac = rows / ((double)B * R);   // (the rows F_max .. R - 1 of the longest utterances are computed and then zeroed)
+  if (ragged) { p.act_rows = lens + B; p.act_rows_host = e->dn_h.data() + B; }
+  char name[48];
+  snprintf(name, sizeof name, "dn_fwd %s", conv_gemm_class(p));
+  ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
+  KCHK(e, launch_conv_gemm(p, e->stream));
+  return E2ETTS_OK;
+}
+
+// in: device rows [B] of stride in_bs; wav / pcm: device [B, n] (either may be null).  Always the exact-fp32 convolution.
+int denoise_impl(e2etts_engine* e, const float* in, long long in_bs, const long long* nv, int B, long long n, float strength, float* wav, int16_t* pcm) {
+  const auto& d = e->dn;
+  int F_max = 0;
+  bool ragged = false;
+  RET(denoise_table(e, nv, B, &F_max, &ragged));
+  const int32_t* lens = ptr<int32_t>(e->dn_lens);
+  const int R = F_max + d.nov - 1;
+  RET(ensure(e, e->dn_ola, (size_t)B * R * d.hop * 4));
+  if (F_max > 0) {
+    RET(denoise_forward(e, in, in_bs, B, F_max, ragged));
+    {
+      ProfScope ps(e, "denoise_sub", 0, (double)B * R * d.cpad * 8.0);
+      KCHK(e, launch_spectral_subtract(ptr<float>(e->dn_spec), ptr<float>(e->dn_bias), lens + B, B, R, d.cpad, d.nfft, d.nov, strength, e->stream));
+    }
+    // The transposed convolution, ONE LAUNCH PER TAP: out[q] = sum_s spec[q - s] . W_s, s = 0 first, the others accumulated onto it through
+    // an output pointer moved down s rows (no row is read out of range).  As one KW = n_overlap convolution every output would be a single
+    // fp32 chain of n_overlap x 1 056 terms of the size of the spectrum's peaks that cancel to a sample: measured 3.6 x the reference's own
+    // fp32 error, and past the bar on audio with a constant offset.  Chains a quarter as long, summed in a fixed order, halve that; the price
+    // is the spectrum read once per tap instead of once.
+    const size_t wmat = (size_t)d.hop * d.cpad, wfrag = x3_frag_bytes(d.hop, 1, d.cpad) / 4;
+    for (int s = 0; s < d.nov; ++s) {
+      if (R - s <= 0) break;
+      ConvParams p;
+      p.B = B; p.T = R - s; p.in = ptr<float>(e->dn_spec); p.w = ptr<float>(e->dn_wi) + s * wmat; p.wfrag = ptr<float>(e->dn_wi_frag) + s * wfrag;
+      p.out = ptr<float>(e->dn_ola) + (size_t)s * d.hop;
+      p.Cin = d.cpad; p.Cout = d.hop; p.KW = 1; p.pad = 0; p.x3 = 0; p.accumulate = s > 0;
+      p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
+      double rows = 0;
+      for (int b = 0; b < B; ++b) rows += e->dn_h[(size_t)(2 + s) * B + b];
+      p.act_frac = rows / ((double)B * p.T);
+      if (ragged) { p.act_rows = lens + (size_t)(2 + s) * B; p.act_rows_host = e->dn_h.data() + (size_t)(2 + s) * B; }
+      char name[48];
+      snprintf(name, sizeof name, "dn_inv %s", conv_gemm_class(p));
+      ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
+      KCHK(e, launch_conv_gemm(p, e->stream));
+    }
+  }
+  ProfScope ps(e, "denoise_ola", 0, (double)B * n * (4.0 + (wav ? 4.0 : 0.0) + (pcm ? 2.0 : 0.0)));
+  KCHK(e, launch_ola_norm(ptr<float>(e->dn_ola), in, in_bs, lens, lens + B, ptr<double>(e->dn_win), wav, pcm, B, n, R, d.nfft, d.hop, e->stream));
+  return E2ETTS_OK;
+}
+
+int denoise_ready(e2etts_engine* e) {
+  if (!e->dn.loaded) return e->fail(E2ETTS_ESTATE, "no denoiser bases loaded (e2etts_denoiser_load)");
+  if (!e->dn.have_bias) return e->fail(E2ETTS_ESTATE, "no denoiser bias spectrum (e2etts_denoiser_set_bias / e2etts_denoiser_calibrate)");
+  return E2ETTS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2592,11 +2706,23 @@ static int synthesize_entry(e2etts_engine* e, const int64_t* ids, const int64_t*
   HIPCHK(e, hipSetDevice(e->device));
   if (B > 4096) return e->fail(E2ETTS_EINVAL, "B > 4096");
   if (ctl) RET(check_controls(e, *ctl, B, L));
+  const bool denoise = e->dn.strength > 0.f;   // e2etts_set_denoise
+  if (denoise) {
+    RET(denoise_ready(e));
+    if (e->cfg.hop_length % e->dn.hop)
+      return e->fail(E2ETTS_EINVAL, "denoiser hop %d does not divide the vocoder's hop_length %d", e->dn.hop, e->cfg.hop_length);
+  }
   bool ragged = e->ragged != 0;
   RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, ragged, ctl));
   ragged = ragged && e->rag_short;
   if (T_out) *T_out = e->last_T;
   RET(vocoder_impl(e, ptr<float>(e->melpost), B, e->last_T, false, true, ragged ? ptr<int32_t>(e->mel32) : nullptr, ragged ? e->h_mel : nullptr));
+  if (denoise) {  // each row's valid samples, before the int16 conversion: the resident PCM becomes the denoised one, the resident wav stays
+    const long long n = (long long)e->last_T * e->cfg.hop_length;
+    std::vector<long long> nv(B);
+    for (int b = 0; b < B; ++b) nv[b] = std::min<long long>(std::max<long long>(e->h_mel[b], 0), e->last_T) * e->cfg.hop_length;
+    RET(denoise_impl(e, ptr<float>(e->wav), n, nv.data(), B, n, e->dn.strength, nullptr, ptr<int16_t>(e->pcm)));
+  }
   if (mel_lens_out) RET(copy_out(e, mel_lens_out, e->mel64.p, (size_t)B * 8));
   const size_t ns = (size_t)B * e->last_T * e->cfg.hop_length;
   if (pcm_out) {
@@ -2835,6 +2961,164 @@ int e2etts_tempo(e2etts_engine* e, const int16_t* pcm_in, size_t n_in, double sp
     RET(copy_out(e, pcm_out, e->tempo_out.p, (size_t)nout * 2));
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
+  return E2ETTS_OK;
+}
+
+int e2etts_denoiser_load(e2etts_engine* e, const float* fwd_basis, const float* inv_basis, const float* win_sq_or_null, int filter_length, int hop) {
+  if (!e) return E2ETTS_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!fwd_basis || !inv_basis) return e->fail(E2ETTS_EINVAL, "fwd_basis / inv_basis must not be NULL");
+  int nov = 0;
+  if (const char* m = denoiser_geometry_check(filter_length, hop, &nov))
+    return e->fail(E2ETTS_EINVAL, "%s (filter_length %d, hop %d)", m, filter_length, hop);
+  const int N = filter_length, C2 = N + 2, cpad = (C2 + 31) / 32 * 32;
+  // the reference's buffers ([filter_length + 2, filter_length], STFT.forward_basis / inverse_basis squeezed) -> conv_gemm's tap-major
+  // [Cout][KW * Cin]: forward Cout = cpad (rows beyond filter_length + 2 zero), tap j = columns j * hop ..: the basis rows as they are;
+  // inverse: one [hop][cpad] matrix per tap s (a plain Linear each, see denoise_impl), the basis columns s * hop ..
+  std::vector<float> hb((size_t)C2 * N), wf((size_t)cpad * N, 0.f), wi((size_t)hop * nov * cpad, 0.f);
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  HIPCHK(e, hipMemcpy(hb.data(), fwd_basis, hb.size() * 4, hipMemcpyDefault));
+  std::copy(hb.begin(), hb.end(), wf.begin());
+  HIPCHK(e, hipMemcpy(hb.data(), inv_basis, hb.size() * 4, hipMemcpyDefault));
+  for (int r = 0; r < hop; ++r)
+    for (int j = 0; j < nov; ++j)
+      for (int c = 0; c < C2; ++c) wi[((size_t)j * hop + r) * cpad + c] = hb[(size_t)c * N + (size_t)j * hop + r];
+  std::vector<double> win(N);
+  if (win_sq_or_null) {
+    std::vector<float> w32(N);
+    HIPCHK(e, hipMemcpy(w32.data(), win_sq_or_null, (size_t)N * 4, hipMemcpyDefault));
+    for (int k = 0; k < N; ++k) win[k] = (double)w32[k];
+  } else {  // periodic Hann (scipy.signal.get_window('hann', N, fftbins=True)), squared, in float64
+    for (int k = 0; k < N; ++k) {
+      const double w = 0.5 - 0.5 * std::cos(2.0 * M_PI * (double)k / (double)N);
+      win[k] = w * w;
+    }
+  }
+  e->dn.loaded = false;
+  e->dn.have_bias = false;   // a bias belongs to the geometry it was taken with
+  RET(ensure(e, e->dn_wf, wf.size() * 4));
+  RET(ensure(e, e->dn_wi, wi.size() * 4));
+  RET(ensure(e, e->dn_wf_frag, x3_frag_bytes(cpad, nov, hop)));
+  RET(ensure(e, e->dn_wi_frag, (size_t)nov * x3_frag_bytes(hop, 1, cpad)));
+  RET(ensure(e, e->dn_win, (size_t)N * 8));
+  RET(ensure(e, e->dn_bias, (size_t)(N / 2 + 1) * 4));
+  HIPCHK(e, hipMemcpyAsync(e->dn_wf.p, wf.data(), wf.size() * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dn_wi.p, wi.data(), wi.size() * 4, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(e->dn_win.p, win.data(), (size_t)N * 8, hipMemcpyHostToDevice, e->stream));
+  KCHK(e, launch_f32_to_frag(ptr<float>(e->dn_wf), ptr<float>(e->dn_wf_frag), cpad, nov, hop, e->stream));
+  for (int j = 0; j < nov; ++j)
+    KCHK(e, launch_f32_to_frag(ptr<float>(e->dn_wi) + (size_t)j * hop * cpad, ptr<float>(e->dn_wi_frag) + (size_t)j * (x3_frag_bytes(hop, 1, cpad) / 4), hop, 1,
+                               cpad, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));   // the host images above are read until here
+  e->dn.nfft = N; e->dn.hop = hop; e->dn.nov = nov; e->dn.cpad = cpad;
+  e->dn.loaded = true;
+  return E2ETTS_OK;
+}
+
+int e2etts_denoiser_set_bias(e2etts_engine* e, const float* bias, int n_bins) {
+  if (!e) return E2ETTS_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->dn.loaded) return e->fail(E2ETTS_ESTATE, "no denoiser bases loaded (e2etts_denoiser_load)");
+  if (!bias || n_bins != e->dn.nfft / 2 + 1)
+    return e->fail(E2ETTS_EINVAL, "bias must hold filter_length / 2 + 1 = %d bins (caller said %d)", e->dn.nfft / 2 + 1, n_bins);
+  RET(copy_in(e, e->dn_bias.p, bias, (size_t)n_bins * 4));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->dn.have_bias = true;
+  return E2ETTS_OK;
+}
+
+int e2etts_denoiser_calibrate(e2etts_engine* e, const float* mel_btc_or_null, int T, float* bias_out_or_null) {
+  if (!e) return E2ETTS_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  if (!e->dn.loaded) return e->fail(E2ETTS_ESTATE, "no denoiser bases loaded (e2etts_denoiser_load)");
+  if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
+  if (T <= 0) return e->fail(E2ETTS_EINVAL, "T must be positive");
+  const long long ns = (long long)T * e->cfg.hop_length;
+  if (ns % e->dn.hop || ns <= e->dn.nfft / 2)
+    return e->fail(E2ETTS_EINVAL, "%d frames give %lld samples: need a multiple of the denoiser hop %d above filter_length / 2 = %d", T, ns, e->dn.hop,
+                   e->dn.nfft / 2);
+  const size_t nm = (size_t)T * e->cfg.n_mel * 4;
+  RET(ensure(e, e->dn_mel, nm));
+  if (mel_btc_or_null) RET(copy_in(e, e->dn_mel.p, mel_btc_or_null, nm));
+  else HIPCHK(e, hipMemsetAsync(e->dn_mel.p, 0, nm, e->stream));
+  {
+    // the vocoder writes into buffers of this call; the iSTFT tail's tap buffers are stood in for, so every resident result (the wav and
+    // PCM of the last call, the "istft_spec_phase" tap) is what it was
+    struct TapSwap {
+      e2etts_engine* e; int B; long long F;
+      void swap() { std::swap(e->istft_q, e->dn_iq); std::swap(e->istft_ri, e->dn_iri); std::swap(e->istft_sp, e->dn_isp); }
+      TapSwap(e2etts_engine* e_) : e(e_), B(e_->istft_B), F(e_->istft_F) { swap(); }
+      ~TapSwap() { swap(); e->istft_B = B; e->istft_F = F; }
+    } keep(e);
+    RET(vocoder_impl(e, ptr<float>(e->dn_mel), 1, T, true, false, nullptr, nullptr, &e->dn_cwav, &e->dn_cpcm));
+  }
+  const long long nv = ns;
+  int F_max = 0;
+  bool ragged = false;
+  RET(denoise_table(e, &nv, 1, &F_max, &ragged));
+  RET(denoise_forward(e, ptr<float>(e->dn_cwav), ns, 1, F_max, false));
+  KCHK(e, launch_bias_frame(ptr<float>(e->dn_spec), ptr<float>(e->dn_bias), e->dn.nfft, e->stream));   // magnitudes of frame 0 (V/denoiser.py:179)
+  if (bias_out_or_null) RET(copy_out(e, bias_out_or_null, e->dn_bias.p, (size_t)(e->dn.nfft / 2 + 1) * 4));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  e->dn.have_bias = true;
+  return E2ETTS_OK;
+}
+
+int e2etts_denoise(e2etts_engine* e, const float* wav_in_or_null, const int64_t* n_valid_or_null, int B, int64_t n, float strength, float* wav_out,
+                   int16_t* pcm_out) {
+  if (!e) return E2ETTS_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  HIPCHK(e, hipSetDevice(e->device));
+  RET(denoise_ready(e));
+  if (B <= 0 || B > 65535 || n <= 0) return e->fail(E2ETTS_EINVAL, "B must lie in [1, 65535] and n be positive (B %d, n %lld)", B, (long long)n);
+  {  // one utterance's spectrum, [n / hop + n_overlap rows][cpad] fp32, is addressed with 32-bit byte offsets by the convolutions
+    const long long rows = (long long)(n / e->dn.hop) + e->dn.nov, limit = ((1LL << 31) - 1) / ((long long)e->dn.cpad * 4);
+    if (rows > limit)
+      return e->fail(E2ETTS_EINVAL, "n = %lld samples per row is too long: its spectrum (%lld rows of %d floats) must stay below 2 GiB, i.e. n <= %lld",
+                     (long long)n, rows, e->dn.cpad, (limit - e->dn.nov) * e->dn.hop);
+  }
+  if (!wav_out && !pcm_out) return e->fail(E2ETTS_EINVAL, "wav_out and pcm_out are both NULL");
+  if (!(strength >= 0.f)) return e->fail(E2ETTS_EINVAL, "strength must be >= 0");
+  if (!wav_in_or_null) {
+    if (!e->have_wav) return e->fail(E2ETTS_ESTATE, "wav_in == NULL but no vocoder result is resident");
+    if (B != e->voc_B || n != (long long)e->voc_T * e->cfg.hop_length)
+      return e->fail(E2ETTS_EINVAL, "resident wav is [%d, %lld], caller said [%d, %lld]", e->voc_B, (long long)e->voc_T * e->cfg.hop_length, B, (long long)n);
+  }
+  std::vector<long long> nv((size_t)B, n);
+  if (n_valid_or_null) {
+    std::vector<int64_t> h(B);
+    HIPCHK(e, hipMemcpyAsync(h.data(), n_valid_or_null, (size_t)B * 8, hipMemcpyDefault, e->stream));
+    HIPCHK(e, hipStreamSynchronize(e->stream));
+    for (int b = 0; b < B; ++b) nv[b] = h[b];
+  }
+  for (int b = 0; b < B; ++b)
+    if (nv[b] < 0 || nv[b] > n || nv[b] % e->dn.hop)
+      return e->fail(E2ETTS_EINVAL, "row %d: %lld valid samples must lie in [0, %lld] and be a multiple of the denoiser hop %d", b, nv[b], (long long)n, e->dn.hop);
+  const size_t ns = (size_t)B * (size_t)n;
+  const float* in = ptr<float>(e->wav);
+  if (wav_in_or_null) {
+    RET(ensure(e, e->dn_in, ns * 4));
+    RET(copy_in(e, e->dn_in.p, wav_in_or_null, ns * 4));
+    in = ptr<float>(e->dn_in);
+  }
+  if (wav_out) RET(ensure(e, e->dn_out, ns * 4));
+  if (pcm_out) RET(ensure(e, e->dn_pcm, ns * 2));
+  RET(denoise_impl(e, in, n, nv.data(), B, n, strength, wav_out ? ptr<float>(e->dn_out) : nullptr, pcm_out ? ptr<int16_t>(e->dn_pcm) : nullptr));
+  if (wav_out) RET(copy_out(e, wav_out, e->dn_out.p, ns * 4));
+  if (pcm_out) RET(copy_out(e, pcm_out, e->dn_pcm.p, ns * 2));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  return E2ETTS_OK;
+}
+
+int e2etts_set_denoise(e2etts_engine* e, float strength) {
+  if (!e) return E2ETTS_EINVAL;
+  std::lock_guard<std::mutex> lk(e->mu);
+  if (!(strength >= 0.f)) return e->fail(E2ETTS_EINVAL, "strength must be >= 0");
+  if (strength > 0.f) RET(denoise_ready(e));
+  e->dn.strength = strength;
   return E2ETTS_OK;
 }
 

@@ -345,6 +345,29 @@ const char* launch_ff_scale(const float* q, int q_ld, const float* gk, const flo
 const char* launch_wsola(const int16_t* x, long long n_in, int16_t* out, long long n_out, double speed, int n, int delta, int n_frames,
                          hipStream_t s);
 
+// ---- denoiser.hip: the passes around the two exact-fp32 convolutions of the vocoder-bias denoiser (reference V/denoiser.py:55-186).
+// Geometry served: filter_length = hop * n_overlap, n_overlap in {2, 4, 8}, hop % 32 == 0, hop <= 1024; nullptr when it is.
+const char* denoiser_geometry_check(int filter_length, int hop, int* n_overlap_out);
+// out [B, R, hop]: per utterance filter_length / 2 reflected samples, its n_valid[b] samples, filter_length / 2 samples reflected at ITS OWN
+// end (F.pad(mode = 'reflect'): the edge sample is not repeated), then zeros.  wav [B] rows of stride wav_bs; needs
+// (n_valid[b] + filter_length) <= R * hop and n_valid[b] <= wav_bs.  Rows with n_valid[b] <= filter_length / 2 cannot be reflected: all zeros.
+const char* launch_stft_pad(const float* wav, long long wav_bs, const int32_t* n_valid, float* out, int B, int R, int filter_length, int hop,
+                            hipStream_t s);
+// In place on spec [B, R, Cpad] (re[0 .. bins) | im[0 .. bins) | padding, bins = filter_length / 2 + 1), rows f < frames[b]:
+// mag = sqrt(re^2 + im^2), md = max(mag - strength * bias[k], 0), (re, im) *= md / mag (0 where mag == 0); padding channels -> 0.
+// Rows frames[b] <= f < frames[b] + n_overlap - 1 -> 0 (what the inverse convolution reads past the last frame); later rows untouched.
+const char* launch_spectral_subtract(float* spec, const float* bias, const int32_t* frames, int B, int R, int Cpad, int filter_length, int n_overlap,
+                                     float strength, hipStream_t s);
+// bias[k] = sqrt(re^2 + im^2) of one spectrum row, k < filter_length / 2 + 1
+const char* launch_bias_frame(const float* spec_row, float* bias, int filter_length, hipStream_t s);
+// y [B, R, hop]: the inverse convolution's rows = the overlap-add.  Sample i < n_valid[b] of utterance b is y[b, i + filter_length / 2]
+// divided by the window sum-square envelope of frames[b] frames where that exceeds FLT_MIN (win_sq: the squared, centre-padded window
+// [filter_length] in float64, summed into a float32 accumulator frame by frame as librosa's window_sumsquare does), times filter_length / hop.
+// Rows with n_valid[b] <= filter_length / 2 copy in[b, i] (row stride in_bs).  Samples i >= n_valid[b] are 0.  wav [B, n] fp32 and / or
+// pcm [B, n] int16 = trunc(v * 32768) SATURATED to [-32768, 32767].
+const char* launch_ola_norm(const float* y, const float* in, long long in_bs, const int32_t* n_valid, const int32_t* frames, const double* win_sq,
+                            float* wav, int16_t* pcm, int B, long long n, int R, int filter_length, int hop, hipStream_t s);
+
 const char* launch_transpose_bct_btc(const float* in, float* out, int B, int C, int T, hipStream_t s);
 // wav = tanh(conv7(lrelu_0.01(x))) with Cout = 1; pcm = (int16)(int32)(wav * 32768)
 // act_rows / act_rows_host (optional, device / host copies of the same B values): only samples < act_rows[b] are needed (ragged batches):

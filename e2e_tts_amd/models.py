@@ -295,3 +295,46 @@ class iSTFT(HifiGan):
     def inference(self, x):
         """x [B, 80, T] -> wav [B, 1, T * hop] (= inverse_stft(*forward(x)))."""
         return self._run(x)[3].unsqueeze(1)
+
+
+class Denoiser:
+    """Mirror of reference ``models.vocoder.denoiser.Denoiser`` (V/denoiser.py:156-186): same constructor arguments, ``bias_spec``
+    [1, filter_length / 2 + 1, 1] and ``forward(audio [B, n], strength=0.1) -> [B, 1, n]``, torch tensors on the engine's GPU.
+
+    ``vocoder`` is a ``HifiGan`` / ``iSTFT`` mirror: the bias is taken from ITS engine's vocoder in its current precision
+    (e2etts_denoiser_calibrate) -- mode='zeros' on 88 zero frames, mode='normal' on a standard-normal mel, as the reference draws it.
+    Differences from the reference, which runs one padded batch: ``n`` must be a multiple of the hop (vocoder output is), and
+    ``forward(audio, strength, n_valid=[...])`` denoises every row alone over its own valid samples (include/e2etts.h: e2etts_denoise)."""
+
+    def __init__(self, vocoder, filter_length: int = 1024, n_overlap: int = 4, win_length: int = 1024, mode: str = "zeros"):
+        from . import denoiser as dn
+        torch = _torch()
+        if mode not in ("zeros", "normal"):
+            raise ValueError(f"mode must be 'zeros' or 'normal', got {mode!r}")
+        self.filter_length, self.hop_length, self.win_length = int(filter_length), int(filter_length) // int(n_overlap), int(win_length)
+        dn.check_geometry(self.filter_length, self.hop_length)
+        fwd, inv, win_sq = dn.stft_bases(self.filter_length, self.hop_length, self.win_length)
+        self._vocoder = vocoder
+        eng = vocoder.engine
+        n_mel = eng.dims.n_mel
+        mel = None if mode == "zeros" else np.ascontiguousarray(torch.randn((1, n_mel, 88)).numpy()[0].T)
+        with eng.lock:
+            eng.denoiser_load(fwd, inv, self.filter_length, self.hop_length, dn.engine_window(win_sq, self.filter_length, self.win_length, "hann"))
+            bias = eng.denoiser_calibrate(mel, 88)
+        self.bias_spec = torch.from_numpy(bias).to(torch.device("cuda", eng.device))[None, :, None]
+
+    def forward(self, audio, strength: float = 0.1, n_valid=None):
+        from . import denoiser as dn
+        torch = _torch()
+        eng = self._vocoder.engine
+        dev = torch.device("cuda", eng.device)
+        x = torch.as_tensor(audio).to(torch.float32).contiguous()
+        if x.dim() != 2:
+            raise ValueError(f"expected audio of shape [B, n], got {tuple(x.shape)}")
+        B, n = x.shape
+        nv = dn.check_lengths([n] * B if n_valid is None else n_valid, n, self.hop_length)
+        out = torch.empty((B, n), dtype=torch.float32, device=dev)
+        eng.denoise(x, nv, strength, out_wav=out)
+        return out.unsqueeze(1)
+
+    __call__ = forward
