@@ -103,6 +103,8 @@ def load_library() -> C.CDLL:
     lib.e2etts_fetch_wav.argtypes = [P, P, SZ]
     lib.e2etts_vocoder_stream_begin.restype = I
     lib.e2etts_vocoder_stream_begin.argtypes = [P, I]
+    lib.e2etts_vocoder_stream_begin_denoised.restype = I
+    lib.e2etts_vocoder_stream_begin_denoised.argtypes = [P, I, F, C.POINTER(I)]
     lib.e2etts_vocoder_stream_push.restype = I
     lib.e2etts_vocoder_stream_push.argtypes = [P, P, I, I, C.POINTER(I)]
     lib.e2etts_vocoder_stream_fetch.restype = I
@@ -154,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "e2etts_set_precision", "e2etts_set_ragged", "e2etts_set_fused_resblocks", "e2etts_profile_enable", "e2etts_profile_filter", "e2etts_profile_read", "e2etts_device_bytes", "e2etts_stream", "e2etts_sync",
     "e2etts_load_weights_bcast", "e2etts_order_after", "e2etts_tempo", "e2etts_acoustic_ctl", "e2etts_synthesize_ctl",
     "e2etts_denoiser_load", "e2etts_denoiser_set_bias", "e2etts_denoiser_calibrate", "e2etts_denoise", "e2etts_set_denoise",
+    "e2etts_vocoder_stream_begin_denoised",
 ]
 
 
@@ -587,13 +590,25 @@ class Engine:
         self._check(self.lib.e2etts_set_fused_resblocks(self._h, level), "e2etts_set_fused_resblocks")
 
     # ---- long-form / streaming vocoder
-    def vocoder_stream(self, chunks, B: int, want_pcm: bool = False):
+    def vocoder_stream(self, chunks, B: int, want_pcm: bool = False, denoise_strength: Optional[float] = None):
         """Generator: feed an iterable of mel chunks [B, n, n_mel] (numpy / torch, channels-last), yield the waveform (or
         int16 PCM) pieces [B, n_emit * hop] as they become final.  Concatenated along axis 1 they equal
-        ``vocoder(whole_mel)`` bit for bit, while HBM use stays bounded by the chunk size."""
+        ``vocoder(whole_mel)`` bit for bit, while HBM use stays bounded by the chunk size.
+
+        ``denoise_strength`` (a number >= 0; None: the plain stream) opens a denoised stream: the pieces then concatenate to
+        ``denoise(vocoder(whole_mel), None, denoise_strength)`` bit for bit, and emitted frames lag pushed ones by
+        ``stream_halo + stream_delay`` (denoiser.stream_delay_frames)."""
         with self.lock:
-            halo = self._check(self.lib.e2etts_vocoder_stream_begin(self._h, B), "e2etts_vocoder_stream_begin")
+            if denoise_strength is None:
+                halo = self._check(self.lib.e2etts_vocoder_stream_begin(self._h, B), "e2etts_vocoder_stream_begin")
+                delay = 0
+            else:
+                d = C.c_int(0)
+                halo = self._check(self.lib.e2etts_vocoder_stream_begin_denoised(self._h, B, float(denoise_strength), C.byref(d)),
+                                   "e2etts_vocoder_stream_begin_denoised")
+                delay = d.value
         self.stream_halo = halo
+        self.stream_delay = delay
         hop = self.dims.hop_length
 
         def fetch(n_emit):   # the OLDEST unfetched chunk (the engine keeps at most two in flight)

@@ -144,6 +144,95 @@ __global__ void __launch_bounds__(256) ola_norm_kernel(const float* __restrict__
   }
 }
 
+// ---- stream forms (e2etts_vocoder_stream_begin_denoised): one WINDOW of a longer signal, every row alike.  The window's L samples sit at
+// absolute position S0 of a signal whose ends may lie outside it: an edge that is a real end of the signal is reflected as above, an edge
+// that is context is copied plainly, and the frames stay on the signal's absolute hop grid (S0 and filter_length / 2 are multiples of hop).
+
+// out [B, Rq, hop], Rq * hop = L + half at each real edge.  seg: the window's samples, rows of stride seg_bs.
+__global__ void __launch_bounds__(256) stft_pad_stream_kernel(const float* __restrict__ seg, long long seg_bs, float* __restrict__ out, long long L,
+                                                              int Rq, int hop, int half, bool left_real, bool right_real, bool vec_in) {
+  const int b = blockIdx.y;
+  const long long total4 = (long long)Rq * hop / 4;
+  const long long i4 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i4 >= total4) return;
+  const long long p0 = i4 * 4, lead = left_real ? half : 0;
+  const long long padded = L + lead + (right_real ? half : 0);
+  const float* w = seg + (long long)b * seg_bs;
+  float4 v;
+  const long long s0 = p0 - lead;
+  if (vec_in && s0 >= 0 && s0 + 3 < L) {
+    v = *reinterpret_cast<const float4*>(w + s0);
+  } else {
+    float t[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long p = p0 + k;
+      long long s = p - lead;
+      if (s < 0) s = -s;                                  // the signal's start: reflected, edge sample not repeated
+      else if (s >= L) s = 2LL * (L - 1) - s;             // the signal's end (only a real right edge has positions past L)
+      s = s < 0 ? 0 : (s >= L ? L - 1 : s);               // (L > half wherever an edge is real: the launcher checks; never out of the window)
+      t[k] = p < padded ? w[s] : 0.f;
+    }
+    v = make_float4(t[0], t[1], t[2], t[3]);
+  }
+  *reinterpret_cast<float4*>(out + ((long long)b * Rq * hop + p0)) = v;
+}
+
+// frames[b] = v for every row: the table spectral_subtract_kernel reads, written on the stream that uses it
+__global__ void fill_i32_kernel(int32_t* __restrict__ p, int n, int32_t v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+// One thread per 4 consecutive EMITTED samples of row blockIdx.y: sample k is y[b, y_off + k], at absolute padded position p_abs0 + k of the
+// signal.  The envelope is ola_norm_kernel's, frame by frame in ascending order over the absolute frames covering the position: clamped at
+// frame 0 by the position itself, and at the last frame F_abs - 1 only where the signal's end is known (F_abs = LLONG_MAX otherwise: the
+// emitted samples of such a window lie more than a filter before anything not yet pushed).  pass: a signal too short to reflect, copied.
+__global__ void __launch_bounds__(256) ola_norm_stream_kernel(const float* __restrict__ y, long long y_bs, long long y_off, const float* __restrict__ in,
+                                                              long long in_bs, const double* __restrict__ win_sq, float* __restrict__ wav,
+                                                              int16_t* __restrict__ pcm, long long n, long long p_abs0, long long F_abs, int hop,
+                                                              int nfft, float scale, bool pass, bool vec_out) {
+  const int b = blockIdx.y;
+  const long long i0 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (i0 >= n) return;
+  float t[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const long long i = i0 + k;
+    float v = 0.f;
+    if (i < n) {
+      if (pass) {
+        v = in[(long long)b * in_bs + i];
+      } else {
+        const long long p = p_abs0 + i;
+        v = y[(long long)b * y_bs + y_off + i];
+        long long f_lo = p - nfft + 1 <= 0 ? 0 : (p - nfft + hop) / hop;
+        long long f_hi = p / hop;
+        if (f_hi > F_abs - 1) f_hi = F_abs - 1;
+        float env = 0.f;
+        for (long long f = f_lo; f <= f_hi; ++f) env = (float)((double)env + win_sq[p - f * hop]);
+        if (env > FLT_MIN) v = __fdiv_rn(v, env);
+        v = __fmul_rn(v, scale);
+      }
+    }
+    t[k] = v;
+  }
+  const long long o = (long long)b * n + i0;
+  if (vec_out && i0 + 3 < n) {
+    if (wav) *reinterpret_cast<float4*>(wav + o) = make_float4(t[0], t[1], t[2], t[3]);
+    if (pcm) {
+      short4 s;
+      s.x = pcm_sat(t[0]); s.y = pcm_sat(t[1]); s.z = pcm_sat(t[2]); s.w = pcm_sat(t[3]);
+      *reinterpret_cast<short4*>(pcm + o) = s;
+    }
+  } else {
+    for (int k = 0; k < 4 && i0 + k < n; ++k) {
+      if (wav) wav[o + k] = t[k];
+      if (pcm) pcm[o + k] = pcm_sat(t[k]);
+    }
+  }
+}
+
 }  // namespace
 
 const char* denoiser_geometry_check(int filter_length, int hop, int* n_overlap_out) {
@@ -202,6 +291,44 @@ const char* launch_ola_norm(const float* y, const float* in, long long in_bs, co
   hipLaunchKernelGGL(ola_norm_kernel, dim3((unsigned)((total4 + 255) / 256), B), dim3(256), 0, s, y, in, in_bs, n_valid, frames, win_sq, wav, pcm, n, R,
                      hop, filter_length, (float)filter_length / (float)hop, vec_out);
   return CHECK_LAUNCH("ola_norm");
+}
+
+const char* launch_stft_pad_stream(const float* seg, long long seg_bs, float* out, int B, long long L, int Rq, int filter_length, int hop, bool left_real,
+                                   bool right_real, hipStream_t s) {
+  if (!seg || !out) return "stft_pad_stream: null pointer";
+  if (const char* m = denoiser_geometry_check(filter_length, hop, nullptr)) return m;
+  const int half = filter_length / 2;
+  if (B <= 0 || B > 65535 || L <= 0 || Rq <= 0 || seg_bs < L) return "stft_pad_stream: bad dims";
+  if ((left_real || right_real) && L <= half) return "stft_pad_stream: a window with a real edge must be longer than filter_length / 2";
+  if ((long long)Rq * hop != L + (left_real ? half : 0) + (right_real ? half : 0)) return "stft_pad_stream: rows do not match the window";
+  if ((uintptr_t)out & 15) return "stft_pad_stream: out must be 16-byte aligned";
+  const bool vec_in = (seg_bs % 4 == 0) && (((uintptr_t)seg & 15) == 0);
+  const long long total4 = (long long)Rq * hop / 4;
+  if ((total4 + 255) / 256 >= (1LL << 31)) return "stft_pad_stream: grid too large";
+  hipLaunchKernelGGL(stft_pad_stream_kernel, dim3((unsigned)((total4 + 255) / 256), B), dim3(256), 0, s, seg, seg_bs, out, L, Rq, hop, half, left_real,
+                     right_real, vec_in);
+  return CHECK_LAUNCH("stft_pad_stream");
+}
+
+const char* launch_fill_i32(int32_t* p, int n, int32_t v, hipStream_t s) {
+  if (!p || n <= 0) return "fill_i32: bad arguments";
+  hipLaunchKernelGGL(fill_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, p, n, v);
+  return CHECK_LAUNCH("fill_i32");
+}
+
+const char* launch_ola_norm_stream(const float* y, long long y_bs, long long y_off, const float* in, long long in_bs, const double* win_sq, float* wav,
+                                   int16_t* pcm, int B, long long n, long long p_abs0, long long F_abs, int filter_length, int hop, bool pass,
+                                   hipStream_t s) {
+  if (!in || !win_sq || (!wav && !pcm) || (!pass && !y)) return "ola_norm_stream: null pointer";
+  if (const char* m = denoiser_geometry_check(filter_length, hop, nullptr)) return m;
+  if (B <= 0 || B > 65535 || n <= 0 || in_bs < n || p_abs0 < 0 || F_abs <= 0) return "ola_norm_stream: bad dims";
+  if (!pass && (y_off < 0 || y_off + n > y_bs)) return "ola_norm_stream: emitted range outside the overlap-add";
+  const bool vec_out = (n % 4 == 0) && (!wav || ((uintptr_t)wav & 15) == 0) && (!pcm || ((uintptr_t)pcm & 7) == 0);
+  const long long total4 = (n + 3) / 4;
+  if ((total4 + 255) / 256 >= (1LL << 31)) return "ola_norm_stream: grid too large";
+  hipLaunchKernelGGL(ola_norm_stream_kernel, dim3((unsigned)((total4 + 255) / 256), B), dim3(256), 0, s, y, y_bs, y_off, in, in_bs, win_sq, wav, pcm, n,
+                     p_abs0, F_abs, hop, filter_length, (float)filter_length / (float)hop, pass, vec_out);
+  return CHECK_LAUNCH("ola_norm_stream");
 }
 
 }  // namespace e2etts

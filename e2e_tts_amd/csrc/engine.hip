@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -161,6 +162,12 @@ struct e2etts_engine {
   int st_B = 0, st_carry_n = 0, st_halo = 0;
   long long st_emitted = 0;
   bool st_open = false, st_done = false;
+  // denoised stream (e2etts_vocoder_stream_begin_denoised): every window carries st_delay more frames of context per side than the halo and
+  // its waveform is denoised as a function of the window alone (denoise_stream_impl), so nothing of the denoiser is carried between chunks
+  bool st_dn = false;
+  float st_strength = 0.f;
+  int st_delay = 0;
+  long long st_abs0 = 0;   // absolute frame index of the carry's first frame
   // Two chunks may be in flight: _push enqueues and returns, _fetch takes the OLDEST unfetched chunk.  A chunk's pass depends on the mel
   // stream only (the carried context is mel frames), so the two passes are independent: each slot has a compute stream, a workspace and
   // output buffers of its own, and the kernels of chunk i + 1 fill the CUs that chunk i's launch tails and small launches leave idle.
@@ -178,6 +185,7 @@ struct e2etts_engine {
   struct StSlot {
     VocCtx ctx;
     DevBuf wav, pcm, win;
+    DevBuf dn_pad, dn_spec, dn_ola, dn_lens, dn_wav, dn_pcm;   // a denoised stream: the slot's own denoiser workspace and denoised outputs
     void* pin = nullptr;
     size_t pin_cap = 0;
     hipEvent_t done = nullptr, win_ready = nullptr;
@@ -2276,6 +2284,25 @@ int denoise_table(e2etts_engine* e, const long long* nv, int B, int* F_max, bool
   return E2ETTS_OK;
 }
 
+// The forward transform of the padded rows pad [B, R, hop] into spec [B, R, cpad].  h_tab: the table of denoise_table on the host; d_tab: the
+// same on the device when the rows differ in length, else null.
+int denoise_fwd_conv(e2etts_engine* e, const float* pad, float* spec, const int32_t* h_tab, const int32_t* d_tab, int B, int R) {
+  const auto& d = e->dn;
+  ConvParams p;
+  p.B = B; p.T = R; p.in = pad; p.w = ptr<float>(e->dn_wf); p.wfrag = ptr<float>(e->dn_wf_frag); p.out = spec;
+  p.Cin = d.hop; p.Cout = d.cpad; p.KW = d.nov; p.pad = 0; p.x3 = 0;
+  p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
+  double rows = 0;
+  for (int b = 0; b < B; ++b) rows += h_tab[(size_t)B + b];
+  p.act_frac = rows / ((double)B * R);   // (the rows F_max .. R - 1 of the longest utterances are computed and then zeroed)
+  if (d_tab) { p.act_rows = d_tab + B; p.act_rows_host = h_tab + B; }
+  char name[48];
+  snprintf(name, sizeof name, "dn_fwd %s", conv_gemm_class(p));
+  ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
+  KCHK(e, launch_conv_gemm(p, e->stream));
+  return E2ETTS_OK;
+}
+
 // reflect-pad + forward transform of in [B] rows (stride in_bs) into e->dn_spec [B, R, cpad], R = F_max + n_overlap - 1; the table is in place
 int denoise_forward(e2etts_engine* e, const float* in, long long in_bs, int B, int F_max, bool ragged) {
   const auto& d = e->dn;
@@ -2287,18 +2314,34 @@ int denoise_forward(e2etts_engine* e, const float* in, long long in_bs, int B, i
     ProfScope ps(e, "denoise_pad", 0, (double)B * R * d.hop * 8.0);
     KCHK(e, launch_stft_pad(in, in_bs, lens, ptr<float>(e->dn_pad), B, R, d.nfft, d.hop, e->stream));
   }
-  ConvParams p;
-  p.B = B; p.T = R; p.in = ptr<float>(e->dn_pad); p.w = ptr<float>(e->dn_wf); p.wfrag = ptr<float>(e->dn_wf_frag); p.out = ptr<float>(e->dn_spec);
-  p.Cin = d.hop; p.Cout = d.cpad; p.KW = d.nov; p.pad = 0; p.x3 = 0;
-  p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
-  double rows = 0;
-  for (int b = 0; b < B; ++b) rows += e->dn_h[(size_t)B + b];
-  p.act_frac = rows / ((double)B * R);   // (the rows F_max .. R - 1 of the longest utterances are computed and then zeroed)
-  if (ragged) { p.act_rows = lens + B; p.act_rows_host = e->dn_h.data() + B; }
-  char name[48];
-  snprintf(name, sizeof name, "dn_fwd %s", conv_gemm_class(p));
-  ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
-  KCHK(e, launch_conv_gemm(p, e->stream));
+  return denoise_fwd_conv(e, ptr<float>(e->dn_pad), ptr<float>(e->dn_spec), e->dn_h.data(), ragged ? lens : nullptr, B, R);
+}
+
+// The transposed convolution of spec [B, R, cpad] into the overlap-add ola [B, R, hop]; h_tab / d_tab as for denoise_fwd_conv.
+// ONE LAUNCH PER TAP: out[q] = sum_s spec[q - s] . W_s, s = 0 first, the others accumulated onto it through an output pointer moved down s
+// rows (no row is read out of range).  As one KW = n_overlap convolution every output would be a single fp32 chain of n_overlap x 1 056 terms
+// of the size of the spectrum's peaks that cancel to a sample: measured 3.6 x the reference's own fp32 error, and past the bar on audio with
+// a constant offset.  Chains a quarter as long, summed in a fixed order, halve that; the price is the spectrum read once per tap instead of
+// once.
+int denoise_inv_convs(e2etts_engine* e, const float* spec, float* ola, const int32_t* h_tab, const int32_t* d_tab, int B, int R) {
+  const auto& d = e->dn;
+  const size_t wmat = (size_t)d.hop * d.cpad, wfrag = x3_frag_bytes(d.hop, 1, d.cpad) / 4;
+  for (int s = 0; s < d.nov; ++s) {
+    if (R - s <= 0) break;
+    ConvParams p;
+    p.B = B; p.T = R - s; p.in = spec; p.w = ptr<float>(e->dn_wi) + s * wmat; p.wfrag = ptr<float>(e->dn_wi_frag) + s * wfrag;
+    p.out = ola + (size_t)s * d.hop;
+    p.Cin = d.cpad; p.Cout = d.hop; p.KW = 1; p.pad = 0; p.x3 = 0; p.accumulate = s > 0;
+    p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
+    double rows = 0;
+    for (int b = 0; b < B; ++b) rows += h_tab[(size_t)(2 + s) * B + b];
+    p.act_frac = rows / ((double)B * p.T);
+    if (d_tab) { p.act_rows = d_tab + (size_t)(2 + s) * B; p.act_rows_host = h_tab + (size_t)(2 + s) * B; }
+    char name[48];
+    snprintf(name, sizeof name, "dn_inv %s", conv_gemm_class(p));
+    ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
+    KCHK(e, launch_conv_gemm(p, e->stream));
+  }
   return E2ETTS_OK;
 }
 
@@ -2317,28 +2360,7 @@ int denoise_impl(e2etts_engine* e, const float* in, long long in_bs, const long 
       ProfScope ps(e, "denoise_sub", 0, (double)B * R * d.cpad * 8.0);
       KCHK(e, launch_spectral_subtract(ptr<float>(e->dn_spec), ptr<float>(e->dn_bias), lens + B, B, R, d.cpad, d.nfft, d.nov, strength, e->stream));
     }
-    // The transposed convolution, ONE LAUNCH PER TAP: out[q] = sum_s spec[q - s] . W_s, s = 0 first, the others accumulated onto it through
-    // an output pointer moved down s rows (no row is read out of range).  As one KW = n_overlap convolution every output would be a single
-    // fp32 chain of n_overlap x 1 056 terms of the size of the spectrum's peaks that cancel to a sample: measured 3.6 x the reference's own
-    // fp32 error, and past the bar on audio with a constant offset.  Chains a quarter as long, summed in a fixed order, halve that; the price
-    // is the spectrum read once per tap instead of once.
-    const size_t wmat = (size_t)d.hop * d.cpad, wfrag = x3_frag_bytes(d.hop, 1, d.cpad) / 4;
-    for (int s = 0; s < d.nov; ++s) {
-      if (R - s <= 0) break;
-      ConvParams p;
-      p.B = B; p.T = R - s; p.in = ptr<float>(e->dn_spec); p.w = ptr<float>(e->dn_wi) + s * wmat; p.wfrag = ptr<float>(e->dn_wi_frag) + s * wfrag;
-      p.out = ptr<float>(e->dn_ola) + (size_t)s * d.hop;
-      p.Cin = d.cpad; p.Cout = d.hop; p.KW = 1; p.pad = 0; p.x3 = 0; p.accumulate = s > 0;
-      p.in_ld = p.Cin; p.out_ld = p.Cout; p.in_bs = (long long)R * p.in_ld; p.out_bs = (long long)R * p.out_ld;
-      double rows = 0;
-      for (int b = 0; b < B; ++b) rows += e->dn_h[(size_t)(2 + s) * B + b];
-      p.act_frac = rows / ((double)B * p.T);
-      if (ragged) { p.act_rows = lens + (size_t)(2 + s) * B; p.act_rows_host = e->dn_h.data() + (size_t)(2 + s) * B; }
-      char name[48];
-      snprintf(name, sizeof name, "dn_inv %s", conv_gemm_class(p));
-      ProfScope ps(e, name, conv_gemm_flops(p), conv_gemm_bytes(p));
-      KCHK(e, launch_conv_gemm(p, e->stream));
-    }
+    RET(denoise_inv_convs(e, ptr<float>(e->dn_spec), ptr<float>(e->dn_ola), e->dn_h.data(), ragged ? lens : nullptr, B, R));   // (one launch per tap)
   }
   ProfScope ps(e, "denoise_ola", 0, (double)B * n * (4.0 + (wav ? 4.0 : 0.0) + (pcm ? 2.0 : 0.0)));
   KCHK(e, launch_ola_norm(ptr<float>(e->dn_ola), in, in_bs, lens, lens + B, ptr<double>(e->dn_win), wav, pcm, B, n, R, d.nfft, d.hop, e->stream));
@@ -2350,6 +2372,60 @@ int denoise_ready(e2etts_engine* e) {
   if (!e->dn.have_bias) return e->fail(E2ETTS_ESTATE, "no denoiser bias spectrum (e2etts_denoiser_set_bias / e2etts_denoiser_calibrate)");
   return E2ETTS_OK;
 }
+
+// The denoiser as a function of one window of a stream, on the engine's CURRENT stream (the slot's, swapped in) and in the slot's own
+// workspace.  seg: L vocoder samples per row (stride seg_bs) that start at absolute sample S0 of the stream; the window's left edge is the
+// stream's start iff S0 == 0, its right edge the stream's end iff right_real.  Writes the denoised samples seg[e0 .. e0 + n_out) of every row
+// to sl.dn_wav / sl.dn_pcm [B, n_out].  The caller keeps filter_length - hop samples of context between a context edge and the emitted range:
+// the frames a context edge lacks (zero frames here, as past a real end) spoil only those.  Every spectrum element and every tap of the
+// inverse is the same k-ordered fp32 chain as in denoise_impl on the whole signal, on the same absolute frame grid: same bits.
+int denoise_stream_impl(e2etts_engine* e, e2etts_engine::StSlot& sl, const float* seg, long long seg_bs, int B, long long L, long long S0, bool right_real,
+                        long long e0, long long n_out, float strength) {
+  const auto& d = e->dn;
+  const int half = d.nfft / 2;
+  const bool left_real = S0 == 0;
+  RET(ensure(e, sl.dn_wav, (size_t)B * n_out * 4));
+  RET(ensure(e, sl.dn_pcm, (size_t)B * n_out * 2));
+  const double* win = ptr<double>(e->dn_win);
+  if (left_real && right_real && L <= half) {   // the whole stream cannot be reflected: copied through, as e2etts_denoise does with such a row
+    ProfScope ps(e, "denoise_ola", 0, (double)B * n_out * 10.0);
+    KCHK(e, launch_ola_norm_stream(nullptr, 0, 0, seg + e0, seg_bs, win, ptr<float>(sl.dn_wav), ptr<int16_t>(sl.dn_pcm), B, n_out, S0 + e0 + half, 1, d.nfft,
+                                   d.hop, true, e->stream));
+    return E2ETTS_OK;
+  }
+  const long long lead = left_real ? half : 0, padded = L + lead + (right_real ? half : 0);
+  const int R = (int)(padded / d.hop), G = R - d.nov + 1;   // padded rows = spectrum rows = overlap-add rows; whole frames in the window
+  if (G <= 0 || e0 < 0 || e0 + n_out > L) return e->fail(E2ETTS_EINVAL, "denoised stream: window of %lld samples too short", L);
+  if ((long long)R > ((1LL << 31) - 1) / ((long long)d.cpad * 4))
+    return e->fail(E2ETTS_EINVAL, "denoised stream: the window's spectrum (%d rows of %d floats) must stay below 2 GiB: push smaller chunks", R, d.cpad);
+  RET(ensure(e, sl.dn_pad, (size_t)B * R * d.hop * 4));
+  RET(ensure(e, sl.dn_spec, (size_t)B * R * d.cpad * 4));
+  RET(ensure(e, sl.dn_ola, (size_t)B * R * d.hop * 4));
+  RET(ensure(e, sl.dn_lens, (size_t)B * 4));
+  std::vector<int32_t> tab((size_t)(2 + d.nov) * B);   // denoise_table's layout, every row alike (read by the host only)
+  for (int b = 0; b < B; ++b) {
+    tab[b] = (int32_t)L;
+    tab[(size_t)B + b] = G;
+    for (int s = 0; s < d.nov; ++s) tab[(size_t)(2 + s) * B + b] = R - s;
+  }
+  {
+    ProfScope ps(e, "denoise_pad", 0, (double)B * R * d.hop * 8.0);
+    KCHK(e, launch_fill_i32(ptr<int32_t>(sl.dn_lens), B, G, e->stream));
+    KCHK(e, launch_stft_pad_stream(seg, seg_bs, ptr<float>(sl.dn_pad), B, L, R, d.nfft, d.hop, left_real, right_real, e->stream));
+  }
+  RET(denoise_fwd_conv(e, ptr<float>(sl.dn_pad), ptr<float>(sl.dn_spec), tab.data(), nullptr, B, R));
+  {
+    ProfScope ps(e, "denoise_sub", 0, (double)B * R * d.cpad * 8.0);
+    KCHK(e, launch_spectral_subtract(ptr<float>(sl.dn_spec), ptr<float>(e->dn_bias), ptr<int32_t>(sl.dn_lens), B, R, d.cpad, d.nfft, d.nov, strength, e->stream));
+  }
+  RET(denoise_inv_convs(e, ptr<float>(sl.dn_spec), ptr<float>(sl.dn_ola), tab.data(), nullptr, B, R));
+  ProfScope ps(e, "denoise_ola", 0, (double)B * n_out * 14.0);
+  KCHK(e, launch_ola_norm_stream(ptr<float>(sl.dn_ola), (long long)R * d.hop, e0 + lead, seg + e0, seg_bs, win, ptr<float>(sl.dn_wav), ptr<int16_t>(sl.dn_pcm), B,
+                                 n_out, S0 + e0 + half, right_real ? (S0 + L) / d.hop + 1 : LLONG_MAX, d.nfft, d.hop, false, e->stream));
+  return E2ETTS_OK;
+}
+
+bool denoised_stream_busy(const e2etts_engine* e) { return e->st_open && e->st_dn && (!e->st_done || e->st_pending > 0); }
 
 }  // namespace
 
@@ -2793,12 +2869,23 @@ struct CtxSwap {
   ~CtxSwap() { swap(); }
 };
 
-int e2etts_vocoder_stream_begin(e2etts_engine* e, int B) {
+// denoise_strength < 0: a plain stream; else a denoised one, *delay_out = its extra frames of context per side
+static int stream_begin(e2etts_engine* e, int B, float denoise_strength, int* delay_out) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
   if (B <= 0 || B > 4096) return e->fail(E2ETTS_EINVAL, "B out of range");
+  const bool dn = denoise_strength >= 0.f;
+  int delay = 0;
+  if (dn) {   // refused before anything of an open stream is touched
+    RET(denoise_ready(e));
+    if (e->cfg.hop_length % e->dn.hop)
+      return e->fail(E2ETTS_EINVAL, "denoiser hop %d does not divide the vocoder's hop_length %d", e->dn.hop, e->cfg.hop_length);
+    if (e->cfg.voc_istft_nfft != 0)
+      return e->fail(E2ETTS_EINVAL, "a denoised stream does not serve the iSTFT tail (its tap buffers are engine-wide: two chunks in flight would share them)");
+    delay = (e->dn.nfft - e->dn.hop + e->cfg.hop_length - 1) / e->cfg.hop_length;
+  }
   for (auto& sl : e->st_slot) {
     if (!sl.done) HIPCHK(e, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.win_ready) HIPCHK(e, hipEventCreateWithFlags(&sl.win_ready, hipEventDisableTiming));
@@ -2821,9 +2908,25 @@ int e2etts_vocoder_stream_begin(e2etts_engine* e, int B) {
   e->st_carry_n = 0;
   e->st_emitted = 0;
   e->st_halo = vocoder_halo_frames(e->cfg);
+  e->st_dn = dn;
+  e->st_strength = dn ? denoise_strength : 0.f;
+  e->st_delay = delay;
+  e->st_abs0 = 0;
   e->st_open = true;
   e->st_done = false;
+  if (delay_out) *delay_out = delay;
   return e->st_halo;
+}
+
+int e2etts_vocoder_stream_begin(e2etts_engine* e, int B) { return stream_begin(e, B, -1.f, nullptr); }
+
+int e2etts_vocoder_stream_begin_denoised(e2etts_engine* e, int B, float strength, int* delay_frames_out) {
+  if (!e) return E2ETTS_EINVAL;
+  if (!(strength >= 0.f)) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    return e->fail(E2ETTS_EINVAL, "strength must be >= 0");
+  }
+  return stream_begin(e, B, strength, delay_frames_out);
 }
 
 // Whether a caller's pointer is ordinary (pageable) host memory: such a chunk is copied into the slot's pinned buffer before _push
@@ -2844,7 +2947,8 @@ int e2etts_vocoder_stream_push(e2etts_engine* e, const float* mel_btc, int n, in
   if (!e->st_open || e->st_done) return e->fail(E2ETTS_ESTATE, "no open vocoder stream");
   if (n < 0 || (n > 0 && !mel_btc)) return e->fail(E2ETTS_EINVAL, "bad chunk");
   if (e->st_pending >= e2etts_engine::ST_DEPTH) return e->fail(E2ETTS_ESTATE, "%d chunks await e2etts_vocoder_stream_fetch", e2etts_engine::ST_DEPTH);
-  const int B = e->st_B, H = e->st_halo, M = e->cfg.n_mel;
+  // a denoised stream keeps st_delay frames more on each side: what the denoiser's frames reach beyond a sample (denoise_stream_impl)
+  const int B = e->st_B, H = e->st_halo + e->st_delay, M = e->cfg.n_mel;
   const int total = e->st_carry_n + n;
   if (n_frames_out) *n_frames_out = 0;
   auto& sl = e->st_slot[(e->st_head + e->st_pending) % e2etts_engine::ST_DEPTH];   // free: whatever used it last has been fetched, hence has finished
@@ -2882,6 +2986,8 @@ int e2etts_vocoder_stream_push(e2etts_engine* e, const float* mel_btc, int n, in
                                (size_t)keep_n * M * 4, B, hipMemcpyDeviceToDevice, cp));
   }
   e->st_carry_n = keep_n;
+  const long long win_abs0 = e->st_abs0;
+  e->st_abs0 += keep_from;
   if (last) e->st_done = true;
   if (n_emit > 0) {
     HIPCHK(e, hipEventRecord(sl.win_ready, cp));
@@ -2891,6 +2997,14 @@ int e2etts_vocoder_stream_push(e2etts_engine* e, const float* mel_btc, int n, in
     {
       CtxSwap in_slot(e, sl.ctx);
       rc = vocoder_impl(e, ptr<float>(sl.win), B, total, true, true, nullptr, nullptr, &sl.wav, &sl.pcm);
+      if (rc == E2ETTS_OK && e->st_dn) {
+        // the window's samples from st_delay frames before the emitted range to st_delay frames after it (or to the stream's ends): all of
+        // them have the vocoder's full halo in the window, i.e. are the one-shot vocoder's samples
+        const long long hl = e->cfg.hop_length;
+        const int d_lo = std::max(0, left_ctx - e->st_delay), d_hi = std::min(total, emit_end + e->st_delay);
+        rc = denoise_stream_impl(e, sl, ptr<float>(sl.wav) + (size_t)d_lo * hl, (long long)total * hl, B, (long long)(d_hi - d_lo) * hl,
+                                 (win_abs0 + d_lo) * hl, last && d_hi == total, (long long)(left_ctx - d_lo) * hl, (long long)n_emit * hl, e->st_strength);
+      }
     }
     if (rc != E2ETTS_OK) {   // the carried context has moved on already: this stream cannot be continued
       e->st_open = false;
@@ -2919,12 +3033,14 @@ int e2etts_vocoder_stream_fetch(e2etts_engine* e, float* wav_out, int16_t* pcm_o
   auto& sl = e->st_slot[e->st_head];
   const size_t hop = e->cfg.hop_length, ns = (size_t)sl.emit_n * hop;
   if (capacity < (size_t)e->st_B * ns) return e->fail(E2ETTS_EINVAL, "buffer holds %zu samples, chunk has %zu", capacity, (size_t)e->st_B * ns);
-  const size_t src_row = (size_t)sl.win_n * hop, off = (size_t)sl.emit_off * hop;
+  // a denoised stream's slot holds the emitted samples alone, [B, ns] compact
+  const size_t src_row = e->st_dn ? ns : (size_t)sl.win_n * hop, off = e->st_dn ? 0 : (size_t)sl.emit_off * hop;
+  DevBuf &src_wav = e->st_dn ? sl.dn_wav : sl.wav, &src_pcm = e->st_dn ? sl.dn_pcm : sl.pcm;
   HIPCHK(e, hipStreamWaitEvent(e->stream, sl.done, 0));
   if (wav_out)
-    HIPCHK(e, hipMemcpy2DAsync(wav_out, ns * 4, ptr<float>(sl.wav) + off, src_row * 4, ns * 4, e->st_B, hipMemcpyDefault, e->stream));
+    HIPCHK(e, hipMemcpy2DAsync(wav_out, ns * 4, ptr<float>(src_wav) + off, src_row * 4, ns * 4, e->st_B, hipMemcpyDefault, e->stream));
   if (pcm_out)
-    HIPCHK(e, hipMemcpy2DAsync(pcm_out, ns * 2, ptr<int16_t>(sl.pcm) + off, src_row * 2, ns * 2, e->st_B, hipMemcpyDefault, e->stream));
+    HIPCHK(e, hipMemcpy2DAsync(pcm_out, ns * 2, ptr<int16_t>(src_pcm) + off, src_row * 2, ns * 2, e->st_B, hipMemcpyDefault, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   e->st_head = (e->st_head + 1) % e2etts_engine::ST_DEPTH;
   --e->st_pending;
@@ -2969,6 +3085,7 @@ int e2etts_denoiser_load(e2etts_engine* e, const float* fwd_basis, const float* 
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (!fwd_basis || !inv_basis) return e->fail(E2ETTS_EINVAL, "fwd_basis / inv_basis must not be NULL");
+  if (denoised_stream_busy(e)) return e->fail(E2ETTS_ESTATE, "a denoised vocoder stream is open: its chunks in flight read the bases and the bias");
   int nov = 0;
   if (const char* m = denoiser_geometry_check(filter_length, hop, &nov))
     return e->fail(E2ETTS_EINVAL, "%s (filter_length %d, hop %d)", m, filter_length, hop);
@@ -3020,6 +3137,7 @@ int e2etts_denoiser_set_bias(e2etts_engine* e, const float* bias, int n_bins) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
+  if (denoised_stream_busy(e)) return e->fail(E2ETTS_ESTATE, "a denoised vocoder stream is open: its chunks in flight read the bases and the bias");
   if (!e->dn.loaded) return e->fail(E2ETTS_ESTATE, "no denoiser bases loaded (e2etts_denoiser_load)");
   if (!bias || n_bins != e->dn.nfft / 2 + 1)
     return e->fail(E2ETTS_EINVAL, "bias must hold filter_length / 2 + 1 = %d bins (caller said %d)", e->dn.nfft / 2 + 1, n_bins);
@@ -3033,6 +3151,7 @@ int e2etts_denoiser_calibrate(e2etts_engine* e, const float* mel_btc_or_null, in
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
+  if (denoised_stream_busy(e)) return e->fail(E2ETTS_ESTATE, "a denoised vocoder stream is open: its chunks in flight read the bases and the bias");
   if (!e->dn.loaded) return e->fail(E2ETTS_ESTATE, "no denoiser bases loaded (e2etts_denoiser_load)");
   if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
   if (T <= 0) return e->fail(E2ETTS_EINVAL, "T must be positive");

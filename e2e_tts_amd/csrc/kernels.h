@@ -368,6 +368,19 @@ const char* launch_bias_frame(const float* spec_row, float* bias, int filter_len
 const char* launch_ola_norm(const float* y, const float* in, long long in_bs, const int32_t* n_valid, const int32_t* frames, const double* win_sq,
                             float* wav, int16_t* pcm, int B, long long n, int R, int filter_length, int hop, hipStream_t s);
 
+// Stream forms (the denoised streaming vocoder): one window of L samples per row (seg, row stride seg_bs) of a longer signal.  An edge that
+// is a real end of the signal is reflected (the window must then be longer than filter_length / 2), an edge that is context is copied:
+// out [B, Rq, hop] with Rq * hop = L + filter_length / 2 per real edge.
+const char* launch_stft_pad_stream(const float* seg, long long seg_bs, float* out, int B, long long L, int Rq, int filter_length, int hop, bool left_real,
+                                   bool right_real, hipStream_t s);
+const char* launch_fill_i32(int32_t* p, int n, int32_t v, hipStream_t s);
+// n emitted samples per row into wav / pcm [B, n]: sample k is y[b, y_off + k] (rows of stride y_bs), at absolute padded position p_abs0 + k,
+// normalised as launch_ola_norm does with the envelope of the absolute frames 0 .. F_abs - 1 (F_abs = LLONG_MAX: end not known yet).
+// pass: copies in[b, k] (row stride in_bs) instead -- a whole signal of at most filter_length / 2 samples.
+const char* launch_ola_norm_stream(const float* y, long long y_bs, long long y_off, const float* in, long long in_bs, const double* win_sq, float* wav,
+                                   int16_t* pcm, int B, long long n, long long p_abs0, long long F_abs, int filter_length, int hop, bool pass,
+                                   hipStream_t s);
+
 const char* launch_transpose_bct_btc(const float* in, float* out, int B, int C, int T, hipStream_t s);
 // wav = tanh(conv7(lrelu_0.01(x))) with Cout = 1; pcm = (int16)(int32)(wav * 32768)
 // act_rows / act_rows_host (optional, device / host copies of the same B values): only samples < act_rows[b] are needed (ragged batches):

@@ -36,6 +36,17 @@ def check_lengths(n_valid, n: int, hop: int) -> np.ndarray:
     return nv
 
 
+def stream_delay_frames(filter_length: int, hop: int, hop_length: int) -> int:
+    """Mel frames of context a denoised vocoder stream keeps on each side beyond the vocoder's halo (``*delay_frames_out`` of
+    e2etts_vocoder_stream_begin_denoised).  A denoised sample depends on the input samples strictly closer than filter_length - hop: every
+    frame that covers it, and every sample those frames cover; hop_length must be a multiple of hop, so that windows start on the frame grid."""
+    filter_length, hop, hop_length = int(filter_length), int(hop), int(hop_length)
+    check_geometry(filter_length, hop)
+    if hop_length <= 0 or hop_length % hop:
+        raise ValueError(f"denoiser: hop {hop} does not divide the vocoder's hop_length {hop_length}")
+    return -(-(filter_length - hop) // hop_length)
+
+
 def centre_pad(x: np.ndarray, size: int) -> np.ndarray:
     """Zero-pad to `size` with the data in the middle (the extra sample of an odd difference goes to the right)."""
     if len(x) > size:

@@ -338,3 +338,23 @@ class Denoiser:
         return out.unsqueeze(1)
 
     __call__ = forward
+
+    def stream(self, mel_chunks, strength: float = 0.1, want_pcm: bool = False):
+        """Generator over channels-last mel chunks [B, n, n_mel] (numpy / torch) on the vocoder's engine: yields numpy pieces
+        [B, n_emit * hop] (float32, or int16 with ``want_pcm``) that concatenate to ``forward(vocoder(whole mel), strength)`` bit for bit
+        while HBM use stays bounded by the chunk (e2etts_vocoder_stream_begin_denoised).  An EXTENSION: the reference has no stream --
+        its Denoiser takes the whole waveform.  B is read from the first chunk; the bases and the bias cannot be replaced (another
+        Denoiser on the same vocoder) until the generator is exhausted."""
+        eng = self._vocoder.engine
+        it = iter(mel_chunks)
+        first = next(it, None)
+        if first is None:
+            return
+        if len(first.shape) != 3 or int(first.shape[2]) != eng.dims.n_mel:
+            raise ValueError(f"expected mel chunks of shape [B, n, {eng.dims.n_mel}], got {tuple(first.shape)}")
+
+        def chunks():
+            yield first
+            yield from it
+
+        yield from eng.vocoder_stream(chunks(), int(first.shape[0]), want_pcm=want_pcm, denoise_strength=float(strength))

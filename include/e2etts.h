@@ -238,8 +238,25 @@ E2ETTS_API int e2etts_fetch_wav(e2etts_engine* engine, float* wav_out, size_t ca
  * copy stream while chunk i + 1 computes.  Each in-flight chunk has its own output buffers; the resident one-shot result
  * (e2etts_fetch_wav / _pcm) is not touched by the stream.  A chunk in pageable host memory has been consumed when _push returns; one in
  * device memory, or in host memory the caller pinned, must stay valid until the fetch of that push (or e2etts_sync) returns.  Errors of
- * the enqueued work surface at the fetch. */
+ * the enqueued work surface at the fetch.
+ *
+ * _begin_denoised(B, strength, &delay) opens a DENOISED stream (vocoder-bias denoiser, below): the concatenated pieces are bit-identical to
+ * e2etts_denoise(wav = e2etts_vocoder(whole mel), n_valid = T * hop_length for every row, strength), as fp32 and as saturated int16, in every
+ * vocoder precision, for any chunking and with two chunks in flight.  The reference's reflect padding happens at the true start and the
+ * true end of the stream only, never at a chunk border; a stream of at most filter_length / 2 samples in total is copied through unchanged
+ * (e2etts_denoise's rule for a row that cannot be reflected); strength 0 is allowed and equals e2etts_denoise(..., 0).
+ * It returns the vocoder's halo like _begin, and *delay = C = ceil((filter_length - hop) / hop_length) (3 for 1024 / 256 at hop_length 256):
+ * the denoiser's frames reach filter_length - hop samples beyond a sample, so every window carries C more mel frames of context per side
+ * and emitted frames lag pushed ones by halo + C.  The denoiser runs on the window's waveform, per slot, in a workspace of the slot's own
+ * (bounded by the chunk): nothing of it is carried between chunks.  _push and _fetch are used as above; n_emit counts frames whose
+ * DENOISED samples became final and _fetch hands those out.  One-shot calls (e2etts_denoise included) between the steps do not disturb it.
+ * Errors: E2ETTS_ESTATE without bases or bias; E2ETTS_EINVAL for a negative strength, for a denoiser hop that does not divide hop_length and
+ * for the iSTFT tail (voc_istft_nfft != 0: its tap buffers are engine-wide).  While a denoised stream is open and unfinished (until its last
+ * chunk is fetched, or the next _begin / _begin_denoised, which abandons it) e2etts_denoiser_load, _set_bias and _calibrate return
+ * E2ETTS_ESTATE: chunks in flight read the bases and the bias.  e2etts_load_weights closes it like any stream.  _begin itself is
+ * unchanged: a stream opened with it is never denoised, whatever e2etts_set_denoise says. */
 E2ETTS_API int e2etts_vocoder_stream_begin(e2etts_engine* engine, int B);
+E2ETTS_API int e2etts_vocoder_stream_begin_denoised(e2etts_engine* engine, int B, float strength, int* delay_frames_out);
 E2ETTS_API int e2etts_vocoder_stream_push(e2etts_engine* engine, const float* mel_btc, int n_frames, int last, int* n_frames_out);
 E2ETTS_API int e2etts_vocoder_stream_fetch(e2etts_engine* engine, float* wav_out, int16_t* pcm_out, size_t capacity);
 
@@ -288,7 +305,8 @@ E2ETTS_API int e2etts_tempo(e2etts_engine* engine, const int16_t* pcm_in, size_t
  *   samples (mel_lens[b] * hop_length; hop_length must be a multiple of the denoiser's hop) before the int16 conversion: its PCM, and the
  *   PCM e2etts_fetch_pcm hands out, are exactly e2etts_denoise of the resident wav (which e2etts_fetch_wav still returns as the vocoder
  *   left it); samples past a row's valid ones are 0.  0 (the default) leaves every path as it is without a denoiser.  e2etts_vocoder[_btc]
- *   and the streaming vocoder (e2etts_vocoder_stream_*) are never denoised: streaming denoise is out of scope. */
+ *   and a stream opened with e2etts_vocoder_stream_begin are never denoised; e2etts_vocoder_stream_begin_denoised (above) opens a stream
+ *   that is, with a strength of its own. */
 E2ETTS_API int e2etts_denoiser_load(e2etts_engine* engine, const float* fwd_basis, const float* inv_basis, const float* win_sq_or_null,
                                     int filter_length, int hop);
 E2ETTS_API int e2etts_denoiser_set_bias(e2etts_engine* engine, const float* bias, int n_bins);
