@@ -1,0 +1,863 @@
+// libe2etts_align.so: the reference's AlignmentEncoder (U/layers.py:275-369) and monotonic alignment search (U/function.py:96-137) behind
+// the C ABI of include/e2etts_align.h.  A companion of libe2etts_hip.so that shares its kernel objects (the exact-fp32 convolution
+// launch_conv_gemm serves the projections) and none of its entry points.
+//
+// Three kinds of device work per call:
+//   projections   key_proj / query_proj as exact-fp32 conv_gemm launches on channels-last [B, N, C] tensors, the speaker terms added to every
+//                 position first (aln_add_rows_kernel);
+//   attention     aln_attn_kernel: squared distance in the direct form, both softmaxes and the prior in one pass per 16-frame tile, the
+//                 scores of the tile living in LDS -- the reference's [B, n_att, T, L] tensor is never formed;
+//   search        aln_mas_wave_kernel (L <= 256): one wavefront per utterance, 1, 2 or 4 phonemes per lane by the row width, the previous log_p row
+//                 in registers, one shuffle per frame; aln_mas_kernel (wider rows): one workgroup per utterance, threads over phonemes, the row ping-ponged in
+//                 LDS, one barrier per frame.  Back-pointers one bit per cell, one lane backtracks.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../../include/e2etts_align.h"
+#include "../host_logic.h"
+#include "../kernels.h"
+
+#ifndef E2EALIGN_SRC_HASH
+#define E2EALIGN_SRC_HASH "unknown"
+#endif
+
+using namespace e2etts;
+
+namespace {
+
+constexpr int MAS_THREADS = 256;
+constexpr int MAS_COLS = E2EALIGN_MAX_L / MAS_THREADS;   // columns per thread at the widest row
+constexpr size_t MAS_LDS_BUDGET = 40 * 1024;            // back-pointer bits live in LDS up to this (with the three [L] rows), else in the workspace
+constexpr size_t ATTN_LDS_MAX = 64 * 1024;
+
+// x[b, t, :] += s[b, :]
+__global__ void aln_add_rows_kernel(float* x, const float* s, int B, int N, int C) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long n = (long long)B * N * C;
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const int b = (int)(i / ((long long)N * C));
+  x[i] = x[i] + s[(size_t)b * C + c];
+}
+
+__device__ __forceinline__ float wave_max(float v) {
+  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One workgroup = TI = 4 * FPT frames of one utterance against ALL its L keys (padded ones included: the prior's log-softmax runs over
+// them).  Phase 1: 64 keys at a time in LDS (row stride odd: conflict-free), thread (wave g, lane j) accumulates the squared distance of key j
+// to the FPT frames of wave g in four interleaved fma chains per frame (channel c goes to chain c mod 4; chains summed (0 + 1) + (2 + 3)),
+// score = -temperature * d into the tile's score rows in LDS.  Phase 2: wave g owns its FPT rows; lanes stride the columns, so every lane
+// rereads only what it wrote: log_softmax over L columns + log(prior + 1e-8) when a prior is given, attn_logprob out, then the masked softmax
+// (masked keys exactly 0).  Every global access is guarded by t < T and j < L.
+template <int FPT>
+__global__ __launch_bounds__(256) void aln_attn_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ prior,
+                                                       const int32_t* __restrict__ txt_lens, float* __restrict__ attn, float* __restrict__ logp,
+                                                       int T, int L, int C, float temperature) {
+  constexpr int TI = 4 * FPT;
+  extern __shared__ __attribute__((aligned(16))) float aln_smem[];
+  const int Cs = C | 1;
+  float* sq = aln_smem;          // [TI][C]
+  float* sk = sq + TI * C;       // [64][Cs]
+  float* ss = sk + 64 * Cs;      // [TI][L]
+  const int b = blockIdx.y, i0 = blockIdx.x * TI, tid = threadIdx.x;
+  const int lane = tid & 63, g = tid >> 6;
+  for (int e = tid; e < TI * C; e += 256) {
+    const int i = e / C, c = e - i * C, t = i0 + i;
+    sq[e] = t < T ? q[((size_t)b * T + t) * C + c] : 0.f;
+  }
+  for (int j0 = 0; j0 < L; j0 += 64) {
+    __syncthreads();   // the previous key tile is consumed (first pass: sq is staged)
+    for (int e = tid; e < 64 * C; e += 256) {
+      const int j = e / C, c = e - j * C;
+      sk[j * Cs + c] = j0 + j < L ? k[((size_t)b * L + j0 + j) * C + c] : 0.f;
+    }
+    __syncthreads();
+    float acc[FPT][4];
+#pragma unroll
+    for (int f = 0; f < FPT; ++f) acc[f][0] = acc[f][1] = acc[f][2] = acc[f][3] = 0.f;
+    const float* kr = sk + lane * Cs;
+    int c = 0;
+    for (; c + 4 <= C; c += 4) {
+      const float k0 = kr[c], k1 = kr[c + 1], k2 = kr[c + 2], k3 = kr[c + 3];
+#pragma unroll
+      for (int f = 0; f < FPT; ++f) {
+        const float* qr = sq + (g * FPT + f) * C + c;
+        const float d0 = qr[0] - k0, d1 = qr[1] - k1, d2 = qr[2] - k2, d3 = qr[3] - k3;
+        acc[f][0] = fmaf(d0, d0, acc[f][0]);
+        acc[f][1] = fmaf(d1, d1, acc[f][1]);
+        acc[f][2] = fmaf(d2, d2, acc[f][2]);
+        acc[f][3] = fmaf(d3, d3, acc[f][3]);
+      }
+    }
+    for (; c < C; ++c) {   // C % 4 channels left: they continue chains 0 .. 2
+      const float kc = kr[c];
+#pragma unroll
+      for (int f = 0; f < FPT; ++f) {
+        const float d = sq[(g * FPT + f) * C + c] - kc;
+        if ((c & 3) == 0) acc[f][0] = fmaf(d, d, acc[f][0]);
+        else if ((c & 3) == 1) acc[f][1] = fmaf(d, d, acc[f][1]);
+        else acc[f][2] = fmaf(d, d, acc[f][2]);
+      }
+    }
+    if (j0 + lane < L) {
+#pragma unroll
+      for (int f = 0; f < FPT; ++f) ss[(g * FPT + f) * L + j0 + lane] = -temperature * ((acc[f][0] + acc[f][1]) + (acc[f][2] + acc[f][3]));
+    }
+  }
+  // phase 2 reads only what the same lane wrote (column j belongs to lane j mod 64 of wave g in both phases): no barrier needed
+  const int len = txt_lens ? txt_lens[b] : L;
+  for (int f = 0; f < FPT; ++f) {
+    const int t = i0 + g * FPT + f;
+    if (t >= T) break;   // wave-uniform
+    float* row = ss + (g * FPT + f) * L;
+    const size_t base = ((size_t)b * T + t) * L;
+    if (prior) {
+      float m = -INFINITY;
+      for (int j = lane; j < L; j += 64) m = fmaxf(m, row[j]);
+      m = wave_max(m);
+      float s = 0.f;
+      for (int j = lane; j < L; j += 64) s += expf(row[j] - m);
+      s = wave_sum(s);
+      const float ls = logf(s);
+      for (int j = lane; j < L; j += 64) row[j] = ((row[j] - m) - ls) + logf(prior[base + j] + 1e-8f);
+    }
+    float m2 = -INFINITY;
+    for (int j = lane; j < L; j += 64) {
+      const float v = row[j];
+      logp[base + j] = v;
+      if (j < len) m2 = fmaxf(m2, v);
+    }
+    m2 = wave_max(m2);
+    float s2 = 0.f;
+    for (int j = lane; j < len; j += 64) s2 += expf(row[j] - m2);
+    s2 = wave_sum(s2);
+    for (int j = lane; j < L; j += 64) attn[base + j] = j < len ? expf(row[j] - m2) / s2 : 0.f;
+  }
+}
+
+// Backtracking by one lane, from column n - 1 of the last frame: marks attn_hard, counts the marks per column, follows the back-pointer bits.
+__device__ __forceinline__ void mas_backtrack(const uint32_t* bits, int* cnt, float* hard, int b, int n, int m, int T, int L, int W) {
+  int idx = n - 1;
+  for (int i = m - 1; i >= 1; --i) {
+    cnt[idx] += 1;
+    if (hard) hard[((size_t)b * T + i) * L + idx] = 1.f;
+    if ((bits[(size_t)i * W + (idx >> 5)] >> (idx & 31)) & 1u) idx -= 1;
+  }
+  cnt[idx] += 1;
+  if (hard) hard[(size_t)b * T * L + idx] = 1.f;
+  // the reference's closing `opt[0, curr_text_idx] = 1` with curr_text_idx read from prev_ind's row 0, which is all zeros: opt[0, 0]
+  if (idx != 0) {
+    cnt[0] += 1;
+    if (hard) hard[(size_t)b * T * L] = 1.f;
+  }
+}
+
+// The same search for rows of at most MAS_WAVE_L phonemes in ONE wavefront per utterance: lane l owns the CPL columns CPL l .. CPL l + CPL - 1
+// (CPL = 1, 2 or 4 by the row width, so that narrow rows use every lane: the kernel is bound by its instruction count per frame, the fp32
+// logarithms first), the previous log_p row lives in registers and only column CPL l - 1 crosses lanes (one shuffle per frame) -- no barrier and no LDS round trip on
+// the frame-to-frame chain, which is what bounds the workgroup form.  Same additions, same comparisons, same bit layout of the back-pointers
+// (the CPL bits of a lane are merged over groups of 32 / CPL lanes into the word of their 32 columns), same backtracking.
+constexpr int MAS_WAVE_L = 256;
+constexpr int MAS_WAVE_R = 8;   // frames per register block
+template <int CPL>
+__global__ __launch_bounds__(64) void aln_mas_wave_kernel(const float* __restrict__ map, int is_log, const int32_t* __restrict__ in_lens,
+                                                          const int32_t* __restrict__ out_lens, uint32_t* bits_ws, int bits_in_lds, float* hard,
+                                                          float* __restrict__ dur, int T, int L, int W) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t mas_smem[];
+  int* cnt = (int*)mas_smem;   // [L]
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int n = in_lens[b], m = out_lens[b];
+  const float* a = map + (size_t)b * T * L;
+  uint32_t* bits = bits_in_lds ? mas_smem + L : bits_ws + (size_t)b * T * W;
+  for (int j = lane; j < L; j += 64) cnt[j] = 0;
+  const int j0 = CPL * lane;
+  // frames are loaded MAS_WAVE_R at a time, one block ahead of the block being combined: the frame-to-frame chain then waits on registers,
+  // not on a global load per frame
+  float prev[CPL], cur[MAS_WAVE_R][CPL], nxt[MAS_WAVE_R][CPL];
+#pragma unroll
+  for (int c = 0; c < CPL; ++c) prev[c] = -INFINITY;   // row 0: columns >= 1 are -inf
+  if (lane == 0) prev[0] = is_log ? a[0] : logf(a[0]);
+#pragma unroll
+  for (int r = 0; r < MAS_WAVE_R; ++r)
+#pragma unroll
+    for (int c = 0; c < CPL; ++c) cur[r][c] = (j0 + c < n && 1 + r < m) ? a[(size_t)(1 + r) * L + j0 + c] : 1.f;
+  for (int i0 = 1; i0 < m; i0 += MAS_WAVE_R) {
+#pragma unroll
+    for (int r = 0; r < MAS_WAVE_R; ++r)
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) nxt[r][c] = (j0 + c < n && i0 + MAS_WAVE_R + r < m) ? a[(size_t)(i0 + MAS_WAVE_R + r) * L + j0 + c] : 1.f;
+#pragma unroll
+    for (int r = 0; r < MAS_WAVE_R; ++r) {
+      const int i = i0 + r;
+      if (i >= m) break;   // wavefront-uniform
+      const float left = __shfl_up(prev[CPL - 1], 1, 64);   // column CPL l - 1 (lane 0: unused, column 0 has no diagonal)
+      uint32_t nib = 0;
+      float nw[CPL];
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) {
+        const int j = j0 + c;
+        float p = prev[c];
+        const float pd = c == 0 ? left : prev[c - 1];
+        if (j >= 1 && j < n && pd >= p) {   // the reference's >= : ties, -inf ties included, take the diagonal
+          p = pd;
+          nib |= 1u << c;
+        }
+        nw[c] = (is_log ? cur[r][c] : logf(cur[r][c])) + p;
+      }
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) prev[c] = nw[c];
+      if (CPL == 1) {
+        const unsigned long long bal = __ballot(nib != 0);
+        if (lane == 0) {
+          bits[(size_t)i * W] = (uint32_t)bal;
+          if (W > 1) bits[(size_t)i * W + 1] = (uint32_t)(bal >> 32);
+        }
+      } else {
+        constexpr int G = 32 / CPL;   // lanes per 32-column word
+        uint32_t word = nib << (CPL * (lane & (G - 1)));
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) word |= __shfl_xor(word, o, 64);
+        if ((lane & (G - 1)) == 0 && lane / G < W) bits[(size_t)i * W + lane / G] = word;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < MAS_WAVE_R; ++r)
+#pragma unroll
+      for (int c = 0; c < CPL; ++c) cur[r][c] = nxt[r][c];
+  }
+  __syncthreads();
+  if (lane == 0) mas_backtrack(bits, cnt, hard, b, n, m, T, L, W);
+  __syncthreads();
+  for (int j = lane; j < L; j += 64) dur[(size_t)b * L + j] = (float)cnt[j];
+}
+
+// mas_width1 on the slice [:m, :n] of utterance blockIdx.x (m = out_lens[b] frames, n = in_lens[b] phonemes).  Thread tid owns columns
+// tid, tid + 256, ... (MAS_COLS of them at most); the next frame's values are loaded before the current frame is combined.  The back-pointer
+// of a cell is ONE bit (1 = came from column j - 1), gathered per wavefront by a ballot and written by its first lane: bits[i][j / 32].
+// `hard` (optional) was zeroed by the host.  cnt[j] counts the marks of column j = attn_hard.sum over frames.
+__global__ __launch_bounds__(MAS_THREADS) void aln_mas_kernel(const float* __restrict__ map, int is_log, const int32_t* __restrict__ in_lens,
+                                                              const int32_t* __restrict__ out_lens, uint32_t* bits_ws, int bits_in_lds,
+                                                              float* hard, float* __restrict__ dur, int T, int L, int W) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t mas_smem[];
+  float* pp = (float*)mas_smem;   // [L] previous log_p row
+  float* pc = pp + L;             // [L] row being written
+  int* cnt = (int*)(pc + L);      // [L]
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = in_lens[b], m = out_lens[b];
+  const float* a = map + (size_t)b * T * L;
+  uint32_t* bits = bits_in_lds ? mas_smem + 3 * (size_t)L : bits_ws + (size_t)b * T * W;
+  for (int j = tid; j < L; j += MAS_THREADS) {
+    cnt[j] = 0;
+    if (j < n) {
+      float v = -INFINITY;   // row 0: columns >= 1 are -inf
+      if (j == 0) v = is_log ? a[0] : logf(a[0]);
+      pp[j] = v;
+    }
+  }
+  float nx[MAS_COLS];
+#pragma unroll
+  for (int c = 0; c < MAS_COLS; ++c) {
+    const int j = tid + c * MAS_THREADS;
+    nx[c] = (j < n && 1 < m) ? a[(size_t)L + j] : 1.f;
+  }
+  __syncthreads();
+  for (int i = 1; i < m; ++i) {
+    float cur[MAS_COLS];
+#pragma unroll
+    for (int c = 0; c < MAS_COLS; ++c) {
+      cur[c] = nx[c];
+      const int j = tid + c * MAS_THREADS;
+      nx[c] = (j < n && i + 1 < m) ? a[(size_t)(i + 1) * L + j] : 1.f;
+    }
+#pragma unroll
+    for (int c = 0; c < MAS_COLS; ++c) {
+      if (c * MAS_THREADS >= n) break;   // workgroup-uniform: every lane of a wavefront reaches the ballot
+      const int j = tid + c * MAS_THREADS;
+      bool diag = false;
+      if (j < n) {
+        float p = pp[j];
+        if (j >= 1) {
+          const float pd = pp[j - 1];
+          if (pd >= p) {   // the reference's >= : ties, -inf ties included, take the diagonal
+            p = pd;
+            diag = true;
+          }
+        }
+        pc[j] = (is_log ? cur[c] : logf(cur[c])) + p;
+      }
+      const unsigned long long bal = __ballot(diag);
+      if ((tid & 63) == 0) {
+        const int w = j >> 5;   // j is a multiple of 64 here
+        if (w < W) bits[(size_t)i * W + w] = (uint32_t)bal;
+        if (w + 1 < W) bits[(size_t)i * W + w + 1] = (uint32_t)(bal >> 32);
+      }
+    }
+    __syncthreads();
+    float* t = pp;
+    pp = pc;
+    pc = t;
+  }
+  if (tid == 0) mas_backtrack(bits, cnt, hard, b, n, m, T, L, W);
+  __syncthreads();
+  for (int j = tid; j < L; j += MAS_THREADS) dur[(size_t)b * L + j] = (float)cnt[j];
+}
+
+#ifdef E2EALIGN_TEST_HOOKS
+__global__ void aln_poison_kernel(uint32_t* p, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0x7fc00000u | (uint32_t)(i & 0xffff);
+}
+#endif
+
+struct Buf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+
+thread_local std::string g_create_error;
+
+}  // namespace
+
+struct e2ealign_handle {
+  int device = 0;
+  int n_mel = 0, n_att = 0, n_text = 0;
+  float temperature = 0.f;
+  std::mutex mu;
+  std::string err;
+  bool open = false;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[6] = {};
+  hipEvent_t order_ev = nullptr;
+  bool profile = false;
+  double last_ms[3] = {0, 0, 0};
+  size_t dev_bytes = 0;
+  // weights: one HBM image, pointers into it
+  Buf blob;
+  bool loaded = false;
+  const float *k0w = nullptr, *k0b = nullptr, *k2w = nullptr, *k2b = nullptr, *q0w = nullptr, *q0b = nullptr, *q2w = nullptr, *q2b = nullptr,
+              *q4w = nullptr, *q4b = nullptr, *kspkw = nullptr, *qspkw = nullptr;
+  // workspaces
+  Buf kx, ky, kenc, qx, qy, spk, kspk, qspk, prior, attn, logp, hard, dur, bits, map, lens_txt, lens_in, lens_out;
+  std::vector<int32_t> host_txt, host_in, host_out;   // int32 images of the length arrays: they outlive the asynchronous copies of a call
+  bool unfinished = false;   // a call returned on an error before its stream was drained
+  int rB = 0, rT = 0, rL = 0;   // geometry of the resident attn / attn_logprob (0: nothing resident)
+
+  int fail(int code, const std::string& msg) {
+    err = msg;
+    return code;
+  }
+};
+
+namespace {
+
+#define HIPCHK(h, call)                                                                                     \
+  do {                                                                                                      \
+    hipError_t e_ = (call);                                                                                 \
+    if (e_ != hipSuccess) return (h)->fail(E2EALIGN_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define KCHK(h, call)                                            \
+  do {                                                           \
+    const char* m_ = (call);                                     \
+    if (m_) return (h)->fail(E2EALIGN_EHIP, std::string("launch refused: ") + m_); \
+  } while (0)
+#define RET(call)                      \
+  do {                                 \
+    int rc_ = (call);                  \
+    if (rc_ != E2EALIGN_OK) return rc_; \
+  } while (0)
+
+bool is_device_pointer(const void* p) {
+  hipPointerAttribute_t attr;
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeDevice;
+}
+
+int open_device(e2ealign_handle* h) {
+  HIPCHK(h, hipSetDevice(h->device));
+  if (h->open) return E2EALIGN_OK;
+  HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  for (auto& e : h->ev) HIPCHK(h, hipEventCreate(&e));
+  HIPCHK(h, hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
+  h->open = true;
+  return E2EALIGN_OK;
+}
+
+int reserve(e2ealign_handle* h, Buf& b, size_t bytes) {
+  bytes = (bytes + 255) / 256 * 256;
+  if (b.bytes >= bytes) return E2EALIGN_OK;
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  if (b.p) {
+    HIPCHK(h, hipFree(b.p));
+    h->dev_bytes -= b.bytes;
+    b.p = nullptr;
+    b.bytes = 0;
+  }
+  if (hipMalloc(&b.p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    b.p = nullptr;
+    return h->fail(E2EALIGN_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
+  }
+  b.bytes = bytes;
+  h->dev_bytes += bytes;
+  return E2EALIGN_OK;
+}
+
+// [B] int64 lengths (host or device memory) -> host vector; validated against [1, hi] by the caller
+int fetch_lens(e2ealign_handle* h, const int64_t* p, int B, std::vector<int64_t>& out) {
+  out.resize(B);
+  if (is_device_pointer(p)) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpy(out.data(), p, (size_t)B * 8, hipMemcpyDefault));
+  } else {
+    memcpy(out.data(), p, (size_t)B * 8);
+  }
+  return E2EALIGN_OK;
+}
+
+int check_lens(e2ealign_handle* h, const std::vector<int64_t>& v, long long hi, const char* name, const char* hi_name) {
+  for (size_t b = 0; b < v.size(); ++b)
+    if (v[b] < 1 || v[b] > hi)
+      return h->fail(E2EALIGN_EINVAL, std::string(name) + "[" + std::to_string(b) + "] = " + std::to_string((long long)v[b]) + " outside [1, " + hi_name +
+                                          " = " + std::to_string(hi) + "]");
+  return E2EALIGN_OK;
+}
+
+int check_dims(e2ealign_handle* h, int B, int T, int L) {
+  if (B < 1 || T < 1 || L < 1) return h->fail(E2EALIGN_EINVAL, "B, T and L must be positive (got " + std::to_string(B) + ", " + std::to_string(T) + ", " + std::to_string(L) + ")");
+  if (B > E2EALIGN_MAX_B) return h->fail(E2EALIGN_EINVAL, "B > " + std::to_string(E2EALIGN_MAX_B));
+  if (L > E2EALIGN_MAX_L) return h->fail(E2EALIGN_EINVAL, "L > " + std::to_string(E2EALIGN_MAX_L));
+  if ((long long)T * L >= (1LL << 28)) return h->fail(E2EALIGN_EINVAL, "one utterance's map (T * L) must stay below 2^28 cells");
+  if ((long long)B * T * L >= (1LL << 33)) return h->fail(E2EALIGN_EINVAL, "B * T * L too large");
+  return E2EALIGN_OK;
+}
+
+size_t attn_lds_bytes(int TI, int L, int C) { return ((size_t)TI * C + 64 * (size_t)(C | 1) + (size_t)TI * L) * 4; }
+
+// `host` belongs to the handle and is rewritten by the next call only, after this call's stream has drained (begin_call): no wait here
+int upload_lens(e2ealign_handle* h, Buf& dst, std::vector<int32_t>& host, const std::vector<int64_t>& v) {
+  host.assign(v.begin(), v.end());
+  RET(reserve(h, dst, host.size() * 4));
+  HIPCHK(h, hipMemcpyAsync(dst.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, h->stream));
+  return E2EALIGN_OK;
+}
+
+// after validation, before the first thing a computing call enqueues
+int begin_call(e2ealign_handle* h) {
+  RET(open_device(h));
+  if (h->unfinished) HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->unfinished = true;
+  return E2EALIGN_OK;
+}
+
+ConvParams conv(const float* in, const float* w, const float* bias, float* out, int B, int N, int Cin, int Cout, int KW, int act) {
+  ConvParams p;
+  p.in = in; p.w = w; p.bias = bias; p.out = out;
+  p.B = B; p.T = N; p.Cin = Cin; p.Cout = Cout; p.KW = KW; p.dil = 1; p.pad = (KW - 1) / 2;
+  p.in_ld = Cin; p.out_ld = Cout;
+  p.in_bs = (long long)N * Cin; p.out_bs = (long long)N * Cout;
+  p.x3 = 0;   // exact fp32
+  p.act = act;
+  return p;
+}
+
+// validated arguments of a forward
+struct FwdArgs {
+  const float *mel, *keys, *speaker, *prior;
+  const std::vector<int64_t>* txt_lens;   // null: no mask
+  int B, T, L;
+};
+
+int check_forward(e2ealign_handle* h, const FwdArgs& a) {
+  RET(check_dims(h, a.B, a.T, a.L));
+  if (!a.mel || !a.keys) return h->fail(E2EALIGN_EINVAL, "mel and keys must not be NULL");
+  if (!h->loaded) return h->fail(E2EALIGN_ESTATE, "e2ealign_forward before e2ealign_load_weights");
+  // what launch_conv_gemm would refuse (32-bit offsets inside one utterance; widths and alignment are settled by e2ealign_create and the
+  // 256-byte aligned buffers): refused here, so that no launcher can object once copies are enqueued
+  if ((long long)a.T * 2 * h->n_mel * 4 >= (1LL << 31) || (long long)a.L * 2 * h->n_text * 4 >= (1LL << 31))
+    return h->fail(E2EALIGN_EINVAL, "one utterance's widest projection (T * 2 n_mel or L * 2 n_text floats) must stay below 2 GiB");
+  if (attn_lds_bytes(4, a.L, h->n_att) > ATTN_LDS_MAX) return h->fail(E2EALIGN_EINVAL, "L * n_att too large for the attention pass's LDS tile");
+  return E2EALIGN_OK;
+}
+
+int run_forward(e2ealign_handle* h, const FwdArgs& a) {
+  const int B = a.B, T = a.T, L = a.L, M = h->n_mel, H = h->n_text, A = h->n_att;
+  const size_t BTL = (size_t)B * T * L;
+  h->rB = h->rT = h->rL = 0;
+  RET(reserve(h, h->kx, (size_t)B * L * H * 4));
+  RET(reserve(h, h->ky, (size_t)B * L * 2 * H * 4));
+  RET(reserve(h, h->kenc, (size_t)B * L * A * 4));
+  RET(reserve(h, h->qx, (size_t)B * T * M * 4));
+  RET(reserve(h, h->qy, (size_t)B * T * (2 * M > A ? 2 * M : A) * 4));
+  RET(reserve(h, h->attn, BTL * 4));
+  RET(reserve(h, h->logp, BTL * 4));
+  if (a.txt_lens) RET(upload_lens(h, h->lens_txt, h->host_txt, *a.txt_lens));
+  const float* prior = nullptr;
+  if (a.prior) {
+    if (is_device_pointer(a.prior)) {
+      prior = a.prior;
+    } else {
+      RET(reserve(h, h->prior, BTL * 4));
+      HIPCHK(h, hipMemcpyAsync(h->prior.p, a.prior, BTL * 4, hipMemcpyDefault, h->stream));
+      prior = (const float*)h->prior.p;
+    }
+  }
+  hipStream_t s = h->stream;
+  HIPCHK(h, hipMemcpyAsync(h->kx.p, a.keys, (size_t)B * L * H * 4, hipMemcpyDefault, s));
+  HIPCHK(h, hipMemcpyAsync(h->qx.p, a.mel, (size_t)B * T * M * 4, hipMemcpyDefault, s));
+  if (h->profile) HIPCHK(h, hipEventRecord(h->ev[0], s));
+  float *kx = (float*)h->kx.p, *ky = (float*)h->ky.p, *kenc = (float*)h->kenc.p, *qx = (float*)h->qx.p, *qy = (float*)h->qy.p;
+  if (a.speaker) {
+    RET(reserve(h, h->spk, (size_t)B * H * 4));
+    RET(reserve(h, h->kspk, (size_t)B * H * 4));
+    RET(reserve(h, h->qspk, (size_t)B * M * 4));
+    HIPCHK(h, hipMemcpyAsync(h->spk.p, a.speaker, (size_t)B * H * 4, hipMemcpyDefault, s));
+    // LinearNorm without bias on the B speaker vectors (one "utterance" of B rows), then added to every position
+    KCHK(h, launch_conv_gemm(conv((const float*)h->spk.p, h->kspkw, nullptr, (float*)h->kspk.p, 1, B, H, H, 1, ACT_NONE), s));
+    KCHK(h, launch_conv_gemm(conv((const float*)h->spk.p, h->qspkw, nullptr, (float*)h->qspk.p, 1, B, H, M, 1, ACT_NONE), s));
+    const long long nk = (long long)B * L * H, nq = (long long)B * T * M;
+    hipLaunchKernelGGL(aln_add_rows_kernel, dim3((unsigned)((nk + 255) / 256)), dim3(256), 0, s, kx, (const float*)h->kspk.p, B, L, H);
+    hipLaunchKernelGGL(aln_add_rows_kernel, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s, qx, (const float*)h->qspk.p, B, T, M);
+  }
+  // key_proj: conv k = 3 (H -> 2H), ReLU, conv k = 1 (2H -> n_att); query_proj: conv k = 3 (M -> 2M), ReLU, 1x1 (2M -> M), ReLU, 1x1 (M -> n_att)
+  KCHK(h, launch_conv_gemm(conv(kx, h->k0w, h->k0b, ky, B, L, H, 2 * H, 3, ACT_RELU), s));
+  KCHK(h, launch_conv_gemm(conv(ky, h->k2w, h->k2b, kenc, B, L, 2 * H, A, 1, ACT_NONE), s));
+  KCHK(h, launch_conv_gemm(conv(qx, h->q0w, h->q0b, qy, B, T, M, 2 * M, 3, ACT_RELU), s));
+  KCHK(h, launch_conv_gemm(conv(qy, h->q2w, h->q2b, qx, B, T, 2 * M, M, 1, ACT_RELU), s));
+  KCHK(h, launch_conv_gemm(conv(qx, h->q4w, h->q4b, qy, B, T, M, A, 1, ACT_NONE), s));
+  if (h->profile) HIPCHK(h, hipEventRecord(h->ev[1], s));
+  const int32_t* lens = a.txt_lens ? (const int32_t*)h->lens_txt.p : nullptr;
+  if (attn_lds_bytes(16, L, A) <= ATTN_LDS_MAX) {
+    hipLaunchKernelGGL(aln_attn_kernel<4>, dim3((T + 15) / 16, B), dim3(256), attn_lds_bytes(16, L, A), s, (const float*)qy, (const float*)kenc, prior, lens,
+                       (float*)h->attn.p, (float*)h->logp.p, T, L, A, h->temperature);
+  } else {
+    hipLaunchKernelGGL(aln_attn_kernel<1>, dim3((T + 3) / 4, B), dim3(256), attn_lds_bytes(4, L, A), s, (const float*)qy, (const float*)kenc, prior, lens,
+                       (float*)h->attn.p, (float*)h->logp.p, T, L, A, h->temperature);
+  }
+  HIPCHK(h, hipGetLastError());
+  if (h->profile) HIPCHK(h, hipEventRecord(h->ev[2], s));
+  h->rB = B; h->rT = T; h->rL = L;
+  return E2EALIGN_OK;
+}
+
+// the search on a DEVICE map; lengths already validated
+int run_mas(e2ealign_handle* h, const float* dmap, int is_log, const std::vector<int64_t>& in_lens, const std::vector<int64_t>& out_lens, int B, int T,
+            int L, bool want_hard) {
+  const int W = (L + 31) / 32;
+  RET(upload_lens(h, h->lens_in, h->host_in, in_lens));
+  RET(upload_lens(h, h->lens_out, h->host_out, out_lens));
+  RET(reserve(h, h->dur, (size_t)B * L * 4));
+  RET(reserve(h, h->bits, (size_t)B * T * W * 4));
+  hipStream_t s = h->stream;
+  if (want_hard) {
+    RET(reserve(h, h->hard, (size_t)B * T * L * 4));
+    HIPCHK(h, hipMemsetAsync(h->hard.p, 0, (size_t)B * T * L * 4, s));
+  }
+  const bool wave = L <= MAS_WAVE_L;   // one wavefront per utterance, the row in registers; wider rows: one workgroup, the row in LDS
+  size_t lds = (wave ? 1 : 3) * (size_t)L * 4;
+  const size_t with_bits = lds + (size_t)T * W * 4;
+  const int in_lds = with_bits <= MAS_LDS_BUDGET ? 1 : 0;
+  if (in_lds) lds = with_bits;
+  if (h->profile) HIPCHK(h, hipEventRecord(h->ev[3], s));
+#define ALN_MAS_WAVE(CPL)                                                                                                                              \
+  hipLaunchKernelGGL(aln_mas_wave_kernel<CPL>, dim3(B), dim3(64), lds, s, dmap, is_log, (const int32_t*)h->lens_in.p, (const int32_t*)h->lens_out.p, \
+                     (uint32_t*)h->bits.p, in_lds, want_hard ? (float*)h->hard.p : nullptr, (float*)h->dur.p, T, L, W)
+  if (wave && L <= 64) ALN_MAS_WAVE(1);
+  else if (wave && L <= 128) ALN_MAS_WAVE(2);
+  else if (wave) ALN_MAS_WAVE(4);
+#undef ALN_MAS_WAVE
+  else
+    hipLaunchKernelGGL(aln_mas_kernel, dim3(B), dim3(MAS_THREADS), lds, s, dmap, is_log, (const int32_t*)h->lens_in.p, (const int32_t*)h->lens_out.p,
+                       (uint32_t*)h->bits.p, in_lds, want_hard ? (float*)h->hard.p : nullptr, (float*)h->dur.p, T, L, W);
+  HIPCHK(h, hipGetLastError());
+  if (h->profile) HIPCHK(h, hipEventRecord(h->ev[4], s));
+  return E2EALIGN_OK;
+}
+
+int finish(e2ealign_handle* h, bool fwd, bool mas) {
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->unfinished = false;
+  if (h->profile) {
+    float ms = 0.f;
+    h->last_ms[0] = h->last_ms[1] = h->last_ms[2] = 0.0;
+    if (fwd) {
+      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+      h->last_ms[0] = ms;
+      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
+      h->last_ms[1] = ms;
+    }
+    if (mas) {
+      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[3], h->ev[4]));
+      h->last_ms[2] = ms;
+    }
+  }
+  return E2EALIGN_OK;
+}
+
+int copy_out(e2ealign_handle* h, void* dst, const void* src, size_t bytes) {
+  if (dst) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, h->stream));
+  return E2EALIGN_OK;
+}
+
+struct Want {
+  const char* name;
+  const float** dst;
+  size_t numel;
+};
+
+}  // namespace
+
+extern "C" {
+
+const char* e2ealign_version(void) { return "e2etts-align 1 E2EALIGN_SRC_HASH=" E2EALIGN_SRC_HASH; }
+int e2ealign_abi_version(void) { return E2EALIGN_ABI_VERSION; }
+
+const char* e2ealign_last_error(const e2ealign_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+int e2ealign_create(int device_id, int n_mel, int n_att, int n_text, float temperature, e2ealign_handle** out) {
+  if (!out) {
+    g_create_error = "out is NULL";
+    return E2EALIGN_EINVAL;
+  }
+  *out = nullptr;
+  if (device_id < 0 || n_mel < 4 || n_att < 1 || n_text < 4 || n_mel % 4 || n_text % 4 || n_att > E2EALIGN_MAX_ATT || n_mel > 4096 || n_text > 4096 ||
+      !(temperature == temperature)) {
+    g_create_error = "e2ealign_create: need device_id >= 0, n_mel and n_text positive multiples of 4 (<= 4096), 1 <= n_att <= " +
+                     std::to_string(E2EALIGN_MAX_ATT) + " and a temperature that is a number (got n_mel " + std::to_string(n_mel) + ", n_att " +
+                     std::to_string(n_att) + ", n_text " + std::to_string(n_text) + ")";
+    return E2EALIGN_EINVAL;
+  }
+  e2ealign_handle* h = new (std::nothrow) e2ealign_handle();
+  if (!h) {
+    g_create_error = "out of host memory";
+    return E2EALIGN_ENOMEM;
+  }
+  h->device = device_id;
+  h->n_mel = n_mel; h->n_att = n_att; h->n_text = n_text;
+  h->temperature = temperature;
+  *out = h;
+  return E2EALIGN_OK;
+}
+
+void e2ealign_destroy(e2ealign_handle* h) {
+  if (!h) return;
+  if (h->open && hipSetDevice(h->device) == hipSuccess) {
+    (void)hipStreamSynchronize(h->stream);
+    for (Buf* b : {&h->blob, &h->kx, &h->ky, &h->kenc, &h->qx, &h->qy, &h->spk, &h->kspk, &h->qspk, &h->prior, &h->attn, &h->logp, &h->hard, &h->dur, &h->bits,
+                   &h->map, &h->lens_txt, &h->lens_in, &h->lens_out})
+      if (b->p) (void)hipFree(b->p);
+    for (auto& e : h->ev)
+      if (e) (void)hipEventDestroy(e);
+    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
+    (void)hipStreamDestroy(h->stream);
+  }
+  delete h;
+}
+
+int e2ealign_load_weights(e2ealign_handle* h, const void* blob, size_t nbytes) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!blob) return h->fail(E2EALIGN_EINVAL, "blob is NULL");
+  if (nbytes < sizeof(BlobHeader)) return h->fail(E2EALIGN_EINVAL, "weight blob too small");
+  // header and directory on the host first (a device image is read back; nothing is enqueued until the directory holds every tensor)
+  const bool dev = is_device_pointer(blob);
+  BlobHeader hd;
+  if (dev) {
+    HIPCHK(h, hipSetDevice(h->device));
+    HIPCHK(h, hipMemcpy(&hd, blob, sizeof hd, hipMemcpyDefault));
+  } else {
+    memcpy(&hd, blob, sizeof hd);
+  }
+  if (const char* m = blob_check_header(hd, nbytes)) return h->fail(E2EALIGN_EINVAL, m);
+  std::vector<BlobEntry> dir(hd.n_entries);
+  if (hd.n_entries) {
+    if (dev) HIPCHK(h, hipMemcpy(dir.data(), (const char*)blob + sizeof hd, dir.size() * sizeof(BlobEntry), hipMemcpyDefault));
+    else memcpy(dir.data(), (const char*)blob + sizeof hd, dir.size() * sizeof(BlobEntry));
+  }
+  std::vector<BlobTensor> tensors;
+  std::string bad;
+  if (const char* m = blob_check_directory(hd, dir.data(), nbytes, tensors, bad)) return h->fail(E2EALIGN_EINVAL, std::string(m) + ": " + bad);
+  const size_t M = h->n_mel, H = h->n_text, A = h->n_att;
+  const float *k0w, *k0b, *k2w, *k2b, *q0w, *q0b, *q2w, *q2b, *q4w, *q4b, *kspkw, *qspkw;
+  const Want wants[] = {
+      {"aln.key.0.w", &k0w, 2 * H * 3 * H}, {"aln.key.0.b", &k0b, 2 * H},   {"aln.key.2.w", &k2w, A * 2 * H},   {"aln.key.2.b", &k2b, A},
+      {"aln.query.0.w", &q0w, 2 * M * 3 * M}, {"aln.query.0.b", &q0b, 2 * M}, {"aln.query.2.w", &q2w, M * 2 * M}, {"aln.query.2.b", &q2b, M},
+      {"aln.query.4.w", &q4w, A * M},       {"aln.query.4.b", &q4b, A},     {"aln.key_spk.w", &kspkw, H * H},   {"aln.query_spk.w", &qspkw, M * H},
+  };
+  uint64_t offs[sizeof wants / sizeof wants[0]];
+  for (size_t i = 0; i < sizeof wants / sizeof wants[0]; ++i) {
+    const BlobTensor* t = nullptr;
+    for (const auto& x : tensors)
+      if (x.name == wants[i].name) t = &x;
+    if (!t) return h->fail(E2EALIGN_EINVAL, std::string("weight blob has no tensor '") + wants[i].name + "'");
+    if (t->numel != wants[i].numel)
+      return h->fail(E2EALIGN_EINVAL, std::string("tensor '") + wants[i].name + "' has " + std::to_string(t->numel) + " elements, this aligner's dims need " +
+                                          std::to_string(wants[i].numel));
+    offs[i] = t->offset;
+  }
+  RET(open_device(h));
+  RET(reserve(h, h->blob, nbytes));
+  HIPCHK(h, hipMemcpyAsync(h->blob.p, blob, nbytes, hipMemcpyDefault, h->stream));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  for (size_t i = 0; i < sizeof wants / sizeof wants[0]; ++i) *wants[i].dst = (const float*)((const char*)h->blob.p + offs[i]);
+  h->k0w = k0w; h->k0b = k0b; h->k2w = k2w; h->k2b = k2b; h->q0w = q0w; h->q0b = q0b; h->q2w = q2w; h->q2b = q2b; h->q4w = q4w; h->q4b = q4b;
+  h->kspkw = kspkw; h->qspkw = qspkw;
+  h->loaded = true;
+  return E2EALIGN_OK;
+}
+
+void* e2ealign_stream(e2ealign_handle* h) {
+  if (!h) return nullptr;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (open_device(h) != E2EALIGN_OK) return nullptr;
+  return (void*)h->stream;
+}
+
+int e2ealign_order_after(e2ealign_handle* h, void* caller_stream) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RET(open_device(h));
+  HIPCHK(h, hipEventRecord(h->order_ev, (hipStream_t)caller_stream));
+  HIPCHK(h, hipStreamWaitEvent(h->stream, h->order_ev, 0));
+  return E2EALIGN_OK;
+}
+
+int e2ealign_sync(e2ealign_handle* h) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->open) return E2EALIGN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  return E2EALIGN_OK;
+}
+
+size_t e2ealign_device_bytes(const e2ealign_handle* h) { return h ? h->dev_bytes : 0; }
+
+int e2ealign_forward(e2ealign_handle* h, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens, const float* prior, int B,
+                     int T, int L, float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl;
+  FwdArgs a{mel, keys, speaker, prior, nullptr, B, T, L};
+  RET(check_forward(h, a));
+  if (txt_lens) {
+    RET(fetch_lens(h, txt_lens, B, tl));
+    RET(check_lens(h, tl, L, "txt_lens", "L"));
+    a.txt_lens = &tl;
+  }
+  RET(begin_call(h));
+  RET(run_forward(h, a));
+  const size_t n = (size_t)B * T * L * 4;
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, true, false);
+}
+
+int e2ealign_mas(e2ealign_handle* h, const float* map, int flags, const int64_t* in_lens, const int64_t* out_lens, int B, int T, int L,
+                 float* attn_hard_out, float* dur_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RET(check_dims(h, B, T, L));
+  if (flags & ~E2EALIGN_LOG_MAP) return h->fail(E2EALIGN_EINVAL, "unknown flag bits");
+  if (!in_lens || !out_lens) return h->fail(E2EALIGN_EINVAL, "in_lens and out_lens must not be NULL");
+  if (!map) {
+    if (!h->rB) return h->fail(E2EALIGN_EINVAL, "map is NULL and no attn is resident (no e2ealign_forward has completed)");
+    if (h->rB != B || h->rT != T || h->rL != L)
+      return h->fail(E2EALIGN_EINVAL, "map is NULL and (B, T, L) differ from the resident attn's (" + std::to_string(h->rB) + ", " + std::to_string(h->rT) + ", " +
+                                          std::to_string(h->rL) + ")");
+    if (flags & E2EALIGN_LOG_MAP) return h->fail(E2EALIGN_EINVAL, "the resident attn is a probability map: E2EALIGN_LOG_MAP does not apply");
+  }
+  std::vector<int64_t> il, ol;
+  RET(fetch_lens(h, in_lens, B, il));
+  RET(check_lens(h, il, L, "in_lens", "L"));
+  RET(fetch_lens(h, out_lens, B, ol));
+  RET(check_lens(h, ol, T, "out_lens", "T"));
+  RET(begin_call(h));
+  const size_t n = (size_t)B * T * L * 4;
+  const float* dmap = (const float*)h->attn.p;
+  if (map) {
+    if (is_device_pointer(map)) {
+      dmap = map;
+    } else {
+      RET(reserve(h, h->map, n));
+      HIPCHK(h, hipMemcpyAsync(h->map.p, map, n, hipMemcpyDefault, h->stream));
+      dmap = (const float*)h->map.p;
+    }
+  }
+  RET(run_mas(h, dmap, (flags & E2EALIGN_LOG_MAP) ? 1 : 0, il, ol, B, T, L, attn_hard_out != nullptr));
+  RET(copy_out(h, attn_hard_out, h->hard.p, n));
+  RET(copy_out(h, dur_out, h->dur.p, (size_t)B * L * 4));
+  return finish(h, false, true);
+}
+
+int e2ealign_align(e2ealign_handle* h, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens, const int64_t* mel_lens,
+                   const float* prior, int B, int T, int L, float* dur_out, float* attn_hard_out, float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl, ml;
+  FwdArgs a{mel, keys, speaker, prior, &tl, B, T, L};
+  RET(check_forward(h, a));
+  if (!txt_lens || !mel_lens) return h->fail(E2EALIGN_EINVAL, "txt_lens and mel_lens must not be NULL");
+  RET(fetch_lens(h, txt_lens, B, tl));
+  RET(check_lens(h, tl, L, "txt_lens", "L"));
+  RET(fetch_lens(h, mel_lens, B, ml));
+  RET(check_lens(h, ml, T, "mel_lens", "T"));
+  RET(begin_call(h));
+  RET(run_forward(h, a));
+  RET(run_mas(h, (const float*)h->attn.p, 0, tl, ml, B, T, L, attn_hard_out != nullptr));
+  const size_t n = (size_t)B * T * L * 4;
+  RET(copy_out(h, dur_out, h->dur.p, (size_t)B * L * 4));
+  RET(copy_out(h, attn_hard_out, h->hard.p, n));
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, true, true);
+}
+
+int e2ealign_profile_enable(e2ealign_handle* h, int on) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->profile = on != 0;
+  return E2EALIGN_OK;
+}
+
+int e2ealign_profile_read(e2ealign_handle* h, double ms_out[3]) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!ms_out) return h->fail(E2EALIGN_EINVAL, "ms_out is NULL");
+  for (int i = 0; i < 3; ++i) ms_out[i] = h->last_ms[i];
+  return E2EALIGN_OK;
+}
+
+#ifdef E2EALIGN_TEST_HOOKS
+int e2ealign_debug_poison_workspace(e2ealign_handle* h) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!h->open) return E2EALIGN_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  for (Buf* b : {&h->kx, &h->ky, &h->kenc, &h->qx, &h->qy, &h->spk, &h->kspk, &h->qspk, &h->prior, &h->attn, &h->logp, &h->hard, &h->dur, &h->bits, &h->map,
+                 &h->lens_txt, &h->lens_in, &h->lens_out}) {
+    if (!b->p) continue;
+    const size_t n = b->bytes / 4;
+    hipLaunchKernelGGL(aln_poison_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t*)b->p, n);
+  }
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->rB = h->rT = h->rL = 0;
+  return E2EALIGN_OK;
+}
+#endif
+
+}  // extern "C"

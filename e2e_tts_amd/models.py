@@ -7,6 +7,9 @@
 
 They are NOT nn.Modules and hold no torch parameters: ``load_state_dict`` packs the checkpoint into the
 engine's HBM image.  Training-side methods (``forward`` with targets, ``parse_batch``) are out of scope.
+
+Forced alignment -- the reference's ``AlignmentEncoder`` and ``b_mas``, i.e. the ``attn_out`` of its training forward -- is served by the
+companion library (include/e2etts_align.h): ``AlignmentEncoder``, ``b_mas`` and ``UnsupervisedFastSpeech2.align`` below.
 """
 from __future__ import annotations
 
@@ -147,10 +150,147 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         mel_lens = torch.from_numpy(r["mel_lens"]).to(dev)
         return (mel, mel_post, dur), mel_lens
 
+    def load_state_dict(self, state_dict: Mapping[str, object], strict: bool = True):
+        """As before for synthesis; additionally keeps what forced alignment reads (``variance_adaptor.aligner.*``, the phoneme and speaker
+        embedding tables) when the checkpoint holds it.  Nothing is sent to a GPU for it until ``align`` is called."""
+        super().load_state_dict(state_dict, strict)
+        self._aligner = None
+        self._align_state = None
+        if any(k.startswith(packer.ALIGNER_PREFIX) for k in state_dict):
+            keep = [k for k in state_dict if k.startswith(packer.ALIGNER_PREFIX)] + ["encoder.src_word_emb.weight", "speaker_emb.weight"]
+            self._align_state = {k: packer._np(state_dict[k]) for k in keep}
+        return self
+
+    def _ensure_aligner(self):
+        if getattr(self, "_align_state", None) is None:
+            raise RuntimeError("align() needs a loaded state dict that holds variance_adaptor.aligner.* (load_state_dict first)")
+        if self._aligner is None or self._aligner[0].encoder.device != self._device:
+            torch = _torch()
+            dev = torch.device("cuda", self._device)
+            temperature = self.config["variance"]["duration_modelling"]["aligner_temperature"]
+            H = self.config["encoder_hidden"]
+            enc = AlignmentEncoder(self.n_channels, self.n_channels, H, temperature, device=self._device)   # U/layers.py:30-35: n_att = n_mel
+            enc.load_state_dict({k[len(packer.ALIGNER_PREFIX):]: v for k, v in self._align_state.items() if k.startswith(packer.ALIGNER_PREFIX)})
+            emb = torch.from_numpy(np.ascontiguousarray(self._align_state["encoder.src_word_emb.weight"], dtype=np.float32)).to(dev)
+            spk = torch.from_numpy(np.ascontiguousarray(self._align_state["speaker_emb.weight"], dtype=np.float32)).to(dev)
+            self._aligner = (enc, emb, spk)
+        return self._aligner
+
+    def align(self, speaker, texts, txt_lens, mels, mel_lens, attn_prior=None):
+        """Forced alignment of recordings with the model's own aligner: the reference's ``attn_out`` (U/layers.py:203-212) without the rest
+        of the training forward.  speaker [B] (or one id for the batch), texts [B, L] int64, txt_lens [B], mels [B, T, n_mel] (the layout
+        ``inference`` returns; the reference's parse_batch transposes to it, U/model.py:80), mel_lens [B], attn_prior [B, T, L] or None -- the
+        beta-binomial prior is then built per row, as the reference's data preparation does.
+        -> (attn_soft [B, 1, T, L], attn_hard [B, 1, T, L], attn_hard_dur [B, L], attn_logprob [B, 1, T, L]), torch tensors on the GPU."""
+        from . import aligner as al
+        torch = _torch()
+        enc, emb, spk_table = self._ensure_aligner()
+        dev = torch.device("cuda", self._device)
+        ids = torch.as_tensor(texts, dtype=torch.int64).to(dev)
+        B, L = ids.shape
+        mel = torch.as_tensor(mels, dtype=torch.float32).to(dev).contiguous()
+        if mel.dim() != 3 or mel.shape[0] != B or mel.shape[2] != self.n_channels:
+            raise ValueError(f"expected mels of shape [{B}, T, {self.n_channels}], got {tuple(mel.shape)}")
+        T = int(mel.shape[1])
+        tl = np.asarray(torch.as_tensor(txt_lens).cpu(), dtype=np.int64).reshape(-1)
+        ml = np.asarray(torch.as_tensor(mel_lens).cpu(), dtype=np.int64).reshape(-1)
+        sp = torch.as_tensor(speaker, dtype=torch.int64).reshape(-1).to(dev)
+        if sp.numel() == 1:
+            sp = sp.expand(B)
+        keys = emb[ids].contiguous()          # plumbing: the embedding rows are gathered with torch
+        spk = spk_table[sp].contiguous()
+        if attn_prior is None:
+            if tl.shape != (B,) or ml.shape != (B,) or (tl < 1).any() or (tl > L).any() or (ml < 1).any() or (ml > T).any():
+                raise ValueError("txt_lens must lie in [1, L] and mel_lens in [1, T], one per row")
+            attn_prior = al.batch_prior(tl, ml, T, L)
+        prior = torch.as_tensor(attn_prior, dtype=torch.float32).to(dev).contiguous()
+        soft = torch.empty((B, T, L), dtype=torch.float32, device=dev)
+        hard, logprob = torch.empty_like(soft), torch.empty_like(soft)
+        dur = torch.empty((B, L), dtype=torch.float32, device=dev)
+        enc.encoder.align(mel, keys, spk, tl, ml, prior, out_dur=dur, out_hard=hard, out_attn=soft, out_logprob=logprob, want=())
+        return soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1)
+
     def forward(self, *a, **k):
-        raise NotImplementedError("training forward is out of scope; use .inference()")
+        raise NotImplementedError("training forward is out of scope; use .inference(), or .align() for the aligner's attn_out")
 
     __call__ = forward
+
+
+class AlignmentEncoder:
+    """Mirror of the reference's ``AlignmentEncoder`` (U/layers.py:275-369) on the alignment library: same constructor arguments,
+    ``load_state_dict`` with the submodule's key names, ``forward(queries [B, C, T1], keys [B, C2, T2], mask, attn_prior, speaker_embed)``
+    -> ``(attn, attn_logprob)``, both [B, 1, T1, T2] torch tensors on the GPU.  ``mask`` is the reference's [B, T2, 1] boolean mask (True =
+    padded); it must be a prefix mask (get_mask_from_lengths), which is what the library takes as lengths."""
+
+    def __init__(self, n_mel_channels: int, n_att_channels: int, n_text_channels: int, temperature: float, device=None):
+        from . import aligner as al
+        self.n_mel_channels, self.n_att_channels, self.n_text_channels = int(n_mel_channels), int(n_att_channels), int(n_text_channels)
+        self.temperature = temperature
+        self.encoder = al.Aligner(n_mel_channels, n_att_channels, n_text_channels, temperature, _device_index(device))
+        self.training = False
+
+    def load_state_dict(self, state_dict: Mapping[str, object], strict: bool = True):
+        dims = packer.aligner_dims(state_dict, "")
+        if dims != (self.n_mel_channels, self.n_att_channels, self.n_text_channels):
+            raise ValueError(f"state dict is of an AlignmentEncoder{dims}, this one is "
+                             f"{(self.n_mel_channels, self.n_att_channels, self.n_text_channels)}")
+        self.encoder.load_weights(packer.pack_aligner(state_dict, ""))
+        return self
+
+    def eval(self):
+        return self
+
+    def forward(self, queries, keys, mask=None, attn_prior=None, speaker_embed=None):
+        torch = _torch()
+        dev = torch.device("cuda", self.encoder.device)
+        q = torch.as_tensor(queries, dtype=torch.float32).to(dev).transpose(1, 2).contiguous()   # channels-last, the library's layout
+        k = torch.as_tensor(keys, dtype=torch.float32).to(dev).transpose(1, 2).contiguous()
+        B, T, L = q.shape[0], q.shape[1], k.shape[1]
+        lens = None
+        if mask is not None:
+            m = torch.as_tensor(mask).reshape(B, L).bool().cpu()
+            lens = (~m).sum(1).to(torch.int64)
+            if not torch.equal(m, torch.arange(L)[None, :] >= lens[:, None]):
+                raise ValueError("mask must be a prefix mask (True from each row's length on)")
+            lens = lens.numpy()
+        prior = None if attn_prior is None else torch.as_tensor(attn_prior, dtype=torch.float32).to(dev).contiguous()
+        spk = None if speaker_embed is None else torch.as_tensor(speaker_embed, dtype=torch.float32).to(dev).contiguous()
+        attn = torch.empty((B, T, L), dtype=torch.float32, device=dev)
+        logprob = torch.empty_like(attn)
+        self.encoder.forward(q, k, spk, lens, prior, out_attn=attn, out_logprob=logprob, want=())
+        return attn.unsqueeze(1), logprob.unsqueeze(1)
+
+    __call__ = forward
+
+
+_MAS_HANDLES = {}
+
+
+def b_mas(attn, in_lens, out_lens, width: int = 1, device=None):
+    """The reference's ``b_mas`` (U/function.py:128-137) on the GPU: attn [B, 1, T, L] probabilities (numpy, as the reference takes it, or a
+    torch tensor) -> attn_hard of the same kind and shape.  ``width`` must be 1, as there."""
+    if width != 1:
+        raise NotImplementedError("b_mas: width != 1 is out of scope (the reference asserts width == 1)")
+    from . import aligner as al
+    torch = _torch()
+    is_np = isinstance(attn, np.ndarray)
+    if device is None and not is_np and attn.is_cuda:
+        device = attn.device
+    idx = _device_index(device)
+    if idx not in _MAS_HANDLES:
+        _MAS_HANDLES[idx] = al.Aligner(4, 1, 4, 1.0, idx)   # the search needs no weights: any dims do
+    a = torch.as_tensor(attn, dtype=torch.float32)
+    if a.dim() != 4 or a.shape[1] != 1:
+        raise ValueError(f"expected attn of shape [B, 1, T, L], got {tuple(a.shape)}")
+    a3 = a[:, 0].contiguous()
+    a3 = a3.numpy() if not a3.is_cuda else a3
+    to_np = lambda v: np.asarray(torch.as_tensor(v).cpu(), dtype=np.int64).reshape(-1)  # noqa: E731
+    if is_np or not attn.is_cuda:
+        hard = _MAS_HANDLES[idx].mas(a3, to_np(in_lens), to_np(out_lens), want=("attn_hard",))["attn_hard"][:, None]
+        return hard.astype(attn.dtype) if is_np else torch.from_numpy(hard)
+    hard = torch.empty_like(a3)
+    _MAS_HANDLES[idx].mas(a3, to_np(in_lens), to_np(out_lens), out_hard=hard, want=())
+    return hard.unsqueeze(1)
 
 
 def _vocoder_only_dims(hifigan_config: dict, n_mel: int = 80, vocoder: str = "hifigan") -> EngineDims:

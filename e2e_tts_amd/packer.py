@@ -392,3 +392,38 @@ def build_blob(tensors: Mapping[str, np.ndarray]) -> np.ndarray:
 
 def pack(dims: EngineDims, acoustic: Optional[Mapping[str, object]], vocoder: Optional[Mapping[str, object]]) -> np.ndarray:
     return build_blob(pack_tensors(dims, acoustic, vocoder))
+
+
+ALIGNER_PREFIX = "variance_adaptor.aligner."
+
+
+def aligner_dims(state_dict: Mapping[str, object], prefix: str = ALIGNER_PREFIX):
+    """(n_mel_channels, n_att_channels, n_text_channels) of the AlignmentEncoder whose tensors `state_dict` holds under `prefix`."""
+    for key in ("key_proj.2.conv.weight", "query_proj.0.conv.weight"):
+        if prefix + key not in state_dict:
+            raise KeyError(f"checkpoint has no tensor {prefix + key!r}")
+    k2 = tuple(state_dict[prefix + "key_proj.2.conv.weight"].shape)
+    q0 = tuple(state_dict[prefix + "query_proj.0.conv.weight"].shape)
+    return int(q0[1]), int(k2[0]), int(k2[1]) // 2
+
+
+def pack_aligner_tensors(state_dict: Mapping[str, object], prefix: str = ALIGNER_PREFIX) -> "OrderedDict[str, np.ndarray]":
+    """The reference's AlignmentEncoder (U/layers.py:288-330) -> tensors `aln.*` of the alignment library (csrc/align/aligner.hip:
+    e2ealign_load_weights): the five ConvNorm layers as tap-major rows + bias, the two bias-free LinearNorm speaker projections as they are.
+    `prefix` is "variance_adaptor.aligner." for a model checkpoint and "" for the submodule's own state dict."""
+    A = {k[len(prefix):]: _np(v) for k, v in state_dict.items() if k.startswith(prefix)}
+    M, natt, H = aligner_dims(A, "")
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for name, key, shape in (("aln.key.0", "key_proj.0", (2 * H, H, 3)), ("aln.key.2", "key_proj.2", (natt, 2 * H, 1)),
+                             ("aln.query.0", "query_proj.0", (2 * M, M, 3)), ("aln.query.2", "query_proj.2", (M, 2 * M, 1)),
+                             ("aln.query.4", "query_proj.4", (natt, M, 1))):
+        out[name + ".w"] = conv_rows(_need(A, key + ".conv.weight", shape))
+        out[name + ".b"] = _need(A, key + ".conv.bias", (shape[0],))
+    out["aln.key_spk.w"] = _need(A, "key_spk_proj.linear.weight", (H, H))
+    out["aln.query_spk.w"] = _need(A, "query_spk_proj.linear.weight", (M, H))
+    return OrderedDict((k, np.ascontiguousarray(v, dtype=np.float32)) for k, v in out.items())
+
+
+def pack_aligner(state_dict: Mapping[str, object], prefix: str = ALIGNER_PREFIX) -> np.ndarray:
+    """The aligner's weights as a blob of their own, in build_blob's container; what pack() produces is unchanged."""
+    return build_blob(pack_aligner_tensors(state_dict, prefix))

@@ -132,7 +132,7 @@ def acoustic_manifest(config: dict, n_speakers: int, n_symbols: int = N_SYMBOLS)
     va = "variance_adaptor"
     add(f"{va}.pitch_bins", (ve["n_bins"] - 1,), "pitch_bins")
     add(f"{va}.energy_bins", (ve["n_bins"] - 1,), "energy_bins")
-    # aligner: training only, unused at inference, but part of the state dict (U/layers.py:275-369)
+    # aligner: unused by synthesis (packer.pack leaves it out); forced alignment packs it into a blob of its own (packer.pack_aligner, U/layers.py:275-369)
     add(f"{va}.aligner.key_proj.0.conv.weight", (2 * H, H, 3), "w")
     add(f"{va}.aligner.key_proj.0.conv.bias", (2 * H,), "b")
     add(f"{va}.aligner.key_proj.2.conv.weight", (n_mel, 2 * H, 1), "w")
@@ -322,6 +322,31 @@ def make_acoustic_state(config: dict, stats: dict, n_speakers: int, seed: int = 
     mode='varied': data-dependent durations of roughly 1..9 frames (correctness fixtures)."""
     return _fill(acoustic_manifest(config, n_speakers, n_symbols), seed, stats=stats, mode=mode,
                  frames_per_phoneme=frames_per_phoneme)
+
+
+def make_aligner_state(hidden: int, n_mel: int, n_speakers: int = 4, seed: int = 77, n_symbols: int = N_SYMBOLS,
+                       weight_scale: float = 1.0) -> "OrderedDict[str, np.ndarray]":
+    """The tensors forced alignment reads, alone and at any widths: ``variance_adaptor.aligner.*`` (the AlignmentEncoder of
+    U/layers.py:275-369, n_att_channels = n_mel), ``encoder.src_word_emb.weight`` and ``speaker_emb.weight``, under their checkpoint names.
+    ``weight_scale`` multiplies the aligner's weight matrices (not its biases): random weights at the shipped temperature give nearly flat
+    attention, and a fixture that wants a decided alignment without a prior sharpens it this way (tools/make_aligner_goldens.py)."""
+    va = "variance_adaptor.aligner."
+    m: "OrderedDict[str, Tuple[Shape, str]]" = OrderedDict()
+    m["encoder.src_word_emb.weight"] = ((n_symbols + 1, hidden), "emb_pad0")
+    m["speaker_emb.weight"] = ((n_speakers, hidden), "emb")
+    for name, shape in (("key_proj.0.conv", (2 * hidden, hidden, 3)), ("key_proj.2.conv", (n_mel, 2 * hidden, 1)),
+                        ("query_proj.0.conv", (2 * n_mel, n_mel, 3)), ("query_proj.2.conv", (n_mel, 2 * n_mel, 1)),
+                        ("query_proj.4.conv", (n_mel, n_mel, 1))):
+        m[f"{va}{name}.weight"] = (shape, "w")
+        m[f"{va}{name}.bias"] = ((shape[0],), "b")
+    m[f"{va}key_spk_proj.linear.weight"] = ((hidden, hidden), "w")
+    m[f"{va}query_spk_proj.linear.weight"] = ((n_mel, hidden), "w")
+    sd = _fill(m, seed, stats=None, mode="fixed", frames_per_phoneme=0)
+    if weight_scale != 1.0:
+        for k in sd:
+            if k.startswith(va) and k.endswith("weight"):
+                sd[k] = (sd[k] * np.float32(weight_scale)).astype(np.float32)
+    return sd
 
 
 def make_vocoder_state(config: dict, seed: int = 4321, vocoder: str = "hifigan") -> "OrderedDict[str, np.ndarray]":
