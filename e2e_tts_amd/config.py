@@ -24,7 +24,7 @@ _DEFAULT = {
     "audio": {
         "signal": {"sampling_rate": 22050, "max_wav_value": 32768.0},
         "stft": {"filter_length": 1024, "hop_length": 256, "win_length": 1024},
-        "mel": {"channels": 80},
+        "mel": {"channels": 80, "mel_fmin": 0.0, "mel_fmax": 8000.0},
     },
     "models": {
         "fastspeech2": {

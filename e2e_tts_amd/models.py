@@ -10,6 +10,10 @@ engine's HBM image.  Training-side methods (``forward`` with targets, ``parse_ba
 
 Forced alignment -- the reference's ``AlignmentEncoder`` and ``b_mas``, i.e. the ``attn_out`` of its training forward -- is served by the
 companion library (include/e2etts_align.h): ``AlignmentEncoder``, ``b_mas`` and ``UnsupervisedFastSpeech2.align`` below.
+
+The analysis side -- the reference's ``TorchSTFT.mel_spectrogram`` / ``generate_melspecs`` (e2e_tts/src/tools/stft.py), a recording to
+log-mel frames and frame energies -- is served by the mel library (include/e2etts_mel.h): ``TorchSTFT``, ``generate_melspecs`` and
+``UnsupervisedFastSpeech2.align_audio`` (recording -> mel -> durations, all on the device).
 """
 from __future__ import annotations
 
@@ -209,6 +213,76 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         dur = torch.empty((B, L), dtype=torch.float32, device=dev)
         enc.encoder.align(mel, keys, spk, tl, ml, prior, out_dur=dur, out_hard=hard, out_attn=soft, out_logprob=logprob, want=())
         return soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1)
+
+    def set_audio_config(self, audio: Mapping[str, object]):
+        """The ``audio`` section of the reference's preprocessing configuration (``stft.filter_length / hop_length / win_length``,
+        ``mel.channels / mel_fmin / mel_fmax``, ``signal.sampling_rate``): what ``align_audio`` builds its transform from."""
+        if int(audio["mel"]["channels"]) != self.n_channels:
+            raise ValueError(f"audio.mel.channels = {audio['mel']['channels']}, this model has {self.n_channels} mel channels")
+        au = self._full_config["audio"]
+        for sec in ("stft", "mel", "signal"):
+            au[sec].update(audio[sec])
+        self._audio_given, self._stft = True, None
+        return self
+
+    def _default_stft(self):
+        au = self._full_config["audio"]
+        if not getattr(self, "_audio_given", False) and (au["signal"]["sampling_rate"], au["stft"]["hop_length"]) != (22050, 256):
+            raise ValueError(f"this model was built with sampling_rate {au['signal']['sampling_rate']} and hop_length {au['stft']['hop_length']}, for which no "
+                             "filter_length / mel_fmin / mel_fmax is known: call set_audio_config(audio) or pass stft=")
+        stft = getattr(self, "_stft", None)
+        if stft is None or stft.frontend.device != self._device:
+            stft = self._stft = TorchSTFT(au["stft"]["filter_length"], au["stft"]["hop_length"], au["stft"]["win_length"], self.n_channels,
+                                          au["signal"]["sampling_rate"], au["mel"]["mel_fmin"], au["mel"]["mel_fmax"], device=self._device)
+        return stft
+
+    def align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior=None, return_energy=False, stft=None):
+        """Forced alignment of RECORDINGS: wavs [B, n] (float32 in [-1, 1] or int16 PCM; numpy or torch, host or GPU), wav_lens [B] samples
+        -> ``align``'s tuple (attn_soft, attn_hard, attn_hard_dur, attn_logprob), plus the frame energies [B, T] when ``return_energy``.
+        The mel is computed on the device by the mel library, every row over its own length (mel_lens = wav_lens // hop, as
+        e2emel_forward returns them), and the aligner reads it where it lies: the mel never visits the host.  ``stft`` is a ``TorchSTFT``
+        to use (e.g. one holding librosa's own filterbank); by default one is built from this model's audio configuration with
+        ``mel.mel_filterbank`` (see its docstring: unpinned against librosa) -- the shipped 22.05 kHz defaults, or what
+        ``set_audio_config`` was given; a model built with another sampling rate or hop and no audio configuration raises instead of
+        guessing a transform."""
+        from . import aligner as al
+        torch = _torch()
+        if stft is None:
+            stft = self._default_stft()
+        enc, emb, spk_table = self._ensure_aligner()
+        dev = torch.device("cuda", self._device)
+        if stft.n_mel_channels != self.n_channels or stft.frontend.device != self._device:
+            raise ValueError(f"stft has {stft.n_mel_channels} mel channels on GPU {stft.frontend.device}; this model has {self.n_channels} on GPU {self._device}")
+        ids = torch.as_tensor(texts, dtype=torch.int64).to(dev)
+        B, L = ids.shape
+        tl = np.asarray(torch.as_tensor(txt_lens).cpu(), dtype=np.int64).reshape(-1)
+        sp = torch.as_tensor(speaker, dtype=torch.int64).reshape(-1).to(dev)
+        if sp.numel() == 1:
+            sp = sp.expand(B)
+        keys = emb[ids].contiguous()
+        spk = spk_table[sp].contiguous()
+        fe = stft.frontend
+        x = stft._audio(wavs)
+        wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
+        energy = None
+        if return_energy:
+            energy = torch.zeros((B, max(1, int(wl.max()) // fe.hop)), dtype=torch.float32, device=dev)
+        r = fe.forward(x, wl, out_energy=energy, want=())          # raises ValueError on a bad length before anything is enqueued
+        T, ml = r["T"], r["mel_lens"]
+        if attn_prior is None:
+            if tl.shape != (B,) or (tl < 1).any() or (tl > L).any():
+                raise ValueError("txt_lens must lie in [1, L], one per row")
+            attn_prior = al.batch_prior(tl, ml, T, L)
+        prior = torch.as_tensor(attn_prior, dtype=torch.float32).to(dev).contiguous()
+        soft = torch.empty((B, T, L), dtype=torch.float32, device=dev)
+        hard, logprob = torch.empty_like(soft), torch.empty_like(soft)
+        dur = torch.empty((B, L), dtype=torch.float32, device=dev)
+        mel_dev, _ = fe.resident()
+        a = enc.encoder
+        a._check(a.lib.e2ealign_order_after(a._h, fe.stream()), "e2ealign_order_after")   # the aligner's stream after the mel's
+        a.align(mel_dev, keys, spk, tl, ml, prior, out_dur=dur, out_hard=hard, out_attn=soft, out_logprob=logprob, want=())
+        out = (soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1))
+        return out + (energy,) if return_energy else out
 
     def forward(self, *a, **k):
         raise NotImplementedError("training forward is out of scope; use .inference(), or .align() for the aligner's attn_out")
@@ -498,3 +572,91 @@ class Denoiser:
             yield from it
 
         yield from eng.vocoder_stream(chunks(), int(first.shape[0]), want_pcm=want_pcm, denoise_strength=float(strength))
+
+
+class TorchSTFT:
+    """Mirror of the reference's ``TorchSTFT`` (e2e_tts/src/tools/stft.py:11-89) on the mel library: same constructor arguments,
+    ``mel_basis`` [n_mel, bins] and ``window`` [win_length] attributes (torch tensors on the GPU), ``mel_spectrogram(input_data [B, n],
+    center=False, return_energy=False)`` -> log-mel [B, n_mel, T] (and energy [B, T]), torch tensors on the GPU.
+
+    ``mel_basis=`` replaces the filterbank: by default it is ``mel.mel_filterbank``, a restatement of librosa 0.9.2's formula that has not
+    been compared against librosa itself (librosa is not available where this project is built); pass librosa's matrix to be sure.
+    Differences from the reference: ``input_data`` may be int16 PCM (divided by 32768 on the device); ``n_valid=[...]`` selects the ragged
+    form, every row padded, reflected and framed over its own samples (the reference, given one padded batch, reflects at the batch's end);
+    only center=False, the reference's default and the only form its callers use, is served."""
+
+    def __init__(self, filter_length: int = 1024, hop_length: int = 256, win_length: int = 1024, n_mel_channels: int = 80, sampling_rate: int = 22050,
+                 mel_fmin: float = 0.0, mel_fmax: Optional[float] = 8000.0, device=None, mel_basis=None, clip_val: float = 1e-5):
+        from . import mel as mp
+        torch = _torch()
+        self.sampling_rate, self.n_mel_channels = sampling_rate, int(n_mel_channels)
+        self.filter_length, self.hop_length, self.win_length = int(filter_length), int(hop_length), int(win_length)
+        self.fmin, self.fmax = mel_fmin, mel_fmax
+        pad = int((self.filter_length - self.hop_length) / 2)
+        self.stft_pad = (pad, pad)
+        self.frontend = mp.MelFrontend(self.filter_length, self.hop_length, self.n_mel_channels, _device_index(device))
+        if mel_basis is None:
+            mel_basis = mp.mel_filterbank(sampling_rate, self.filter_length, self.n_mel_channels, mel_fmin, mel_fmax)
+        basis = np.ascontiguousarray(torch.as_tensor(mel_basis).detach().cpu().numpy(), dtype=np.float32)
+        self.frontend.load(mp.dft_basis(self.filter_length, self.win_length), basis, clip_val)
+        self.device = torch.device("cuda", self.frontend.device)
+        self.mel_basis = torch.from_numpy(basis).to(self.device)
+        self.window = torch.hann_window(self.win_length).to(self.device)
+
+    def _audio(self, x):
+        """[B, n] float32 or int16, numpy or torch, as the library takes it."""
+        torch = _torch()
+        if not isinstance(x, np.ndarray) and not hasattr(x, "data_ptr"):
+            x = np.asarray(x)
+        if str(x.dtype).replace("torch.", "") not in ("float32", "int16"):
+            x = x.astype(np.float32) if isinstance(x, np.ndarray) else x.to(torch.float32)
+        if x.ndim != 2:
+            raise ValueError(f"expected audio of shape [B, n], got {tuple(x.shape)}")
+        return x
+
+    def mel_spectrogram(self, input_data, center: bool = False, return_energy: bool = False, n_valid=None):
+        if center:
+            raise NotImplementedError("center=True is out of scope: the reference's mel_spectrogram defaults to center=False (e2e_tts/src/tools/stft.py:46) "
+                                      "after its own reflect padding (:60-64), and so do all its callers")
+        torch = _torch()
+        x = self._audio(input_data)
+        if str(x.dtype).replace("torch.", "") == "float32":   # the reference's two asserts (stft.py:56-57)
+            t = torch.as_tensor(x)
+            assert torch.min(t) >= -1
+            assert torch.max(t) <= 1
+        B, n = int(x.shape[0]), int(x.shape[1])
+        T = n // self.hop_length if n_valid is None else int(np.asarray(torch.as_tensor(n_valid).cpu()).max()) // self.hop_length
+        mel = torch.zeros((B, max(T, 1), self.n_mel_channels), dtype=torch.float32, device=self.device)
+        energy = torch.zeros((B, max(T, 1)), dtype=torch.float32, device=self.device) if return_energy else None
+        self.frontend.forward(x, n_valid, out_mel=mel, out_energy=energy, want=())
+        mel = mel.transpose(1, 2).contiguous()
+        return (mel, energy) if return_energy else mel
+
+
+_STFT_CACHE = {}
+
+
+def generate_melspecs(y, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=256, win_size=1024, fmin=0.0, fmax=8000.0, center=False, device=None):
+    """The function form (e2e_tts/src/tools/stft.py:107-135): y [B, n] -> log-mel [B, num_mels, T] on the GPU.  Like the reference it only
+    warns about samples outside [-1, 1]; the transform objects are cached per geometry and device."""
+    import warnings
+    torch = _torch()
+    if device is None and hasattr(y, "is_cuda") and y.is_cuda:
+        device = y.device
+    key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, _device_index(device))
+    if key not in _STFT_CACHE:
+        _STFT_CACHE[key] = TorchSTFT(n_fft, hop_size, win_size, num_mels, sampling_rate, fmin, fmax, device=device)
+    stft = _STFT_CACHE[key]
+    if center:
+        return stft.mel_spectrogram(y, center=True)   # raises
+    x = stft._audio(y)
+    t = torch.as_tensor(x)
+    if t.dtype == torch.float32:
+        if torch.min(t) < -1.:
+            warnings.warn(f"min value is {torch.min(t).item()}")
+        if torch.max(t) > 1.:
+            warnings.warn(f"max value is {torch.max(t).item()}")
+    B, n = int(x.shape[0]), int(x.shape[1])
+    mel = torch.zeros((B, max(n // hop_size, 1), num_mels), dtype=torch.float32, device=stft.device)
+    stft.frontend.forward(x, None, out_mel=mel, want=())
+    return mel.transpose(1, 2).contiguous()
