@@ -11,25 +11,42 @@ from typing import Optional
 
 import numpy as np
 
+from . import _companion
+from ._companion import E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM  # noqa: F401  (the codes of include/e2etts_align.h)
 from ._lib import _addr, _expect, _is_cuda
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align.so")
 # the TEST build of the same source (-DE2EALIGN_TEST_HOOKS: one more export, e2ealign_debug_poison_workspace), loaded instead of the product
-# library only when E2ETTS_TEST_HOOKS=1 is in the environment (tests/conftest.py sets it), as _lib.py does for the main library
+# library only when E2ETTS_TEST_HOOKS=1 is in the environment (_companion.load)
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align_test.so")
 ABI_VERSION = 1   # E2EALIGN_ABI_VERSION of the include/e2etts_align.h this binding mirrors
-E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM = 0, -1, -2, -3, -4
 LOG_MAP = 1       # E2EALIGN_LOG_MAP
 MAX_ATT, MAX_L, MAX_B = 128, 2048, 4096
 
-# every entry point include/e2etts_align.h declares, and all the library exports (tests/test_aligner_host.py compares the three)
-EXPORTED_SYMBOLS = [
-    "e2ealign_version", "e2ealign_abi_version", "e2ealign_last_error", "e2ealign_create", "e2ealign_destroy", "e2ealign_load_weights",
-    "e2ealign_stream", "e2ealign_order_after", "e2ealign_sync", "e2ealign_device_bytes", "e2ealign_forward", "e2ealign_mas", "e2ealign_align",
-    "e2ealign_profile_enable", "e2ealign_profile_read",
-]
-TEST_HOOK_SYMBOLS = ["e2ealign_debug_poison_workspace"]
+_P, _I, _F, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+# every entry point include/e2etts_align.h declares, and all the library exports (tests/test_aligner_host.py compares the three):
+# name -> (restype, argtypes)
+SIGNATURES = {
+    "e2ealign_version": (C.c_char_p, []),
+    "e2ealign_abi_version": (_I, []),
+    "e2ealign_last_error": (C.c_char_p, [_P]),
+    "e2ealign_create": (_I, [_I, _I, _I, _I, _F, C.POINTER(_P)]),
+    "e2ealign_destroy": (None, [_P]),
+    "e2ealign_load_weights": (_I, [_P, _P, _SZ]),
+    "e2ealign_stream": (_P, [_P]),
+    "e2ealign_order_after": (_I, [_P, _P]),
+    "e2ealign_sync": (_I, [_P]),
+    "e2ealign_device_bytes": (_SZ, [_P]),
+    "e2ealign_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "e2ealign_mas": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "e2ealign_align": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "e2ealign_profile_enable": (_I, [_P, _I]),
+    "e2ealign_profile_read": (_I, [_P, C.POINTER(C.c_double)]),
+}
+HOOK_SIGNATURES = {"e2ealign_debug_poison_workspace": (_I, [_P])}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+TEST_HOOK_SYMBOLS = list(HOOK_SIGNATURES)
 
 _lib = None
 
@@ -37,53 +54,9 @@ _lib = None
 def load_library() -> C.CDLL:
     """dlopen the in-tree alignment library (built by __graft_entry__.build())."""
     global _lib
-    if _lib is not None:
-        return _lib
-    hooks = os.environ.get("E2ETTS_TEST_HOOKS", "") not in ("", "0")
-    path = TEST_LIB_PATH if hooks else LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950).  e2e_tts_amd has no CPU fallback.")
-    import torch  # noqa: F401  (ONE HIP runtime per process: see _lib.load_library)
-    lib = C.CDLL(path)
-    P, I, F, SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    lib.e2ealign_version.restype = C.c_char_p
-    lib.e2ealign_version.argtypes = []
-    lib.e2ealign_abi_version.restype = I
-    lib.e2ealign_abi_version.argtypes = []
-    if lib.e2ealign_abi_version() != ABI_VERSION:
-        raise ImportError(f"{path}: ABI version {lib.e2ealign_abi_version()}, this binding mirrors version {ABI_VERSION}: rebuild the library")
-    lib.e2ealign_last_error.restype = C.c_char_p
-    lib.e2ealign_last_error.argtypes = [P]
-    lib.e2ealign_create.restype = I
-    lib.e2ealign_create.argtypes = [I, I, I, I, F, C.POINTER(P)]
-    lib.e2ealign_destroy.restype = None
-    lib.e2ealign_destroy.argtypes = [P]
-    lib.e2ealign_load_weights.restype = I
-    lib.e2ealign_load_weights.argtypes = [P, P, SZ]
-    lib.e2ealign_stream.restype = P
-    lib.e2ealign_stream.argtypes = [P]
-    lib.e2ealign_order_after.restype = I
-    lib.e2ealign_order_after.argtypes = [P, P]
-    lib.e2ealign_sync.restype = I
-    lib.e2ealign_sync.argtypes = [P]
-    lib.e2ealign_device_bytes.restype = SZ
-    lib.e2ealign_device_bytes.argtypes = [P]
-    lib.e2ealign_forward.restype = I
-    lib.e2ealign_forward.argtypes = [P, P, P, P, P, P, I, I, I, P, P]
-    lib.e2ealign_mas.restype = I
-    lib.e2ealign_mas.argtypes = [P, P, I, P, P, I, I, I, P, P]
-    lib.e2ealign_align.restype = I
-    lib.e2ealign_align.argtypes = [P, P, P, P, P, P, P, I, I, I, P, P, P, P]
-    lib.e2ealign_profile_enable.restype = I
-    lib.e2ealign_profile_enable.argtypes = [P, I]
-    lib.e2ealign_profile_read.restype = I
-    lib.e2ealign_profile_read.argtypes = [P, C.POINTER(C.c_double)]
-    if hooks:
-        lib.e2ealign_debug_poison_workspace.restype = I
-        lib.e2ealign_debug_poison_workspace.argtypes = [P]
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _companion.load("e2ealign", LIB_PATH, TEST_LIB_PATH, ABI_VERSION, SIGNATURES, HOOK_SIGNATURES)
+    return _lib
 
 
 def beta_binomial_prior_distribution(phoneme_count: int, mel_count: int, scaling_factor: float = 1.0) -> np.ndarray:
@@ -112,9 +85,10 @@ def batch_prior(txt_lens, mel_lens, max_mel_len: int, max_txt_len: int, scaling_
                           max_mel_len, max_txt_len)
 
 
-class Aligner:
+class Aligner(_companion.CompanionHandle):
     """One e2ealign_handle.  Inputs are numpy arrays or torch tensors (host or GPU), outputs are written into the arrays / tensors given
     (``out_*``) or returned as fresh numpy arrays when asked for by ``want``."""
+    _prefix, _what, _phases = "e2ealign", "alignment", ("proj", "attn", "mas")
 
     def __init__(self, n_mel: int, n_att: int, n_text: int, temperature: float, device: int = 0):
         self.lib = load_library()
@@ -124,35 +98,6 @@ class Aligner:
         if rc != E_OK:
             raise ValueError(self.lib.e2ealign_last_error(None).decode())
         self._h = h
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.e2ealign_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int, what: str):
-        if rc == E_OK:
-            return
-        msg = f"{what}: {self.lib.e2ealign_last_error(self._h).decode()}"
-        if rc == E_INVAL:
-            raise ValueError(msg)
-        if rc == E_NOMEM:
-            raise MemoryError(msg)
-        raise RuntimeError(msg)
-
-    def _order(self, *xs):
-        """Order the handle's stream after torch's current stream when any argument lives on the GPU."""
-        if any(_is_cuda(x) for x in xs):
-            import torch
-            with torch.cuda.device(self.device):
-                s = torch.cuda.current_stream().cuda_stream
-            self._check(self.lib.e2ealign_order_after(self._h, s), "e2ealign_order_after")
 
     def load_weights(self, blob) -> None:
         blob = np.ascontiguousarray(blob, dtype=np.uint8)
@@ -233,24 +178,3 @@ class Aligner:
         self._check(self.lib.e2ealign_align(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(mel_lens), _addr(prior),
                                             B, T, L, _addr(out_dur), _addr(out_hard), _addr(out_attn), _addr(out_logprob)), "e2ealign_align")
         return r
-
-    def profile_enable(self, on: bool = True):
-        self._check(self.lib.e2ealign_profile_enable(self._h, 1 if on else 0), "e2ealign_profile_enable")
-
-    def profile_read(self):
-        """Milliseconds of the last call's phases: {"proj", "attn", "mas"}."""
-        ms = (C.c_double * 3)()
-        self._check(self.lib.e2ealign_profile_read(self._h, ms), "e2ealign_profile_read")
-        return {"proj": ms[0], "attn": ms[1], "mas": ms[2]}
-
-    def poison_workspace(self):
-        """Test build only (E2ETTS_TEST_HOOKS=1)."""
-        if not hasattr(self.lib, "e2ealign_debug_poison_workspace"):
-            raise RuntimeError("poison_workspace needs the test build of the alignment library (E2ETTS_TEST_HOOKS=1)")
-        self._check(self.lib.e2ealign_debug_poison_workspace(self._h), "e2ealign_debug_poison_workspace")
-
-    def device_bytes(self) -> int:
-        return int(self.lib.e2ealign_device_bytes(self._h))
-
-    def sync(self):
-        self._check(self.lib.e2ealign_sync(self._h), "e2ealign_sync")

@@ -19,6 +19,10 @@
 #include <vector>
 
 #include "../../../include/e2etts_align.h"
+#ifdef E2EALIGN_TEST_HOOKS
+#define E2E_COMPANION_TEST_HOOKS
+#endif
+#include "../companion/handle.h"
 #include "../host_logic.h"
 #include "../kernels.h"
 
@@ -27,6 +31,10 @@
 #endif
 
 using namespace e2etts;
+using namespace e2etts::companion;
+
+static_assert(E2EALIGN_OK == E_OK && E2EALIGN_EINVAL == E_INVAL && E2EALIGN_EHIP == E_HIP && E2EALIGN_ESTATE == E_STATE && E2EALIGN_ENOMEM == E_NOMEM,
+              "include/e2etts_align.h and csrc/companion/handle.h disagree on the error codes");
 
 namespace {
 
@@ -313,120 +321,26 @@ __global__ __launch_bounds__(MAS_THREADS) void aln_mas_kernel(const float* __res
   for (int j = tid; j < L; j += MAS_THREADS) dur[(size_t)b * L + j] = (float)cnt[j];
 }
 
-#ifdef E2EALIGN_TEST_HOOKS
-__global__ void aln_poison_kernel(uint32_t* p, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0x7fc00000u | (uint32_t)(i & 0xffff);
-}
-#endif
-
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 thread_local std::string g_create_error;
 
 }  // namespace
 
-struct e2ealign_handle {
-  int device = 0;
+struct e2ealign_handle : Handle {
   int n_mel = 0, n_att = 0, n_text = 0;
   float temperature = 0.f;
-  std::mutex mu;
-  std::string err;
-  bool open = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[6] = {};
-  hipEvent_t order_ev = nullptr;
-  bool profile = false;
-  double last_ms[3] = {0, 0, 0};
-  size_t dev_bytes = 0;
   // weights: one HBM image, pointers into it
-  Buf blob;
+  Buf blob{this, Buf::WEIGHTS};
   bool loaded = false;
   const float *k0w = nullptr, *k0b = nullptr, *k2w = nullptr, *k2b = nullptr, *q0w = nullptr, *q0b = nullptr, *q2w = nullptr, *q2b = nullptr,
               *q4w = nullptr, *q4b = nullptr, *kspkw = nullptr, *qspkw = nullptr;
   // workspaces
-  Buf kx, ky, kenc, qx, qy, spk, kspk, qspk, prior, attn, logp, hard, dur, bits, map, lens_txt, lens_in, lens_out;
+  Buf kx{this}, ky{this}, kenc{this}, qx{this}, qy{this}, spk{this}, kspk{this}, qspk{this}, prior{this}, attn{this}, logp{this}, hard{this}, dur{this},
+      bits{this}, map{this}, lens_txt{this}, lens_in{this}, lens_out{this};
   std::vector<int32_t> host_txt, host_in, host_out;   // int32 images of the length arrays: they outlive the asynchronous copies of a call
-  bool unfinished = false;   // a call returned on an error before its stream was drained
   int rB = 0, rT = 0, rL = 0;   // geometry of the resident attn / attn_logprob (0: nothing resident)
-
-  int fail(int code, const std::string& msg) {
-    err = msg;
-    return code;
-  }
 };
 
 namespace {
-
-#define HIPCHK(h, call)                                                                                     \
-  do {                                                                                                      \
-    hipError_t e_ = (call);                                                                                 \
-    if (e_ != hipSuccess) return (h)->fail(E2EALIGN_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define KCHK(h, call)                                            \
-  do {                                                           \
-    const char* m_ = (call);                                     \
-    if (m_) return (h)->fail(E2EALIGN_EHIP, std::string("launch refused: ") + m_); \
-  } while (0)
-#define RET(call)                      \
-  do {                                 \
-    int rc_ = (call);                  \
-    if (rc_ != E2EALIGN_OK) return rc_; \
-  } while (0)
-
-bool is_device_pointer(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice;
-}
-
-int open_device(e2ealign_handle* h) {
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->open) return E2EALIGN_OK;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  for (auto& e : h->ev) HIPCHK(h, hipEventCreate(&e));
-  HIPCHK(h, hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
-  h->open = true;
-  return E2EALIGN_OK;
-}
-
-int reserve(e2ealign_handle* h, Buf& b, size_t bytes) {
-  bytes = (bytes + 255) / 256 * 256;
-  if (b.bytes >= bytes) return E2EALIGN_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (b.p) {
-    HIPCHK(h, hipFree(b.p));
-    h->dev_bytes -= b.bytes;
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  if (hipMalloc(&b.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return h->fail(E2EALIGN_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-  }
-  b.bytes = bytes;
-  h->dev_bytes += bytes;
-  return E2EALIGN_OK;
-}
-
-// [B] int64 lengths (host or device memory) -> host vector; validated against [1, hi] by the caller
-int fetch_lens(e2ealign_handle* h, const int64_t* p, int B, std::vector<int64_t>& out) {
-  out.resize(B);
-  if (is_device_pointer(p)) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpy(out.data(), p, (size_t)B * 8, hipMemcpyDefault));
-  } else {
-    memcpy(out.data(), p, (size_t)B * 8);
-  }
-  return E2EALIGN_OK;
-}
 
 int check_lens(e2ealign_handle* h, const std::vector<int64_t>& v, long long hi, const char* name, const char* hi_name) {
   for (size_t b = 0; b < v.size(); ++b)
@@ -452,14 +366,6 @@ int upload_lens(e2ealign_handle* h, Buf& dst, std::vector<int32_t>& host, const 
   host.assign(v.begin(), v.end());
   RET(reserve(h, dst, host.size() * 4));
   HIPCHK(h, hipMemcpyAsync(dst.p, host.data(), host.size() * 4, hipMemcpyHostToDevice, h->stream));
-  return E2EALIGN_OK;
-}
-
-// after validation, before the first thing a computing call enqueues
-int begin_call(e2ealign_handle* h) {
-  RET(open_device(h));
-  if (h->unfinished) HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->unfinished = true;
   return E2EALIGN_OK;
 }
 
@@ -587,29 +493,10 @@ int run_mas(e2ealign_handle* h, const float* dmap, int is_log, const std::vector
   return E2EALIGN_OK;
 }
 
+// the profiled phases: projections (events 0, 1) and attention (1, 2) of a forward, the search (3, 4)
 int finish(e2ealign_handle* h, bool fwd, bool mas) {
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->unfinished = false;
-  if (h->profile) {
-    float ms = 0.f;
-    h->last_ms[0] = h->last_ms[1] = h->last_ms[2] = 0.0;
-    if (fwd) {
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-      h->last_ms[0] = ms;
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[1], h->ev[2]));
-      h->last_ms[1] = ms;
-    }
-    if (mas) {
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[3], h->ev[4]));
-      h->last_ms[2] = ms;
-    }
-  }
-  return E2EALIGN_OK;
-}
-
-int copy_out(e2ealign_handle* h, void* dst, const void* src, size_t bytes) {
-  if (dst) HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, h->stream));
-  return E2EALIGN_OK;
+  const Phase none{-1, -1}, phases[3] = {fwd ? Phase{0, 1} : none, fwd ? Phase{1, 2} : none, mas ? Phase{3, 4} : none};
+  return companion::finish(h, phases);
 }
 
 struct Want {
@@ -652,20 +539,7 @@ int e2ealign_create(int device_id, int n_mel, int n_att, int n_text, float tempe
   return E2EALIGN_OK;
 }
 
-void e2ealign_destroy(e2ealign_handle* h) {
-  if (!h) return;
-  if (h->open && hipSetDevice(h->device) == hipSuccess) {
-    (void)hipStreamSynchronize(h->stream);
-    for (Buf* b : {&h->blob, &h->kx, &h->ky, &h->kenc, &h->qx, &h->qy, &h->spk, &h->kspk, &h->qspk, &h->prior, &h->attn, &h->logp, &h->hard, &h->dur, &h->bits,
-                   &h->map, &h->lens_txt, &h->lens_in, &h->lens_out})
-      if (b->p) (void)hipFree(b->p);
-    for (auto& e : h->ev)
-      if (e) (void)hipEventDestroy(e);
-    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
-    (void)hipStreamDestroy(h->stream);
-  }
-  delete h;
-}
+void e2ealign_destroy(e2ealign_handle* h) { companion::destroy(h); }
 
 int e2ealign_load_weights(e2ealign_handle* h, const void* blob, size_t nbytes) {
   if (!h) return E2EALIGN_EINVAL;
@@ -719,32 +593,10 @@ int e2ealign_load_weights(e2ealign_handle* h, const void* blob, size_t nbytes) {
   return E2EALIGN_OK;
 }
 
-void* e2ealign_stream(e2ealign_handle* h) {
-  if (!h) return nullptr;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (open_device(h) != E2EALIGN_OK) return nullptr;
-  return (void*)h->stream;
-}
-
-int e2ealign_order_after(e2ealign_handle* h, void* caller_stream) {
-  if (!h) return E2EALIGN_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RET(open_device(h));
-  HIPCHK(h, hipEventRecord(h->order_ev, (hipStream_t)caller_stream));
-  HIPCHK(h, hipStreamWaitEvent(h->stream, h->order_ev, 0));
-  return E2EALIGN_OK;
-}
-
-int e2ealign_sync(e2ealign_handle* h) {
-  if (!h) return E2EALIGN_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->open) return E2EALIGN_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return E2EALIGN_OK;
-}
-
-size_t e2ealign_device_bytes(const e2ealign_handle* h) { return h ? h->dev_bytes : 0; }
+void* e2ealign_stream(e2ealign_handle* h) { return companion::stream(h); }
+int e2ealign_order_after(e2ealign_handle* h, void* caller_stream) { return companion::order_after(h, caller_stream); }
+int e2ealign_sync(e2ealign_handle* h) { return companion::sync(h); }
+size_t e2ealign_device_bytes(const e2ealign_handle* h) { return companion::device_bytes(h); }
 
 int e2ealign_forward(e2ealign_handle* h, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens, const float* prior, int B,
                      int T, int L, float* attn_out, float* attn_logprob_out) {
@@ -754,7 +606,7 @@ int e2ealign_forward(e2ealign_handle* h, const float* mel, const float* keys, co
   FwdArgs a{mel, keys, speaker, prior, nullptr, B, T, L};
   RET(check_forward(h, a));
   if (txt_lens) {
-    RET(fetch_lens(h, txt_lens, B, tl));
+    RET(fetch_host(h, txt_lens, B, tl));
     RET(check_lens(h, tl, L, "txt_lens", "L"));
     a.txt_lens = &tl;
   }
@@ -781,9 +633,9 @@ int e2ealign_mas(e2ealign_handle* h, const float* map, int flags, const int64_t*
     if (flags & E2EALIGN_LOG_MAP) return h->fail(E2EALIGN_EINVAL, "the resident attn is a probability map: E2EALIGN_LOG_MAP does not apply");
   }
   std::vector<int64_t> il, ol;
-  RET(fetch_lens(h, in_lens, B, il));
+  RET(fetch_host(h, in_lens, B, il));
   RET(check_lens(h, il, L, "in_lens", "L"));
-  RET(fetch_lens(h, out_lens, B, ol));
+  RET(fetch_host(h, out_lens, B, ol));
   RET(check_lens(h, ol, T, "out_lens", "T"));
   RET(begin_call(h));
   const size_t n = (size_t)B * T * L * 4;
@@ -811,9 +663,9 @@ int e2ealign_align(e2ealign_handle* h, const float* mel, const float* keys, cons
   FwdArgs a{mel, keys, speaker, prior, &tl, B, T, L};
   RET(check_forward(h, a));
   if (!txt_lens || !mel_lens) return h->fail(E2EALIGN_EINVAL, "txt_lens and mel_lens must not be NULL");
-  RET(fetch_lens(h, txt_lens, B, tl));
+  RET(fetch_host(h, txt_lens, B, tl));
   RET(check_lens(h, tl, L, "txt_lens", "L"));
-  RET(fetch_lens(h, mel_lens, B, ml));
+  RET(fetch_host(h, mel_lens, B, ml));
   RET(check_lens(h, ml, T, "mel_lens", "T"));
   RET(begin_call(h));
   RET(run_forward(h, a));
@@ -826,35 +678,14 @@ int e2ealign_align(e2ealign_handle* h, const float* mel, const float* keys, cons
   return finish(h, true, true);
 }
 
-int e2ealign_profile_enable(e2ealign_handle* h, int on) {
-  if (!h) return E2EALIGN_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->profile = on != 0;
-  return E2EALIGN_OK;
-}
-
-int e2ealign_profile_read(e2ealign_handle* h, double ms_out[3]) {
-  if (!h) return E2EALIGN_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!ms_out) return h->fail(E2EALIGN_EINVAL, "ms_out is NULL");
-  for (int i = 0; i < 3; ++i) ms_out[i] = h->last_ms[i];
-  return E2EALIGN_OK;
-}
+int e2ealign_profile_enable(e2ealign_handle* h, int on) { return companion::profile_enable(h, on); }
+int e2ealign_profile_read(e2ealign_handle* h, double ms_out[3]) { return companion::profile_read(h, ms_out); }
 
 #ifdef E2EALIGN_TEST_HOOKS
 int e2ealign_debug_poison_workspace(e2ealign_handle* h) {
   if (!h) return E2EALIGN_EINVAL;
   std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->open) return E2EALIGN_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  for (Buf* b : {&h->kx, &h->ky, &h->kenc, &h->qx, &h->qy, &h->spk, &h->kspk, &h->qspk, &h->prior, &h->attn, &h->logp, &h->hard, &h->dur, &h->bits, &h->map,
-                 &h->lens_txt, &h->lens_in, &h->lens_out}) {
-    if (!b->p) continue;
-    const size_t n = b->bytes / 4;
-    hipLaunchKernelGGL(aln_poison_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t*)b->p, n);
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  RET(poison_workspaces(h));
   h->rB = h->rT = h->rL = 0;
   return E2EALIGN_OK;
 }

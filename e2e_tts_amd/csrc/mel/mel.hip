@@ -23,6 +23,10 @@
 #include <vector>
 
 #include "../../../include/e2etts_mel.h"
+#ifdef E2EMEL_TEST_HOOKS
+#define E2E_COMPANION_TEST_HOOKS
+#endif
+#include "../companion/handle.h"
 #include "../kernels.h"
 
 #ifndef E2EMEL_SRC_HASH
@@ -30,6 +34,10 @@
 #endif
 
 using namespace e2etts;
+using namespace e2etts::companion;
+
+static_assert(E2EMEL_OK == E_OK && E2EMEL_EINVAL == E_INVAL && E2EMEL_EHIP == E_HIP && E2EMEL_ESTATE == E_STATE && E2EMEL_ENOMEM == E_NOMEM,
+              "include/e2etts_mel.h and csrc/companion/handle.h disagree on the error codes");
 
 namespace {
 
@@ -155,115 +163,23 @@ __global__ void __launch_bounds__(TAIL_THREADS) mel_tail_kernel(const float* __r
   }
 }
 
-#ifdef E2EMEL_TEST_HOOKS
-__global__ void mel_poison_kernel(uint32_t* p, size_t n) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = 0x7fc00000u | (uint32_t)(i & 0xffff);
-}
-#endif
-
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 thread_local std::string g_create_error;
 
 }  // namespace
 
-struct e2emel_handle {
-  int device = 0;
+struct e2emel_handle : Handle {
   int n_fft = 0, hop = 0, nov = 0, n_mel = 0, bins = 0, cpad = 0, tile = 0;
   float clip = 1e-5f, log_clip = 0.f;            // log_clip = log(clip) in float64, rounded once
-  std::mutex mu;
-  std::string err;
-  bool open = false;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {};
-  hipEvent_t order_ev = nullptr;
-  bool profile = false;
-  double last_ms[3] = {0, 0, 0};
-  size_t dev_bytes = 0;
   bool loaded = false;
-  Buf wf, wf_frag, basis, band;                  // the bases
-  Buf in, pad, spec, mel, energy, lens;          // workspaces; mel / energy are the resident outputs
+  Buf wf{this, Buf::WEIGHTS}, wf_frag{this, Buf::WEIGHTS}, basis{this, Buf::WEIGHTS}, band{this, Buf::WEIGHTS};   // the bases
+  Buf in{this}, pad{this}, spec{this}, mel{this}, energy{this}, lens{this};   // workspaces; mel / energy are the resident outputs
   std::vector<int32_t> host_lens;                // int32 image of the frame counts: outlives the asynchronous copy of a call
   std::vector<int64_t> host_lens64;
   std::vector<int32_t> host_band;                // [n_mel][first, last] as recorded by e2emel_load
-  bool unfinished = false;                       // a call returned on an error before its stream was drained
   int rB = 0;                                    // batch of the resident outputs (0: nothing resident)
-
-  int fail(int code, const std::string& msg) {
-    err = msg;
-    return code;
-  }
 };
 
 namespace {
-
-#define HIPCHK(h, call)                                                                                    \
-  do {                                                                                                     \
-    hipError_t e_ = (call);                                                                                \
-    if (e_ != hipSuccess) return (h)->fail(E2EMEL_EHIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define KCHK(h, call)                                                             \
-  do {                                                                            \
-    const char* m_ = (call);                                                      \
-    if (m_) return (h)->fail(E2EMEL_EHIP, std::string("launch refused: ") + m_); \
-  } while (0)
-#define RET(call)                    \
-  do {                               \
-    int rc_ = (call);                \
-    if (rc_ != E2EMEL_OK) return rc_; \
-  } while (0)
-
-bool is_device_pointer(const void* p) {
-  hipPointerAttribute_t attr;
-  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return attr.type == hipMemoryTypeDevice;
-}
-
-int open_device(e2emel_handle* h) {
-  HIPCHK(h, hipSetDevice(h->device));
-  if (h->open) return E2EMEL_OK;
-  HIPCHK(h, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  for (auto& e : h->ev) HIPCHK(h, hipEventCreate(&e));
-  HIPCHK(h, hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
-  h->open = true;
-  return E2EMEL_OK;
-}
-
-int reserve(e2emel_handle* h, Buf& b, size_t bytes) {
-  bytes = (bytes + 255) / 256 * 256;
-  if (b.bytes >= bytes) return E2EMEL_OK;
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  if (b.p) {
-    HIPCHK(h, hipFree(b.p));
-    h->dev_bytes -= b.bytes;
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  if (hipMalloc(&b.p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return h->fail(E2EMEL_ENOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
-  }
-  b.bytes = bytes;
-  h->dev_bytes += bytes;
-  return E2EMEL_OK;
-}
-
-// frees a buffer (the stream must be drained)
-void release(e2emel_handle* h, Buf& b) {
-  if (!b.p) return;
-  (void)hipFree(b.p);
-  h->dev_bytes -= b.bytes;
-  b.p = nullptr;
-  b.bytes = 0;
-}
 
 // the images of e2emel_load into fresh buffers nb = {wf, wf_frag, basis, band}; returns after the stream has drained
 int stage_bases(e2emel_handle* h, Buf* nb, const std::vector<float>& wf, const std::vector<float>& mb, const std::vector<int32_t>& band) {
@@ -277,18 +193,6 @@ int stage_bases(e2emel_handle* h, Buf* nb, const std::vector<float>& wf, const s
   HIPCHK(h, hipMemcpyAsync(nb[3].p, band.data(), band.size() * 4, hipMemcpyHostToDevice, h->stream));
   KCHK(h, launch_f32_to_frag((const float*)nb[0].p, (float*)nb[1].p, h->cpad, h->nov, h->hop, h->stream));
   HIPCHK(h, hipStreamSynchronize(h->stream));   // the host images are read until here
-  return E2EMEL_OK;
-}
-
-// host copy of `count` floats behind a host or device pointer
-int fetch_floats(e2emel_handle* h, const float* p, size_t count, std::vector<float>& out) {
-  out.resize(count);
-  if (is_device_pointer(p)) {
-    HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpy(out.data(), p, count * 4, hipMemcpyDefault));
-  } else {
-    memcpy(out.data(), p, count * 4);
-  }
   return E2EMEL_OK;
 }
 
@@ -341,19 +245,7 @@ int e2emel_create(int device_id, int n_fft, int hop, int n_mel, e2emel_handle** 
   return E2EMEL_OK;
 }
 
-void e2emel_destroy(e2emel_handle* h) {
-  if (!h) return;
-  if (h->open && hipSetDevice(h->device) == hipSuccess) {
-    (void)hipStreamSynchronize(h->stream);
-    for (Buf* b : {&h->wf, &h->wf_frag, &h->basis, &h->band, &h->in, &h->pad, &h->spec, &h->mel, &h->energy, &h->lens})
-      if (b->p) (void)hipFree(b->p);
-    for (auto& e : h->ev)
-      if (e) (void)hipEventDestroy(e);
-    if (h->order_ev) (void)hipEventDestroy(h->order_ev);
-    (void)hipStreamDestroy(h->stream);
-  }
-  delete h;
-}
+void e2emel_destroy(e2emel_handle* h) { companion::destroy(h); }
 
 int e2emel_load(e2emel_handle* h, const float* dft_basis, const float* mel_basis, float clip_val) {
   if (!h) return E2EMEL_EINVAL;
@@ -364,8 +256,8 @@ int e2emel_load(e2emel_handle* h, const float* dft_basis, const float* mel_basis
   // the DFT basis -> conv_gemm's tap-major [Cout][KW * Cin] with Cout = cpad (rows beyond 2 * bins zero) and tap j = columns j * hop ..:
   // the basis rows as they are
   std::vector<float> hb, mb, wf((size_t)cpad * N, 0.f);
-  RET(fetch_floats(h, dft_basis, (size_t)2 * bins * N, hb));
-  RET(fetch_floats(h, mel_basis, (size_t)M * bins, mb));
+  RET(fetch_host(h, dft_basis, (size_t)2 * bins * N, hb));
+  RET(fetch_host(h, mel_basis, (size_t)M * bins, mb));
   std::copy(hb.begin(), hb.end(), wf.begin());
   // [first, last] non-zero bin of every mel row (an all-zero row: the empty band [0, -1])
   std::vector<int32_t> band((size_t)2 * M);
@@ -381,17 +273,17 @@ int e2emel_load(e2emel_handle* h, const float* dft_basis, const float* mel_basis
   }
   RET(open_device(h));
   // staged in buffers of their own and swapped in only when everything has arrived: a failure leaves the bases loaded before in place
-  Buf nb[4];   // wf, wf_frag, basis, band
+  Buf nb[4];   // wf, wf_frag, basis, band: free-standing until they replace the members below
   const int rc = stage_bases(h, nb, wf, mb, band);
   if (rc != E2EMEL_OK) {
     for (Buf& b : nb) release(h, b);
     return rc;
   }
-  Buf* cur[4] = {&h->wf, &h->wf_frag, &h->basis, &h->band};
-  for (int i = 0; i < 4; ++i) {
-    release(h, *cur[i]);   // the stream is drained: nothing reads the old bases
-    *cur[i] = nb[i];
-  }
+  const auto swap_in = [h](Buf& member, const Buf& fresh) {
+    release(h, member);   // the stream is drained: nothing reads the old bases
+    member = fresh;
+  };
+  swap_in(h->wf, nb[0]); swap_in(h->wf_frag, nb[1]); swap_in(h->basis, nb[2]); swap_in(h->band, nb[3]);
   h->rB = 0;
   h->host_band = band;
   h->clip = clip_val;
@@ -400,32 +292,10 @@ int e2emel_load(e2emel_handle* h, const float* dft_basis, const float* mel_basis
   return E2EMEL_OK;
 }
 
-void* e2emel_stream(e2emel_handle* h) {
-  if (!h) return nullptr;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (open_device(h) != E2EMEL_OK) return nullptr;
-  return (void*)h->stream;
-}
-
-int e2emel_order_after(e2emel_handle* h, void* caller_stream) {
-  if (!h) return E2EMEL_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  RET(open_device(h));
-  HIPCHK(h, hipEventRecord(h->order_ev, (hipStream_t)caller_stream));
-  HIPCHK(h, hipStreamWaitEvent(h->stream, h->order_ev, 0));
-  return E2EMEL_OK;
-}
-
-int e2emel_sync(e2emel_handle* h) {
-  if (!h) return E2EMEL_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->open) return E2EMEL_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return E2EMEL_OK;
-}
-
-size_t e2emel_device_bytes(const e2emel_handle* h) { return h ? h->dev_bytes : 0; }
+void* e2emel_stream(e2emel_handle* h) { return companion::stream(h); }
+int e2emel_order_after(e2emel_handle* h, void* caller_stream) { return companion::order_after(h, caller_stream); }
+int e2emel_sync(e2emel_handle* h) { return companion::sync(h); }
+size_t e2emel_device_bytes(const e2emel_handle* h) { return companion::device_bytes(h); }
 
 int e2emel_forward(e2emel_handle* h, const void* audio, int dtype, long long audio_stride, const int64_t* n_valid, int B, long long n, float* mel_out,
                    float* energy_out, int64_t* mel_lens_out, int* T_out) {
@@ -444,14 +314,7 @@ int e2emel_forward(e2emel_handle* h, const void* audio, int dtype, long long aud
   const size_t esz = dtype == E2EMEL_I16 ? 2 : 4;
   if ((uintptr_t)audio % esz) return h->fail(E2EMEL_EINVAL, "audio is not aligned to its element size");
   std::vector<int64_t> nv((size_t)B, (int64_t)n);
-  if (n_valid) {
-    if (is_device_pointer(n_valid)) {
-      HIPCHK(h, hipSetDevice(h->device));
-      HIPCHK(h, hipMemcpy(nv.data(), n_valid, (size_t)B * 8, hipMemcpyDefault));
-    } else {
-      memcpy(nv.data(), n_valid, (size_t)B * 8);
-    }
-  }
+  if (n_valid) RET(fetch_host(h, n_valid, (size_t)B, nv));
   int T = 0;
   for (int b = 0; b < B; ++b) {
     const long long v = nv[b];
@@ -463,9 +326,7 @@ int e2emel_forward(e2emel_handle* h, const void* audio, int dtype, long long aud
   }
   if (!h->loaded) return h->fail(E2EMEL_ESTATE, "e2emel_forward before e2emel_load");
   // ---- enqueue
-  RET(open_device(h));
-  if (h->unfinished) HIPCHK(h, hipStreamSynchronize(h->stream));
-  h->unfinished = true;
+  RET(begin_call(h));
   h->rB = 0;
   const int R = T + nov - 1, M = h->n_mel;
   bool ragged = false;
@@ -525,21 +386,14 @@ int e2emel_forward(e2emel_handle* h, const void* audio, int dtype, long long aud
     HIPCHK(h, hipGetLastError());
   }
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[3], s));
-  if (mel_out) HIPCHK(h, hipMemcpyAsync(mel_out, h->mel.p, (size_t)B * T * M * 4, hipMemcpyDefault, s));
-  if (energy_out) HIPCHK(h, hipMemcpyAsync(energy_out, h->energy.p, (size_t)B * T * 4, hipMemcpyDefault, s));
+  RET(copy_out(h, mel_out, h->mel.p, (size_t)B * T * M * 4));
+  RET(copy_out(h, energy_out, h->energy.p, (size_t)B * T * 4));
   if (mel_lens_out) {
     if (is_device_pointer(mel_lens_out)) HIPCHK(h, hipMemcpyAsync(mel_lens_out, h->host_lens64.data(), (size_t)B * 8, hipMemcpyHostToDevice, s));
     else memcpy(mel_lens_out, h->host_lens64.data(), (size_t)B * 8);
   }
-  HIPCHK(h, hipStreamSynchronize(s));
-  h->unfinished = false;
-  if (h->profile) {
-    for (int i = 0; i < 3; ++i) {
-      float ms = 0.f;
-      HIPCHK(h, hipEventElapsedTime(&ms, h->ev[i], h->ev[i + 1]));
-      h->last_ms[i] = ms;
-    }
-  }
+  const Phase phases[3] = {{0, 1}, {1, 2}, {2, 3}};   // pad, transform, tail
+  RET(finish(h, phases));
   h->rB = B;
   if (T_out) *T_out = T;
   return E2EMEL_OK;
@@ -559,34 +413,14 @@ const float* e2emel_energy_dev(e2emel_handle* h) {
 
 int e2emel_tile_frames(const e2emel_handle* h) { return h ? h->tile : 0; }
 
-int e2emel_profile_enable(e2emel_handle* h, int on) {
-  if (!h) return E2EMEL_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  h->profile = on != 0;
-  return E2EMEL_OK;
-}
-
-int e2emel_profile_read(e2emel_handle* h, double ms_out[3]) {
-  if (!h) return E2EMEL_EINVAL;
-  std::lock_guard<std::mutex> lk(h->mu);
-  if (!ms_out) return h->fail(E2EMEL_EINVAL, "ms_out is NULL");
-  for (int i = 0; i < 3; ++i) ms_out[i] = h->last_ms[i];
-  return E2EMEL_OK;
-}
+int e2emel_profile_enable(e2emel_handle* h, int on) { return companion::profile_enable(h, on); }
+int e2emel_profile_read(e2emel_handle* h, double ms_out[3]) { return companion::profile_read(h, ms_out); }
 
 #ifdef E2EMEL_TEST_HOOKS
 int e2emel_debug_poison_workspace(e2emel_handle* h) {
   if (!h) return E2EMEL_EINVAL;
   std::lock_guard<std::mutex> lk(h->mu);
-  if (!h->open) return E2EMEL_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  for (Buf* b : {&h->in, &h->pad, &h->spec, &h->mel, &h->energy, &h->lens}) {
-    if (!b->p) continue;
-    const size_t n = b->bytes / 4;
-    hipLaunchKernelGGL(mel_poison_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (uint32_t*)b->p, n);
-  }
-  HIPCHK(h, hipGetLastError());
-  HIPCHK(h, hipStreamSynchronize(h->stream));
+  RET(poison_workspaces(h));
   h->rB = 0;
   return E2EMEL_OK;
 }

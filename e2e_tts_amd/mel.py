@@ -11,25 +11,43 @@ from typing import Optional
 
 import numpy as np
 
-from ._lib import _addr, _expect, _is_cuda
+from . import _companion
+from ._companion import E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM  # noqa: F401  (the codes of include/e2etts_mel.h)
+from ._lib import _addr, _expect
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_mel.so")
 # the TEST build of the same source (-DE2EMEL_TEST_HOOKS: two more exports, e2emel_debug_poison_workspace and e2emel_debug_force_dense), loaded instead of the product
-# library only when E2ETTS_TEST_HOOKS=1 is in the environment (tests/conftest.py sets it), as aligner.py does
+# library only when E2ETTS_TEST_HOOKS=1 is in the environment (_companion.load)
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_mel_test.so")
 ABI_VERSION = 1   # E2EMEL_ABI_VERSION of the include/e2etts_mel.h this binding mirrors
-E_OK, E_INVAL, E_HIP, E_STATE, E_NOMEM = 0, -1, -2, -3, -4
 F32, I16 = 0, 1   # E2EMEL_F32, E2EMEL_I16
 MAX_B, MAX_MEL = 4096, 1024
 
-# every entry point include/e2etts_mel.h declares, and all the library exports (tests/test_mel_host.py compares the three)
-EXPORTED_SYMBOLS = [
-    "e2emel_version", "e2emel_abi_version", "e2emel_last_error", "e2emel_create", "e2emel_destroy", "e2emel_load", "e2emel_stream",
-    "e2emel_order_after", "e2emel_sync", "e2emel_device_bytes", "e2emel_forward", "e2emel_mel_dev", "e2emel_energy_dev", "e2emel_tile_frames",
-    "e2emel_profile_enable", "e2emel_profile_read",
-]
-TEST_HOOK_SYMBOLS = ["e2emel_debug_poison_workspace", "e2emel_debug_force_dense"]
+_P, _I, _F, _SZ, _LL = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
+# every entry point include/e2etts_mel.h declares, and all the library exports (tests/test_mel_host.py compares the three):
+# name -> (restype, argtypes)
+SIGNATURES = {
+    "e2emel_version": (C.c_char_p, []),
+    "e2emel_abi_version": (_I, []),
+    "e2emel_last_error": (C.c_char_p, [_P]),
+    "e2emel_create": (_I, [_I, _I, _I, _I, C.POINTER(_P)]),
+    "e2emel_destroy": (None, [_P]),
+    "e2emel_load": (_I, [_P, _P, _P, _F]),
+    "e2emel_stream": (_P, [_P]),
+    "e2emel_order_after": (_I, [_P, _P]),
+    "e2emel_sync": (_I, [_P]),
+    "e2emel_device_bytes": (_SZ, [_P]),
+    "e2emel_forward": (_I, [_P, _P, _I, _LL, _P, _I, _LL, _P, _P, _P, C.POINTER(_I)]),
+    "e2emel_mel_dev": (_P, [_P]),
+    "e2emel_energy_dev": (_P, [_P]),
+    "e2emel_tile_frames": (_I, [_P]),
+    "e2emel_profile_enable": (_I, [_P, _I]),
+    "e2emel_profile_read": (_I, [_P, C.POINTER(C.c_double)]),
+}
+HOOK_SIGNATURES = {"e2emel_debug_poison_workspace": (_I, [_P]), "e2emel_debug_force_dense": (_I, [_P, _I])}
+EXPORTED_SYMBOLS = list(SIGNATURES)
+TEST_HOOK_SYMBOLS = list(HOOK_SIGNATURES)
 
 _lib = None
 
@@ -37,57 +55,9 @@ _lib = None
 def load_library() -> C.CDLL:
     """dlopen the in-tree mel library (built by __graft_entry__.build())."""
     global _lib
-    if _lib is not None:
-        return _lib
-    hooks = os.environ.get("E2ETTS_TEST_HOOKS", "") not in ("", "0")
-    path = TEST_LIB_PATH if hooks else LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950).  e2e_tts_amd has no CPU fallback.")
-    import torch  # noqa: F401  (ONE HIP runtime per process: see _lib.load_library)
-    lib = C.CDLL(path)
-    P, I, F, SZ, LL = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_longlong
-    lib.e2emel_version.restype = C.c_char_p
-    lib.e2emel_version.argtypes = []
-    lib.e2emel_abi_version.restype = I
-    lib.e2emel_abi_version.argtypes = []
-    if lib.e2emel_abi_version() != ABI_VERSION:
-        raise ImportError(f"{path}: ABI version {lib.e2emel_abi_version()}, this binding mirrors version {ABI_VERSION}: rebuild the library")
-    lib.e2emel_last_error.restype = C.c_char_p
-    lib.e2emel_last_error.argtypes = [P]
-    lib.e2emel_create.restype = I
-    lib.e2emel_create.argtypes = [I, I, I, I, C.POINTER(P)]
-    lib.e2emel_destroy.restype = None
-    lib.e2emel_destroy.argtypes = [P]
-    lib.e2emel_load.restype = I
-    lib.e2emel_load.argtypes = [P, P, P, F]
-    lib.e2emel_stream.restype = P
-    lib.e2emel_stream.argtypes = [P]
-    lib.e2emel_order_after.restype = I
-    lib.e2emel_order_after.argtypes = [P, P]
-    lib.e2emel_sync.restype = I
-    lib.e2emel_sync.argtypes = [P]
-    lib.e2emel_device_bytes.restype = SZ
-    lib.e2emel_device_bytes.argtypes = [P]
-    lib.e2emel_forward.restype = I
-    lib.e2emel_forward.argtypes = [P, P, I, LL, P, I, LL, P, P, P, C.POINTER(I)]
-    lib.e2emel_mel_dev.restype = P
-    lib.e2emel_mel_dev.argtypes = [P]
-    lib.e2emel_energy_dev.restype = P
-    lib.e2emel_energy_dev.argtypes = [P]
-    lib.e2emel_tile_frames.restype = I
-    lib.e2emel_tile_frames.argtypes = [P]
-    lib.e2emel_profile_enable.restype = I
-    lib.e2emel_profile_enable.argtypes = [P, I]
-    lib.e2emel_profile_read.restype = I
-    lib.e2emel_profile_read.argtypes = [P, C.POINTER(C.c_double)]
-    if hooks:
-        lib.e2emel_debug_poison_workspace.restype = I
-        lib.e2emel_debug_poison_workspace.argtypes = [P]
-        lib.e2emel_debug_force_dense.restype = I
-        lib.e2emel_debug_force_dense.argtypes = [P, I]
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _companion.load("e2emel", LIB_PATH, TEST_LIB_PATH, ABI_VERSION, SIGNATURES, HOOK_SIGNATURES)
+    return _lib
 
 
 def hann_window(win_length: int) -> np.ndarray:
@@ -190,9 +160,10 @@ class ResidentTensor:
         return int(np.prod(self.shape))
 
 
-class MelFrontend:
+class MelFrontend(_companion.CompanionHandle):
     """One e2emel_handle.  Inputs are numpy arrays or torch tensors (host or GPU); outputs are written into the arrays / tensors given
     (``out_*``) or returned as fresh numpy arrays when asked for by ``want``."""
+    _prefix, _what, _phases = "e2emel", "mel", ("pad", "transform", "tail")
 
     def __init__(self, n_fft: int, hop: int, n_mel: int, device: int = 0):
         self.lib = load_library()
@@ -204,35 +175,6 @@ class MelFrontend:
         self._h = h
         self.bins = self.n_fft // 2 + 1
         self.tile_frames = int(self.lib.e2emel_tile_frames(h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self.lib.e2emel_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int, what: str):
-        if rc == E_OK:
-            return
-        msg = f"{what}: {self.lib.e2emel_last_error(self._h).decode()}"
-        if rc == E_INVAL:
-            raise ValueError(msg)
-        if rc == E_NOMEM:
-            raise MemoryError(msg)
-        raise RuntimeError(msg)
-
-    def _order(self, *xs):
-        """Order the handle's stream after torch's current stream when any argument lives on the GPU."""
-        if any(_is_cuda(x) for x in xs):
-            import torch
-            with torch.cuda.device(self.device):
-                s = torch.cuda.current_stream().cuda_stream
-            self._check(self.lib.e2emel_order_after(self._h, s), "e2emel_order_after")
 
     def load(self, dft, mel_basis, clip_val: float = 1e-5) -> None:
         """dft [2 * bins, n_fft] (``dft_basis``), mel_basis [n_mel, bins], both float32 host arrays."""
@@ -299,32 +241,6 @@ class MelFrontend:
         B, T = self._resident
         return ResidentTensor(mp, (B, T, self.n_mel)), ResidentTensor(ep, (B, T))
 
-    def stream(self) -> int:
-        return int(self.lib.e2emel_stream(self._h) or 0)
-
-    def profile_enable(self, on: bool = True):
-        self._check(self.lib.e2emel_profile_enable(self._h, 1 if on else 0), "e2emel_profile_enable")
-
-    def profile_read(self):
-        """Milliseconds of the last call's phases: {"pad", "transform", "tail"}."""
-        ms = (C.c_double * 3)()
-        self._check(self.lib.e2emel_profile_read(self._h, ms), "e2emel_profile_read")
-        return {"pad": ms[0], "transform": ms[1], "tail": ms[2]}
-
-    def poison_workspace(self):
-        """Test build only (E2ETTS_TEST_HOOKS=1)."""
-        if not hasattr(self.lib, "e2emel_debug_poison_workspace"):
-            raise RuntimeError("poison_workspace needs the test build of the mel library (E2ETTS_TEST_HOOKS=1)")
-        self._check(self.lib.e2emel_debug_poison_workspace(self._h), "e2emel_debug_poison_workspace")
-
     def force_dense(self, on: bool = True):
         """Test build only (E2ETTS_TEST_HOOKS=1): walk all bins of every mel row instead of the recorded bands."""
-        if not hasattr(self.lib, "e2emel_debug_force_dense"):
-            raise RuntimeError("force_dense needs the test build of the mel library (E2ETTS_TEST_HOOKS=1)")
-        self._check(self.lib.e2emel_debug_force_dense(self._h, 1 if on else 0), "e2emel_debug_force_dense")
-
-    def device_bytes(self) -> int:
-        return int(self.lib.e2emel_device_bytes(self._h))
-
-    def sync(self):
-        self._check(self.lib.e2emel_sync(self._h), "e2emel_sync")
+        self._hook("force_dense", 1 if on else 0)
