@@ -142,16 +142,26 @@ struct e2etts_engine {
   DevBuf logd, durf, cum, mel64, mel32, posbuf, ppred, epred, pidx, eidx;
   DevBuf ctlbuf;  // [3][B * L] fp32: the d / p / e controls of the _ctl entry points (grows with B * L only)
   DevBuf dx, dxb, mel, melpost, pn1, pn2;
-  DevBuf melin, v0, v1, v2, v3, wav, pcm;
-  // small batches: the ResBlocks of a vocoder stage run side by side, ResBlock j > 0 on side stream j - 1 with buffers of its own
-  // (stage sum, two ping-pong buffers); created on first use
-  DevBuf vside[E2ETTS_MAX_RB_KERNELS - 1][3];
-  hipStream_t side[E2ETTS_MAX_RB_KERNELS - 1] = {};
-  hipEvent_t ev_fork = nullptr, ev_join[E2ETTS_MAX_RB_KERNELS - 1] = {};
+  DevBuf melin;
+  // Everything one vocoder pass works in besides the weights; vocoder_impl / vocoder_act16 are handed one and touch no other pass.  The
+  // engine owns one for the one-shot calls and synthesize (`voc`: its stream is the engine's, its result the resident one), every
+  // stream slot one, e2etts_denoiser_calibrate one.
+  struct VocPass {
+    hipStream_t stream = nullptr;   // the pass's compute stream: the engine is enqueuing on it (e->stream, see OnStream) while the pass runs
+    DevBuf v0, v1, v2, v3;
+    // small batches: the ResBlocks of a vocoder stage run side by side, ResBlock j > 0 on side stream j - 1 with buffers of its own
+    // (stage sum, two ping-pong buffers); created on first use
+    DevBuf vside[E2ETTS_MAX_RB_KERNELS - 1][3];
+    hipStream_t side[E2ETTS_MAX_RB_KERNELS - 1] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[E2ETTS_MAX_RB_KERNELS - 1] = {};
+    DevBuf wav, pcm;
+    DevBuf istft_q, istft_ri, istft_sp;  // iSTFTNet tail: conv_post output, Re/Im per bin, exp / sin heads (tap "istft_spec_phase")
+    int istft_B = 0;
+    long long istft_F = 0;
+    bool resident = false;   // a finished pass becomes the engine's resident result (have_wav, voc_B, voc_T): what fetches and taps read
+  };
+  VocPass voc;
   DevBuf tempo_in, tempo_out;  // e2etts_tempo
-  DevBuf istft_q, istft_ri, istft_sp;  // iSTFTNet tail: conv_post output, Re/Im per bin, exp / sin heads (tap "istft_spec_phase")
-  int istft_B = 0;
-  long long istft_F = 0;
   int64_t* h_mel = nullptr;  // pinned
   int last_B = 0, last_L = 0, last_T = 0, voc_B = 0, voc_T = 0;
   bool have_acoustic = false, have_wav = false;
@@ -176,15 +186,9 @@ struct e2etts_engine {
   // queues by default (GPU_MAX_HW_QUEUES), the null stream holds one, and streams beyond that share a queue, i.e. run in turn --
   // measured: with a copy stream of its own the two passes landed on one queue and did not overlap at all.
   static constexpr int ST_DEPTH = E2ETTS_ST_DEPTH;
-  struct VocCtx {   // what one vocoder pass works in besides the weights: swapped into the engine around vocoder_impl
-    hipStream_t stream = nullptr;
-    DevBuf v0, v1, v2, v3, vside[E2ETTS_MAX_RB_KERNELS - 1][3];
-    hipStream_t side[E2ETTS_MAX_RB_KERNELS - 1] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[E2ETTS_MAX_RB_KERNELS - 1] = {};
-  };
   struct StSlot {
-    VocCtx ctx;
-    DevBuf wav, pcm, win;
+    VocPass pass;   // (a stream of its own; the window's wav / PCM are pass.wav / pass.pcm)
+    DevBuf win;
     DevBuf dn_pad, dn_spec, dn_ola, dn_lens, dn_wav, dn_pcm;   // a denoised stream: the slot's own denoiser workspace and denoised outputs
     void* pin = nullptr;
     size_t pin_cap = 0;
@@ -211,7 +215,8 @@ struct e2etts_engine {
   DevBuf dn_wf, dn_wi, dn_wf_frag, dn_wi_frag;  // forward basis, tap-major [Cout][KW * Cin], the inverse basis as one [hop][cpad] matrix per tap, and their fragment-order copies
   DevBuf dn_win, dn_bias;                       // squared window [filter_length] float64; bias spectrum [filter_length / 2 + 1]
   DevBuf dn_in, dn_lens, dn_pad, dn_spec, dn_ola, dn_out, dn_pcm;
-  DevBuf dn_mel, dn_cwav, dn_cpcm, dn_iq, dn_iri, dn_isp;  // calibration: mel, the vocoder's outputs, stand-ins for the iSTFT tail's tap buffers
+  DevBuf dn_mel;    // calibration: the mel ...
+  VocPass dn_pass;  // ... and the pass that turns it into audio, on the engine's stream: no resident result (wav, PCM, iSTFT tap) is touched
   std::vector<int32_t> dn_h;                    // host copy of dn_lens: [2 + n_overlap][B] = valid samples, frames, rows of the overlap-add per inverse launch
 
   // profiling
@@ -270,6 +275,27 @@ int ensure(e2etts_engine* e, DevBuf& b, size_t bytes) {
 
 template <typename T>
 T* ptr(DevBuf& b) { return reinterpret_cast<T*>(b.p); }
+
+using VocPass = e2etts_engine::VocPass;
+
+// e->stream is the stream the engine is enqueuing on: conv(), ProfScope, ensure() and the denoiser helpers read it.  Work that goes
+// elsewhere -- a stream slot's pass, a ResBlock on a side stream -- says so with one of these for as long as it lasts; besides
+// e2etts_create and e2etts_destroy nothing else assigns e->stream.
+struct OnStream {
+  e2etts_engine* e;
+  hipStream_t back;
+  OnStream(e2etts_engine* e_, hipStream_t s) : e(e_), back(e_->stream) { e->stream = s; }
+  ~OnStream() { e->stream = back; }
+  OnStream(const OnStream&) = delete;
+  OnStream& operator=(const OnStream&) = delete;
+};
+
+template <typename F>
+void for_each_pass(e2etts_engine* e, F f) {
+  f(e->voc);
+  f(e->dn_pass);
+  for (auto& sl : e->st_slot) f(sl.pass);
+}
 
 int prof_class(e2etts_engine* e, const char* name) {
   for (size_t i = 0; i < e->prof_stats.size(); ++i)
@@ -1441,8 +1467,231 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   return E2ETTS_OK;
 }
 
+// ---- the ResBlock launches of the two vocoder walks (vocoder_impl, vocoder_act16): one set of builders
+
+// The tuning aids of vocoder_impl ("tuning aids"), read once.  All of them change speed only, never a result bit.
+struct VocTuning {
+  long long conc_frames;  // E2ETTS_VOC_CONC_FRAMES=n: most frames per call whose ResBlocks run side by side (unset, < 0: 2 048; 4 096 in exact fp32)
+  bool group;             // E2ETTS_VOC_GROUP=0 keeps the side streams where plain bf16 groups the ResBlocks into one launch
+  bool stream_side;       // E2ETTS_STREAM_SIDE=1: side streams in a stream slot's pass too
+  int brb_stage_big;      // E2ETTS_BRB_STAGE_BIG=0: no whole-stage rb_bf16 launch at large grids
+  bool brb_always;        // E2ETTS_BRB_ALWAYS=1: rb_bf16 (one ResBlock per launch) at large grids too
+  bool profile_fine;      // E2ETTS_PROFILE_FINE (set at all): one profile class per layer shape
+  bool bpair_big;         // E2ETTS_BPAIR_BIG=0 keeps resblock_pair.hip at large grids
+  bool defer_join;        // E2ETTS_VOC_DEFER_JOIN=0: a grouped stage's join as a launch of its own
+};
+const VocTuning& voc_tuning() {
+  static const VocTuning t = [] {
+    auto num = [](const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; };
+    VocTuning v;
+    v.conc_frames = num("E2ETTS_VOC_CONC_FRAMES", -1);
+    v.group = num("E2ETTS_VOC_GROUP", 1) != 0;
+    v.stream_side = num("E2ETTS_STREAM_SIDE", 0) != 0;
+    v.brb_stage_big = (int)num("E2ETTS_BRB_STAGE_BIG", 1);
+    v.brb_always = num("E2ETTS_BRB_ALWAYS", 0) != 0;
+    v.profile_fine = getenv("E2ETTS_PROFILE_FINE") != nullptr;
+    v.bpair_big = num("E2ETTS_BPAIR_BIG", 1) != 0;
+    v.defer_join = num("E2ETTS_VOC_DEFER_JOIN", 1) != 0;
+    return v;
+  }();
+  return t;
+}
+
+// How a walk reads a convolution's weights.  kind 0, vocoder_impl: fp32 biases, the fragment-order pair images and -- in plain bf16 --
+// the conv_bf16.hip images of bimg_of; kind 1 / 2, vocoder_act16: bf16 / fp16 elements, i.e. the images of bimg_of | bimg_act / himg_of and
+// the parameters rounded to that type (r16_of / r16h_of).
+struct VocWeights {
+  const e2etts_engine* e;
+  int kind;
+  const float* param(const float* p) const {   // a bias (conv_post's weights) as the walk's arithmetic takes it
+    if (!kind) return p;
+    const auto& tab = kind == 2 ? e->r16h_of : e->r16_of;
+    auto it = tab.find(p);
+    return it == tab.end() ? nullptr : it->second;
+  }
+  const void* image(const ConvW& w, int* split = nullptr) const {   // null: the walk has no such image
+    if (kind == 2) {
+      auto ih = e->himg_of.find(w.w);
+      if (ih == e->himg_of.end()) return nullptr;
+      if (split) *split = ih->second.second;
+      return ih->second.first;
+    }
+    if (!w.wx3 || (!kind && e->voc_precision != E2ETTS_PRECISION_BF16)) return nullptr;
+    auto it = e->bimg_of.find(w.wx3);
+    if (it == e->bimg_of.end()) {
+      if (!kind) return nullptr;
+      it = e->bimg_act.find(w.wx3);
+      if (it == e->bimg_act.end()) return nullptr;
+    }
+    if (split) *split = it->second.second;
+    return it->second.first;
+  }
+  const float* pair_frag(size_t idx, size_t m) const {   // resblock_pair.hip's image of pair m (null where bind_vocoder built none)
+    if (kind) return nullptr;
+    const auto& tab = e->voc_precision == E2ETTS_PRECISION_FP32 ? e->rb_pair_frag32 : e->rb_pair_frag;
+    return idx < tab.size() && m < tab[idx].size() ? tab[idx][m] : nullptr;
+  }
+  int pair_mode() const { return kind ? kind + 2 : e->voc_precision; }   // PairParams::mode
+  const char* cls() const { return kind == 2 ? "fp16_act" : (kind ? "bf16_act" : "bf16"); }   // in the profile classes of the conv_bf16.hip launches
+  double elt() const { return kind ? 0.5 : 1.0; }   // activation bytes per element over fp32's: scales the *_bytes() figures
+};
+
+struct RbStage {   // the ResBlocks of vocoder stage `stage`: B x n rows of co channels
+  int stage, B, co;
+  long long n;
+};
+
+// The {stage sum, ping, pong} buffers of ResBlock j within a pass: the main ones, or those a ResBlock beside ResBlock 0 has for itself
+struct RbBufs {
+  float *S, *T1, *CUR;
+};
+RbBufs rb_bufs(VocPass& P, int j) {
+  if (j == 0) return {ptr<float>(P.v0), ptr<float>(P.v2), ptr<float>(P.v3)};
+  return {ptr<float>(P.vside[j - 1][0]), ptr<float>(P.vside[j - 1][1]), ptr<float>(P.vside[j - 1][2])};
+}
+
+// dispatch order inside a grouped launch: largest kernel size first
+void rb_order(const e2etts_config& c, int* order) {
+  for (int j = 0; j < c.voc_n_kernels; ++j) order[j] = j;
+  std::sort(order, order + c.voc_n_kernels, [&](int a, int b) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b]; });
+}
+
+// How ResBlock j closes (V/generator.py:44-48): on one stream the last pair of ResBlock j > 0 adds to the sum the ResBlocks before it left in S
+// and the last ResBlock divides by num_kernels; side by side every ResBlock writes a sum of its own and the join does both.
+struct Closing {
+  int accumulate;
+  float out_div;
+};
+Closing closing(int j, bool last_pair, int nk, bool side_by_side) {
+  const bool acc = last_pair && !side_by_side && j > 0;
+  return {acc ? 1 : 0, acc && j == nk - 1 ? (float)nk : 1.0f};
+}
+
+// Pair m of ResBlock j (V/layers.py:35-39) as one fused launch; the caller adds x, out, the row limits and the closing
+PairParams pair_params(const VocWeights& w, const RbStage& g, int j, int m) {
+  const auto& c = w.e->cfg;
+  const size_t idx = (size_t)g.stage * c.voc_n_kernels + j;
+  const ConvW &c1 = w.e->rb_c1[idx][m], &c2 = w.e->rb_c2[idx][m];
+  PairParams q;
+  q.wfrag = w.pair_frag(idx, m); q.b1 = w.param(c1.b); q.b2 = w.param(c2.b); q.bimg1 = w.image(c1); q.bimg2 = w.image(c2);
+  q.B = g.B; q.T = (int)g.n; q.C = g.co; q.KW = c.voc_rb_kernel[j]; q.dil = c.voc_rb_dil[j][m];
+  q.x_bs = q.out_bs = g.n * g.co; q.slope = 0.1f; q.mode = w.pair_mode();
+  return q;
+}
+
+// The same pair as two conv_bf16 launches with a 16-bit hand-over: a: mid = bf16(lrelu(c1(lrelu(x)) + b1)), conv2's operand as it is;
+// z: out = c2(mid) + b2 + x.  The caller adds the closing.
+void handover_params(const VocWeights& w, const RbStage& g, int j, int m, const void* x, void* mid, void* out, BConvParams& a, BConvParams& z) {
+  const auto& c = w.e->cfg;
+  const size_t idx = (size_t)g.stage * c.voc_n_kernels + j;
+  const int k = c.voc_rb_kernel[j], d = c.voc_rb_dil[j][m];
+  a = BConvParams();
+  a.in = x; a.in_bf16 = w.kind ? 1 : 0; a.in_slope = 0.1f; a.wimg = w.image(w.e->rb_c1[idx][m]); a.KWe = a.KW = k; a.dil = d; a.pad = (k * d - d) / 2;
+  a.bias = w.param(w.e->rb_c1[idx][m].b); a.act_slope = 0.1f; a.out_b = mid; a.act16 = w.kind; a.B = g.B; a.T = (int)g.n; a.Cin = a.Cout = g.co;
+  z = BConvParams();
+  z.in = mid; z.in_bf16 = 1; z.wimg = w.image(w.e->rb_c2[idx][m]); z.KWe = z.KW = k; z.dil = 1; z.pad = (k - 1) / 2;
+  z.bias = w.param(w.e->rb_c2[idx][m].b); z.res = reinterpret_cast<const float*>(x); z.act16 = w.kind; z.B = g.B; z.T = (int)g.n; z.Cin = z.Cout = g.co;
+  if (w.kind) z.out_b = out;
+  else z.out = reinterpret_cast<float*>(out);
+}
+
+// The whole ResBlock1 j as one launch (conv_bf16.hip: rb_bf16), x -> out; false: not served (plain bf16 and the 16-bit-activation modes only)
+bool rb_params(const VocWeights& w, const RbStage& g, int j, const float* x, float* out, RbParams& r) {
+  const auto& c = w.e->cfg;
+  if ((!w.kind && w.e->voc_precision != E2ETTS_PRECISION_BF16) || c.voc_resblock != 1 || c.voc_n_dil > RB_MAX_PAIRS) return false;
+  const size_t idx = (size_t)g.stage * c.voc_n_kernels + j;
+  r = RbParams();
+  r.x = x; r.out = out; r.n_pairs = c.voc_n_dil; r.B = g.B; r.T = (int)g.n; r.C = g.co; r.KW = c.voc_rb_kernel[j];
+  r.x_bs = r.out_bs = g.n * g.co; r.slope = 0.1f; r.act16 = w.kind;
+  for (int m = 0; m < c.voc_n_dil; ++m) {
+    r.bimg[m][0] = w.image(w.e->rb_c1[idx][m]); r.bimg[m][1] = w.image(w.e->rb_c2[idx][m]);
+    if (!r.bimg[m][0] || !r.bimg[m][1]) return false;
+    r.b1[m] = w.param(w.e->rb_c1[idx][m].b); r.b2[m] = w.param(w.e->rb_c2[idx][m].b); r.dil[m] = c.voc_rb_dil[j][m];
+  }
+  return rb_bf16_supported(r);
+}
+
+// Every ResBlock of the stage on x and their sum / num_kernels into out as ONE launch, where rb_bf16's stage form serves it (32 channels): x
+// read once, the sum written once, nothing left to join.  rq [num_kernels]: the ResBlocks' parameters in j order -- the kernel adds their
+// results as the join does, (S_0 + S_1) + S_2; all: each of them can run as a launch of its own (the caller's other rb_bf16 forms start
+// from rq), fl: their FLOPs; done: the stage has been launched.
+int whole_stage(e2etts_engine* e, const VocWeights& w, const RbStage& g, const float* x, float* out, RbParams* rq, bool& all, double& fl, bool& done) {
+  const int nk = e->cfg.voc_n_kernels;
+  all = true; fl = 0; done = false;
+  for (int j = 0; j < nk && all; ++j) {
+    all = rb_params(w, g, j, x, out, rq[j]);
+    if (all) fl += rb_bf16_flops(rq[j]);
+  }
+  if (!all || !rb_bf16_stage_supported(rq, nk)) return E2ETTS_OK;
+  char nm[48];
+  snprintf(nm, sizeof nm, "rb_%s_stage_%d", w.cls(), g.co);
+  ProfScope ps(e, nm, fl, 4.0 * w.elt() * 2.0 * g.B * (double)g.n * g.co);
+  KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
+  done = true;
+  return E2ETTS_OK;
+}
+
+int whole_stage(e2etts_engine* e, const VocWeights& w, const RbStage& g, const float* x, float* out, bool& done) {   // for a caller with no other rb_bf16 form
+  RbParams rq[E2ETTS_MAX_RB_KERNELS];
+  bool all;
+  double fl;
+  return whole_stage(e, w, g, x, out, rq, all, fl, done);
+}
+
+// Every ResBlock of the stage in one launch, each into the sum buffer of its own (rb_bufs); the sums are joined downstream.  rq, fl: of whole_stage
+int rb_group(e2etts_engine* e, const VocWeights& w, const RbStage& g, VocPass& P, const RbParams* rq, double fl) {
+  const int nk = e->cfg.voc_n_kernels;
+  RbParams gq[E2ETTS_MAX_RB_KERNELS];
+  int order[E2ETTS_MAX_RB_KERNELS];
+  rb_order(e->cfg, order);
+  double by = 0;
+  for (int t = 0; t < nk; ++t) {
+    gq[t] = rq[order[t]];
+    gq[t].out = rb_bufs(P, order[t]).S;
+    by += rb_bf16_bytes(gq[t]) * w.elt();
+  }
+  char nm[48];
+  snprintf(nm, sizeof nm, "rb_%s_group_%d", w.cls(), g.co);
+  ProfScope ps(e, nm, fl, by);
+  KCHK(e, launch_rb_bf16_group(gq, nk, e->stream));
+  return E2ETTS_OK;
+}
+
+// One ResBlock as a launch of its own, closing as cl says
+int rb_single(e2etts_engine* e, const VocWeights& w, const RbStage& g, RbParams& r, Closing cl) {
+  r.accumulate = cl.accumulate; r.out_div = cl.out_div;
+  char nm[48];
+  snprintf(nm, sizeof nm, "rb_%s_%d", w.cls(), g.co);
+  ProfScope ps(e, nm, rb_bf16_flops(r), rb_bf16_bytes(r) * w.elt());
+  KCHK(e, launch_rb_bf16(r, e->stream));
+  return E2ETTS_OK;
+}
+
+// Pair m of EVERY ResBlock of the stage in one launch, ResBlock j in its own buffers: cur[j], its running x, moves on to what the pair
+// wrote (the sum buffer after the last pair; x and out must differ, so the running x ping-pongs CUR / T1)
+int pair_group(e2etts_engine* e, const VocWeights& w, const RbStage& g, VocPass& P, int m, const int* order, const float** cur) {
+  const int nk = e->cfg.voc_n_kernels;
+  PairParams qs[E2ETTS_MAX_RB_KERNELS];
+  double fl = 0, by = 0;
+  for (int t = 0; t < nk; ++t) {
+    const int j = order[t];
+    const RbBufs b = rb_bufs(P, j);
+    PairParams& q = qs[t];
+    q = pair_params(w, g, j, m);
+    q.x = cur[j];
+    q.out = m == e->cfg.voc_n_dil - 1 ? b.S : (cur[j] == b.CUR ? b.T1 : b.CUR);
+    fl += resblock_pair_flops(q); by += resblock_pair_bytes(q) * w.elt();
+  }
+  char nm[48];
+  snprintf(nm, sizeof nm, "pair_%s_group_%d", w.cls(), g.co);
+  ProfScope ps(e, nm, fl, by);
+  KCHK(e, launch_pair_bf16_group(qs, nk, e->stream));
+  for (int t = 0; t < nk; ++t) cur[order[t]] = qs[t].out;
+  return E2ETTS_OK;
+}
+
 // HifiGan.forward in precision "bf16_act" (E2ETTS_PRECISION_BF16_ACT; the reference module after .bfloat16(), V/generator.py:37-53,
-// V/layers.py:33-40 / 59-64): every activation in HBM is bf16 [B, n, C], every step rounded as include/e2etts.h lists.  On the engine's
+// V/layers.py:33-40 / 59-64): every activation in HBM is bf16 [B, n, C], every step rounded as include/e2etts.h lists.  On the pass's
 // stream: conv_pre and the upsamplers on conv_bf16 (bf16 in / out), the ResBlocks as the fusion level asks -- 2: whole ResBlocks
 // (rb_bf16, the 32-channel stage as ONE launch with its sum), 1: fused pairs (pair_bf16), 0: two conv_bf16 launches per pair; the stage sum
 // in the ResBlocks' epilogues (S = bf16(S + rb_j), then bf16(S / num_kernels)) or, at small windows, in the next upsampler's staging (see
@@ -1450,9 +1699,10 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
 // padded batch is computed in full (no ragged row limits).  Everything the call needs is checked before the first launch.
 // Precision "fp16_act" (E2ETTS_PRECISION_FP16_ACT, the module after .half()) is the same walk with element kind 2: fp16 tensors, the fp16
 // images and fp16-rounded parameters of make_fp16_act_params, the fp16 MFMA; profile classes *_fp16_act*.
-int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& WAV, DevBuf& PCM, bool own_out) {
+int vocoder_act16(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int T) {
   const auto& c = e->cfg;
   const int kind = e->voc_precision == E2ETTS_PRECISION_FP16_ACT ? 2 : 1;
+  const VocWeights W{e, kind};
   const char* tag = kind == 2 ? "fp16" : "bf16";
   const char* conv_nm = kind == 2 ? "conv_fp16_act" : "conv_bf16_act";
   const int nk = c.voc_n_kernels, nd = c.voc_n_dil;
@@ -1465,34 +1715,13 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
   if (len != (long long)T * c.hop_length) return e->fail(E2ETTS_EINVAL, "upsample product != hop_length");
   if (len > 0x7fffffffLL / 2) return e->fail(E2ETTS_EINVAL, "utterance too long");
   // ---- parameters, and every launch's geometry, before anything is launched
-  auto img = [&](const ConvW& w, int* split) -> const void* {
-    if (kind == 2) {
-      auto ih = e->himg_of.find(w.w);
-      if (ih == e->himg_of.end()) return nullptr;
-      if (split) *split = ih->second.second;
-      return ih->second.first;
-    }
-    if (!w.wx3) return nullptr;
-    auto it = e->bimg_of.find(w.wx3);
-    if (it == e->bimg_of.end()) {
-      it = e->bimg_act.find(w.wx3);
-      if (it == e->bimg_act.end()) return nullptr;
-    }
-    if (split) *split = it->second.second;
-    return it->second.first;
-  };
-  auto r16 = [&](const float* p) -> const float* {
-    const auto& tab = kind == 2 ? e->r16h_of : e->r16_of;
-    auto it = tab.find(p);
-    return it == tab.end() ? nullptr : it->second;
-  };
   auto conv_q = [&](const ConvW& w, const void* in, int in_bf16, float in_slope, void* out, int Tn, int Cin, int Cout, int KW, int dil,
                     int pad, BConvParams& q) -> bool {
     q = BConvParams();
     int split = 0;
-    q.wimg = img(w, &split);
+    q.wimg = W.image(w, &split);
     q.in = in; q.in_bf16 = in_bf16; q.in_slope = in_slope; q.tap_split = split; q.KWe = split > 0 ? 2 : KW;
-    q.bias = r16(w.b); q.out_b = out; q.act16 = kind;
+    q.bias = W.param(w.b); q.out_b = out; q.act16 = kind;
     q.B = B; q.T = Tn; q.Cin = Cin; q.Cout = Cout; q.KW = KW; q.dil = dil; q.pad = pad;
     return q.wimg && q.bias && conv_bf16_supported(q);
   };
@@ -1512,18 +1741,17 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
           if (ok && c.voc_resblock == 1) ok = conv_q(e->rb_c2[idx][m], nullptr, 1, 1.0f, nullptr, (int)n, co, co, k, 1, (k - 1) / 2, q);
         }
     }
-    if (!ok || !r16(e->voc_post.w) || !r16(e->voc_post.b) || ch > 128 || (ch % 4))
+    if (!ok || !W.param(e->voc_post.w) || !W.param(e->voc_post.b) || ch > 128 || (ch % 4))
       return e->fail(E2ETTS_EINVAL, "precision %s_act: this vocoder (weights without %s images, or a geometry conv_bf16 does not serve at T = %d) has no %s-activation route", tag, tag, T, tag);
   }
   const size_t vb = (size_t)B * maxv * 2;
-  RET(ensure(e, e->v0, vb));
-  RET(ensure(e, e->v1, vb));
-  RET(ensure(e, e->v2, vb));
-  RET(ensure(e, e->v3, vb));
-  RET(ensure(e, WAV, (size_t)B * len * 4));
-  RET(ensure(e, PCM, (size_t)B * len * 2));
-  if (!own_out) e->have_wav = false;
-  void *S = e->v0.p, *XU = e->v1.p, *T1 = e->v2.p, *CUR = e->v3.p;
+  RET(ensure(e, P.v0, vb));
+  RET(ensure(e, P.v1, vb));
+  RET(ensure(e, P.v2, vb));
+  RET(ensure(e, P.v3, vb));
+  RET(ensure(e, P.wav, (size_t)B * len * 4));
+  RET(ensure(e, P.pcm, (size_t)B * len * 2));
+  if (P.resident) e->have_wav = false;
   auto run_conv = [&](const char* nm, const BConvParams& q, double fl) -> int {
     ProfScope ps(e, nm, fl, 2.0 * ((double)q.B * q.T * (q.Cin + q.Cout * (q.res ? 2 : 1) + (q.accumulate ? q.Cout : 0))) + 2.0 * q.KWe * q.Cin * q.Cout);
     KCHK(e, launch_conv_bf16(q, e->stream));
@@ -1535,9 +1763,17 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
   const bool small_window = nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && nk <= BC_GROUP_MAX && (long long)B * T <= 2048 && e->fuse_pairs >= 1;
   if (small_window)
     for (int j = 0; j + 1 < nk; ++j)
-      for (int k = 0; k < 3; ++k) RET(ensure(e, e->vside[j][k], vb));
+      for (int k = 0; k < 3; ++k) RET(ensure(e, P.vside[j][k], vb));
+  // (16-bit elements behind the float pointers of the parameter structs)
+  float* const XU = ptr<float>(P.v1);
+  const RbBufs mb = rb_bufs(P, 0);
+  float *const S = mb.S, *const T1 = mb.T1, *const CUR = mb.CUR;
   const float* pend_add[3] = {nullptr, nullptr, nullptr};
   float pend_div = 1.0f;
+  auto join_downstream = [&] {   // the next upsampler sums the ResBlocks' buffers while it stages its input
+    for (int j = 1; j < nk; ++j) pend_add[j - 1] = rb_bufs(P, j).S;
+    pend_div = (float)nk;
+  };
   BConvParams q;
   conv_q(e->voc_pre, mel_btc, 0, 1.0f, S, T, c.n_mel, c.voc_init_ch, 7, 1, 3, q);   // bf16(conv_pre(bf16(mel)) + b)
   RET(run_conv(conv_nm, q, 2.0 * B * (double)T * c.voc_init_ch * 7 * c.n_mel));
@@ -1553,177 +1789,99 @@ int vocoder_act16(e2etts_engine* e, const float* mel_btc, int B, int T, DevBuf& 
     RET(run_conv(conv_nm, q, 2.0 * B * (double)n * s * co * 2 * ch));
     n *= s;
     ch = co;
+    const RbStage g{i, B, co, n};
+    const bool group_ok = small_window && i + 1 < c.voc_stages;
     bool stage_done = false;
-    auto rbq = [&](int j, RbParams& r) -> bool {
-      const int idx = i * nk + j;
-      r = RbParams();
-      r.x = reinterpret_cast<const float*>(XU); r.out = reinterpret_cast<float*>(S); r.n_pairs = nd; r.B = B; r.T = (int)n; r.C = co;
-      r.KW = c.voc_rb_kernel[j]; r.x_bs = r.out_bs = n * co; r.slope = 0.1f; r.act16 = kind;
-      if (c.voc_resblock != 1 || nd > RB_MAX_PAIRS) return false;
-      for (int m = 0; m < nd; ++m) {
-        r.bimg[m][0] = img(e->rb_c1[idx][m], nullptr); r.bimg[m][1] = img(e->rb_c2[idx][m], nullptr);
-        r.b1[m] = r16(e->rb_c1[idx][m].b); r.b2[m] = r16(e->rb_c2[idx][m].b); r.dil[m] = c.voc_rb_dil[j][m];
-      }
-      return rb_bf16_supported(r);
-    };
     if (e->fuse_pairs >= 2 && nk <= BC_GROUP_MAX) {   // whole ResBlocks
       RbParams rq[E2ETTS_MAX_RB_KERNELS];
-      bool ok = true;
+      bool all = false;
       double fl = 0;
-      for (int j = 0; j < nk && ok; ++j) {
-        ok = rbq(j, rq[j]);
-        if (ok) fl += rb_bf16_flops(rq[j]);
-      }
-      if (ok && rb_bf16_stage_supported(rq, nk)) {   // the whole stage and its sum in one launch
-        char nm[48];
-        snprintf(nm, sizeof nm, "rb_%s_act_stage_%d", tag, co);
-        ProfScope ps(e, nm, fl, 2.0 * 2.0 * B * (double)n * co);
-        KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
-        stage_done = true;
-      } else if (ok && small_window && i + 1 < c.voc_stages) {   // every ResBlock in one launch, largest kernel first; joined downstream
-        void* Sj[E2ETTS_MAX_RB_KERNELS];
-        RbParams gq[E2ETTS_MAX_RB_KERNELS];
-        int order[E2ETTS_MAX_RB_KERNELS];
-        for (int j = 0; j < nk; ++j) { Sj[j] = j ? e->vside[j - 1][0].p : S; order[j] = j; }
-        std::sort(order, order + nk, [&](int a, int b2) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b2]; });
-        double by = 0;
-        for (int t = 0; t < nk; ++t) {
-          gq[t] = rq[order[t]];
-          gq[t].out = reinterpret_cast<float*>(Sj[order[t]]);
-          by += rb_bf16_bytes(gq[t]) / 2;
-        }
-        char nm[48];
-        snprintf(nm, sizeof nm, "rb_%s_act_group_%d", tag, co);
-        ProfScope ps(e, nm, fl, by);
-        KCHK(e, launch_rb_bf16_group(gq, nk, e->stream));
-        for (int j = 1; j < nk; ++j) pend_add[j - 1] = reinterpret_cast<const float*>(Sj[j]);
-        pend_div = (float)nk;
-        stage_done = true;
-      } else if (ok) {
-        for (int j = 0; j < nk; ++j) {
-          rq[j].accumulate = j > 0;
-          if (j > 0 && j == nk - 1) rq[j].out_div = (float)nk;
-          char nm[48];
-          snprintf(nm, sizeof nm, "rb_%s_act_%d", tag, co);
-          ProfScope ps(e, nm, rb_bf16_flops(rq[j]), rb_bf16_bytes(rq[j]) / 2);
-          KCHK(e, launch_rb_bf16(rq[j], e->stream));
+      RET(whole_stage(e, W, g, XU, S, rq, all, fl, stage_done));
+      if (!stage_done && all) {
+        if (group_ok) {   // every ResBlock in one launch, largest kernel first; joined downstream
+          RET(rb_group(e, W, g, P, rq, fl));
+          join_downstream();
+        } else {
+          for (int j = 0; j < nk; ++j) RET(rb_single(e, W, g, rq[j], closing(j, true, nk, false)));
         }
         stage_done = true;
       }
     }
-    if (!stage_done && small_window && i + 1 < c.voc_stages && c.voc_resblock == 1) {   // pair m of every ResBlock in one launch
+    if (!stage_done && group_ok && c.voc_resblock == 1) {   // pair m of every ResBlock in one launch
       bool ok = true;
-      PairParams gq[E2ETTS_MAX_RB_KERNELS];
-      const void* curj[E2ETTS_MAX_RB_KERNELS];
-      void *Sj[E2ETTS_MAX_RB_KERNELS], *T1j[E2ETTS_MAX_RB_KERNELS], *CURj[E2ETTS_MAX_RB_KERNELS];
-      int order[E2ETTS_MAX_RB_KERNELS];
-      for (int j = 0; j < nk; ++j) {
-        Sj[j] = j ? e->vside[j - 1][0].p : S; T1j[j] = j ? e->vside[j - 1][1].p : T1; CURj[j] = j ? e->vside[j - 1][2].p : CUR;
-        curj[j] = XU; order[j] = j;
-      }
-      std::sort(order, order + nk, [&](int a, int b2) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b2]; });
-      auto member = [&](int j, int m, PairParams& pq) {
-        const int idx = i * nk + j;
-        pq = PairParams();
-        pq.x = reinterpret_cast<const float*>(curj[j]);
-        pq.out = reinterpret_cast<float*>(m == nd - 1 ? Sj[j] : (curj[j] == CURj[j] ? T1j[j] : CURj[j]));
-        pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
-        pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
-        pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = c.voc_rb_kernel[j]; pq.dil = c.voc_rb_dil[j][m]; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
-        pq.mode = kind == 2 ? 4 : 3;
-      };
       for (int j = 0; j < nk && ok; ++j)   // every member of every launch servable: decided before anything is launched
-        for (int m = 0; m < nd && ok; ++m) {
-          PairParams pq;
-          member(j, m, pq);
-          ok = pair_bf16_supported(pq);
-        }
-      for (int m = 0; m < nd && ok; ++m) {
-        double fl = 0, by = 0;
-        for (int t = 0; t < nk; ++t) {
-          member(order[t], m, gq[t]);
-          fl += resblock_pair_flops(gq[t]); by += resblock_pair_bytes(gq[t]) / 2;
-        }
-        char nm[48];
-        snprintf(nm, sizeof nm, "pair_%s_act_group_%d", tag, co);
-        ProfScope ps(e, nm, fl, by);
-        KCHK(e, launch_pair_bf16_group(gq, nk, e->stream));
-        for (int t = 0; t < nk; ++t) curj[order[t]] = gq[t].out;
-      }
+        for (int m = 0; m < nd && ok; ++m) ok = pair_bf16_supported(pair_params(W, g, j, m));
       if (ok) {
-        for (int j = 1; j < nk; ++j) pend_add[j - 1] = reinterpret_cast<const float*>(Sj[j]);
-        pend_div = (float)nk;
+        const float* curj[E2ETTS_MAX_RB_KERNELS];
+        int order[E2ETTS_MAX_RB_KERNELS];
+        for (int j = 0; j < nk; ++j) curj[j] = XU;
+        rb_order(c, order);
+        for (int m = 0; m < nd; ++m) RET(pair_group(e, W, g, P, m, order, curj));
+        join_downstream();
         stage_done = true;
       }
     }
     for (int j = 0; j < nk && !stage_done; ++j) {
       const int idx = i * nk + j, k = c.voc_rb_kernel[j];
-      const void* cur = XU;
+      const float* cur = XU;
       for (int m = 0; m < nd; ++m) {
         const int d = c.voc_rb_dil[j][m];
         const bool last = m == nd - 1;
-        const int acc = last && j > 0 ? 1 : 0;
-        const float div = last && j > 0 && j == nk - 1 ? (float)nk : 1.0f;
+        const Closing cl = closing(j, last, nk, false);
         if (c.voc_resblock == 2) {   // x = bf16(bf16(c(bf16(lrelu(x))) + b) + x); never in place (neighbouring rows are still read)
-          void* out = last ? S : (cur == CUR ? T1 : CUR);
+          float* out = last ? S : (cur == CUR ? T1 : CUR);
           conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, out, (int)n, co, co, k, d, (k * d - d) / 2, q);
-          q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
+          q.res = cur; q.accumulate = cl.accumulate; q.out_div = cl.out_div;
           RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
           cur = out;
           continue;
         }
         PairParams pq;
         if (e->fuse_pairs >= 1) {
-          pq.x = reinterpret_cast<const float*>(cur); pq.out = reinterpret_cast<float*>(last ? S : (cur == CUR ? T1 : CUR));
-          pq.b1 = r16(e->rb_c1[idx][m].b); pq.b2 = r16(e->rb_c2[idx][m].b);
-          pq.bimg1 = img(e->rb_c1[idx][m], nullptr); pq.bimg2 = img(e->rb_c2[idx][m], nullptr);
-          pq.B = B; pq.T = (int)n; pq.C = co; pq.KW = k; pq.dil = d; pq.x_bs = pq.out_bs = n * co; pq.slope = 0.1f;
-          pq.mode = kind == 2 ? 4 : 3; pq.accumulate = acc; pq.out_div = div;
+          pq = pair_params(W, g, j, m);
+          pq.x = cur; pq.out = last ? S : (cur == CUR ? T1 : CUR);
+          pq.accumulate = cl.accumulate; pq.out_div = cl.out_div;
         }
         if (e->fuse_pairs >= 1 && pair_bf16_supported(pq)) {
           char nm[48];
-          snprintf(nm, sizeof nm, "pair_%s_act_%d", tag, co);
-          ProfScope ps(e, nm, resblock_pair_flops(pq), resblock_pair_bytes(pq) / 2);
+          snprintf(nm, sizeof nm, "pair_%s_%d", W.cls(), co);
+          ProfScope ps(e, nm, resblock_pair_flops(pq), resblock_pair_bytes(pq) * W.elt());
           KCHK(e, launch_pair_bf16(pq, e->stream));
           cur = pq.out;
           continue;
         }
         // two launches: xt = bf16(lrelu(bf16(c1 + b1))) handed over in bf16, then x = bf16(bf16(c2(xt) + b2) + x) (conv2 may write over x:
         // its slab reads xt, and each output row reads only its own residual row -- but never over the stage input XU)
-        void* mid = cur == T1 ? CUR : T1;
-        void* out = last ? S : (cur == XU ? (mid == T1 ? CUR : T1) : const_cast<void*>(cur));
-        conv_q(e->rb_c1[idx][m], cur, 1, 0.1f, mid, (int)n, co, co, k, d, (k * d - d) / 2, q);
-        q.act_slope = 0.1f;
+        float* mid = cur == T1 ? CUR : T1;
+        float* out = last ? S : (cur == XU ? (mid == T1 ? CUR : T1) : const_cast<float*>(cur));
+        BConvParams q2;
+        handover_params(W, g, j, m, cur, mid, out, q, q2);
+        q2.accumulate = cl.accumulate; q2.out_div = cl.out_div;
         RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
-        conv_q(e->rb_c2[idx][m], mid, 1, 1.0f, out, (int)n, co, co, k, 1, (k - 1) / 2, q);
-        q.res = reinterpret_cast<const float*>(cur); q.accumulate = acc; q.out_div = div;
-        RET(run_conv(conv_nm, q, 2.0 * B * (double)n * co * k * co));
+        RET(run_conv(conv_nm, q2, 2.0 * B * (double)n * co * k * co));
         cur = out;
       }
     }
   }
   {
     ProfScope ps(e, kind == 2 ? "conv_post_fp16_act" : "conv_post_bf16", 2.0 * B * (double)n * 7 * ch, (double)B * n * (ch * 2.0 + 6.0));
-    KCHK(e, launch_conv_post_bf16(S, r16(e->voc_post.w), r16(e->voc_post.b), ptr<float>(WAV), ptr<int16_t>(PCM), B, n, (int)ch, 7, e->stream, kind == 2));
+    KCHK(e, launch_conv_post_bf16(S, W.param(e->voc_post.w), W.param(e->voc_post.b), ptr<float>(P.wav), ptr<int16_t>(P.pcm), B, n, (int)ch, 7, e->stream, kind == 2));
   }
-  if (!own_out) {
+  if (P.resident) {
     e->voc_B = B; e->voc_T = T;
     e->have_wav = true;
   }
   return E2ETTS_OK;
 }
 
-// HifiGan.forward (V/generator.py:37-53) on channels-last mel [B, T, n_mel] already in HBM
-int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want_wav, bool want_pcm, const int32_t* ragged_lens = nullptr,
-                 const int64_t* ragged_lens_host = nullptr, DevBuf* out_wav = nullptr, DevBuf* out_pcm = nullptr) {
-  // out_wav / out_pcm: the streaming path's slot buffers; the resident one-shot result (e->wav, e->pcm, have_wav) is then left alone
-  const bool own_out = out_wav != nullptr;
-  DevBuf& WAV = own_out ? *out_wav : e->wav;
-  DevBuf& PCM = own_out ? *out_pcm : e->pcm;
+// HifiGan.forward (V/generator.py:37-53) on channels-last mel [B, T, n_mel] already in HBM, in the working set P; the engine is enqueuing
+// on P.stream (e->stream == P.stream: a slot's pass runs inside an OnStream)
+int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int T, const int32_t* ragged_lens = nullptr,
+                 const int64_t* ragged_lens_host = nullptr) {
   const auto& c = e->cfg;
   if (!e->voc_loaded) return e->fail(E2ETTS_ESTATE, "vocoder weights not loaded");
   if (B <= 0 || T <= 0) return e->fail(E2ETTS_EINVAL, "B and T must be positive");
-  if (e->voc_precision == E2ETTS_PRECISION_BF16_ACT || e->voc_precision == E2ETTS_PRECISION_FP16_ACT) return vocoder_act16(e, mel_btc, B, T, WAV, PCM, own_out);   // (ragged limits unused)
+  if (e->voc_precision == E2ETTS_PRECISION_BF16_ACT || e->voc_precision == E2ETTS_PRECISION_FP16_ACT) return vocoder_act16(e, P, mel_btc, B, T);   // (ragged limits unused)
   // largest activation of any stage, in floats per utterance
   long long len = T, ch = c.voc_init_ch;
   long long maxv = len * ch;
@@ -1738,39 +1896,26 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
   if (nsamp != (long long)T * c.hop_length) return e->fail(E2ETTS_EINVAL, "upsample product != hop_length");
   if (istft) maxv += ch;  // the reflection-padded frame (the tail itself is always computed in full: it is 18 channels wide)
   const size_t vb = (size_t)B * maxv * 4;
-  RET(ensure(e, e->v0, vb));
-  RET(ensure(e, e->v1, vb));
-  RET(ensure(e, e->v2, vb));
-  RET(ensure(e, e->v3, vb));
-  RET(ensure(e, WAV, (size_t)B * nsamp * 4));
-  RET(ensure(e, PCM, (size_t)B * nsamp * 2));
-  if (!own_out) e->have_wav = false;
-  float *S = ptr<float>(e->v0), *XU = ptr<float>(e->v1), *T1 = ptr<float>(e->v2), *CUR = ptr<float>(e->v3);
+  RET(ensure(e, P.v0, vb));
+  RET(ensure(e, P.v1, vb));
+  RET(ensure(e, P.v2, vb));
+  RET(ensure(e, P.v3, vb));
+  RET(ensure(e, P.wav, (size_t)B * nsamp * 4));
+  RET(ensure(e, P.pcm, (size_t)B * nsamp * 2));
+  if (P.resident) e->have_wav = false;
+  float* const XU = ptr<float>(P.v1);
+  const RbBufs mb = rb_bufs(P, 0);
+  float *const S = mb.S, *const T1 = mb.T1, *const CUR = mb.CUR;
+  const VocTuning& tune = voc_tuning();
+  const VocWeights W{e, 0};
 
   // weight selection: split-precision image when requested and present, else fp32
   auto setw = [&](ConvParams& q, const ConvW& w) {
     q.bias = w.b;
     if (e->voc_precision != E2ETTS_PRECISION_FP32 && w.wx3) { q.w = w.wx3; q.x3 = e->voc_precision; }
     else { q.w = w.w; q.x3 = 0; }
-    if (q.x3 == E2ETTS_PRECISION_BF16) {   // plain bf16: the same weights in conv_bf16.hip's order (the router in conv() decides)
-      auto it = e->bimg_of.find(w.wx3);
-      if (it != e->bimg_of.end()) { q.bimg = it->second.first; q.bimg_tap_split = it->second.second; }
-    }
-  };
-  // plain bf16: a whole ResBlock1 of stage `stage`, kernel index j, as ONE launch (conv_bf16.hip: rb_bf16) where that applies
-  auto rb_params = [&](int stage, int j, int co, long long n, const float* x, float* out, RbParams& q) -> bool {
-    if (e->voc_precision != E2ETTS_PRECISION_BF16 || c.voc_resblock != 1 || c.voc_n_dil > RB_MAX_PAIRS) return false;
-    const int idx = stage * c.voc_n_kernels + j;
-    q = RbParams();
-    q.x = x; q.out = out; q.n_pairs = c.voc_n_dil; q.B = B; q.T = (int)n; q.C = co; q.KW = c.voc_rb_kernel[j];
-    q.x_bs = q.out_bs = n * co; q.slope = 0.1f;
-    for (int m = 0; m < c.voc_n_dil; ++m) {
-      auto i1 = e->bimg_of.find(e->rb_c1[idx][m].wx3), i2 = e->bimg_of.find(e->rb_c2[idx][m].wx3);
-      if (i1 == e->bimg_of.end() || i2 == e->bimg_of.end()) return false;
-      q.bimg[m][0] = i1->second.first; q.bimg[m][1] = i2->second.first;
-      q.b1[m] = e->rb_c1[idx][m].b; q.b2[m] = e->rb_c2[idx][m].b; q.dil[m] = c.voc_rb_dil[j][m];
-    }
-    return rb_bf16_supported(q);
+    // plain bf16: the same weights in conv_bf16.hip's order (the router in conv() decides)
+    if (const void* im = W.image(w, &q.bimg_tap_split)) q.bimg = im;
   };
   // Ragged mode: the layers of stage i compute rows < mel_len * rate_i + halo_i only (host_logic.h: vocoder_stage_halo_rows -- the
   // reach of what is still to come, in that stage's rows: 12 frames after conv_pre, 76 / 109 / 94 / 63 rows in the four stages of
@@ -1805,50 +1950,50 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
   }
   // Small batches (the B = 1 latency path): the ResBlocks of a stage are independent until their sum (V/generator.py:44-48), and one
   // ResBlock's launches -- 384 tiles on 256 CUs at B = 1, chains of 40-70 us kernels -- leave CUs idle at every tail.  They run side by
-  // side: ResBlock 0 on the engine's stream into S, ResBlock j > 0 on a side stream into a sum buffer of its own, joined by
+  // side: ResBlock 0 on the pass's stream into S, ResBlock j > 0 on a side stream into a sum buffer of its own, joined by
   // S = (S + S_j) [/ num_kernels] in the accumulating epilogue's order -- same operations, same bits.  Off while the full class profile is taken
   // and above E2ETTS_VOC_CONC_FRAMES frames (default 2 048; 4 096 in exact fp32), where every launch fills the chip.
   // (measured per batch size and mode: bf16x3 gains up to B = 2 at T = 768 and loses 1-2 % from B = 4, exact fp32 still gains 2 % at
   // B = 4 and loses from B = 8; a per-stage limit on the tile count instead showed nothing beyond noise)
-  static const long long conc_env = getenv("E2ETTS_VOC_CONC_FRAMES") ? atoll(getenv("E2ETTS_VOC_CONC_FRAMES")) : -1;
-  const long long conc_frames = conc_env >= 0 ? conc_env : (e->voc_precision == E2ETTS_PRECISION_FP32 ? 4096 : 2048);
-  const int nk = c.voc_n_kernels;
+  const long long conc_frames = tune.conc_frames >= 0 ? tune.conc_frames : (e->voc_precision == E2ETTS_PRECISION_FP32 ? 4096 : 2048);
+  const int nk = c.voc_n_kernels, nd = c.voc_n_dil;
   // (a profile of ALL classes wants one kernel at a time; a profile filtered to one class -- bench.py's timed region -- records its
   // events on whichever stream the launch goes to and is fine)
   const bool full_profile = e->prof_on && e->prof_filter.empty();
   // Plain bf16 at such sizes goes one step further (conv_bf16.hip: launch_*_group): pair m of ALL ResBlocks of the stage is ONE launch on
-  // the engine's stream -- a third of the launches, no fork / join events, and a grid the three kernel sizes fill together (one ResBlock's
+  // the pass's stream -- a third of the launches, no fork / join events, and a grid the three kernel sizes fill together (one ResBlock's
   // pair is 1.15 rounds of workgroups at a 542-frame window, the k = 11 stream the critical path of every stage, and the host needed
   // longer to enqueue three streams' launches than the GPU to run them).  Each ResBlock keeps its own buffers as on the side streams,
   // and the join below is the same: same bits.  E2ETTS_VOC_GROUP=0 (tuning aid) keeps the streams.
-  static const bool group_env = !(getenv("E2ETTS_VOC_GROUP") && atoi(getenv("E2ETTS_VOC_GROUP")) == 0);
   const bool small_window = nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && nk <= BC_GROUP_MAX && (long long)B * T <= conc_frames;
-  const bool group_mode = group_env && small_window && e->voc_precision == E2ETTS_PRECISION_BF16 && !ragged_lens && c.voc_resblock == 1 && e->fuse_pairs;
+  const bool group_mode = tune.group && small_window && e->voc_precision == E2ETTS_PRECISION_BF16 && !ragged_lens && c.voc_resblock == 1 && e->fuse_pairs;
   // A pass in a stream slot (e2etts_vocoder_stream_push) overlaps with the other slot's pass instead: side streams of its own would only
-  // crowd the process's four hardware queues (E2ETTS_STREAM_SIDE=1, tuning aid, keeps them).
-  static const bool side_in_slot = getenv("E2ETTS_STREAM_SIDE") && atoi(getenv("E2ETTS_STREAM_SIDE")) != 0;
+  // crowd the process's four hardware queues (E2ETTS_STREAM_SIDE=1, tuning aid, keeps them); the calibration pass has none either.
   const bool conc = (!full_profile || group_mode) && nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && (long long)B * T <= conc_frames &&
-                    (!own_out || side_in_slot || group_mode);
-  if (conc) {
+                    (P.resident || tune.stream_side || group_mode);
+  if (conc)
+    for (int j = 0; j + 1 < nk; ++j)
+      for (int k = 0; k < 3; ++k) RET(ensure(e, P.vside[j][k], vb));
+  // the pass's side streams and events, made when a stage first forks: a pass whose stages all run grouped never owns any
+  auto side_streams = [&]() -> int {
     for (int j = 0; j + 1 < nk; ++j) {
-      if (!e->side[j]) HIPCHK(e, hipStreamCreateWithFlags(&e->side[j], hipStreamNonBlocking));
-      if (!e->ev_join[j]) HIPCHK(e, hipEventCreateWithFlags(&e->ev_join[j], hipEventDisableTiming));
-      for (int k = 0; k < 3; ++k) RET(ensure(e, e->vside[j][k], vb));
+      if (!P.side[j]) HIPCHK(e, hipStreamCreateWithFlags(&P.side[j], hipStreamNonBlocking));
+      if (!P.ev_join[j]) HIPCHK(e, hipEventCreateWithFlags(&P.ev_join[j], hipEventDisableTiming));
     }
-    if (!e->ev_fork) HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-  }
-  hipStream_t const main_stream = e->stream;
+    if (!P.ev_fork) HIPCHK(e, hipEventCreateWithFlags(&P.ev_fork, hipEventDisableTiming));
+    return E2ETTS_OK;
+  };
   // A failure between a stage's fork and its join must not leave ResBlocks queued on the side streams: the next call could overwrite
   // XU or vside[*] -- or ensure() free them -- under work still in flight.  Whatever path leaves this function while
   // `armed`, the side streams are drained first.
   struct SideDrain {
-    e2etts_engine* e; int n; bool armed;
+    VocPass& P; int n; bool armed;
     ~SideDrain() {
       if (!armed) return;
       for (int j = 0; j < n; ++j)
-        if (e->side[j]) (void)hipStreamSynchronize(e->side[j]);
+        if (P.side[j]) (void)hipStreamSynchronize(P.side[j]);
     }
-  } drain{e, conc ? nk - 1 : 0, false};
+  } drain{P, conc ? nk - 1 : 0, false};
   ConvParams p;
   p.B = B; p.T = T; p.act_rows = act_stage[0]; p.act_rows_host = act_stage_h[0]; p.act_frac = vfs[0]; p.in = mel_btc; setw(p, e->voc_pre); p.out = S; p.Cin = c.n_mel; p.Cout = c.voc_init_ch;
   p.KW = 7; p.pad = 3;
@@ -1880,185 +2025,97 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
     n *= s;
     ch = co;
     if (n > 0x7fffffffLL / 2) return e->fail(E2ETTS_EINVAL, "utterance too long");
+    const RbStage g{i, B, co, n};
     // ---- grouped launches (see group_mode above): pair m of every ResBlock in one launch; at 256 channels, where a pair runs as two
     // convolutions with a bf16 hand-over, conv1 of every ResBlock and then conv2 of every ResBlock
     bool grouped_stage = false;
     bool joined_in_kernel = false;   // the stage's launch already wrote (S_0 + S_1 + ...) / n to S
     if (group_mode) {
-      float* Sj[E2ETTS_MAX_RB_KERNELS]; float* T1j[E2ETTS_MAX_RB_KERNELS]; float* CURj[E2ETTS_MAX_RB_KERNELS];
-      int order[E2ETTS_MAX_RB_KERNELS];   // dispatch order inside a launch: largest kernel size first
-      for (int j = 0; j < nk; ++j) {
-        Sj[j] = j ? ptr<float>(e->vside[j - 1][0]) : S; T1j[j] = j ? ptr<float>(e->vside[j - 1][1]) : T1; CURj[j] = j ? ptr<float>(e->vside[j - 1][2]) : CUR;
-        order[j] = j;
-      }
-      std::sort(order, order + nk, [&](int a, int b2) { return c.voc_rb_kernel[a] > c.voc_rb_kernel[b2]; });
+      int order[E2ETTS_MAX_RB_KERNELS];
+      rb_order(c, order);
       bool as_pairs = co <= 128;
-      if (co == 256) {   // fused pairs at 256 channels too where conv_bf16.hip has them (eight-wavefront workgroups)
-        PairParams q;
-        q.x = XU; q.out = Sj[0]; q.B = B; q.T = (int)n; q.C = co; q.KW = c.voc_rb_kernel[0]; q.dil = 1; q.x_bs = q.out_bs = (long long)n * co; q.mode = 2;
-        const int idx0 = i * nk;
-        auto i1 = e->bimg_of.find(e->rb_c1[idx0][0].wx3), i2 = e->bimg_of.find(e->rb_c2[idx0][0].wx3);
-        if (i1 != e->bimg_of.end() && i2 != e->bimg_of.end()) { q.bimg1 = i1->second.first; q.bimg2 = i2->second.first; as_pairs = pair_bf16_supported(q); }
-      }
+      // fused pairs at 256 channels too where conv_bf16.hip has them (eight-wavefront workgroups).  Asked of pair (0, 0) as it is: should its
+      // dilation be out of pair_bf16's reach, the hand-over form is probed below and fails on the same halo limit -- the stage is not grouped
+      if (co == 256) as_pairs = pair_bf16_supported(pair_params(W, g, 0, 0));
       // 32 / 64 channels: the WHOLE ResBlock of every kernel size in one launch (these stages' tensors, 35 MB per 542-frame window at 48 kHz,
-      // stream through the Infinity Cache: pair by pair each is read twice and written once per pair)
-      if (e->fuse_pairs >= 2) {   // ... and, where one workgroup can hold it (32 channels), ALL the ResBlocks of the stage and their sum
+      // stream through the Infinity Cache: pair by pair each is read twice and written once per pair) ... and, where one workgroup can
+      // hold it (32 channels), ALL the ResBlocks of the stage and their sum
+      if (e->fuse_pairs >= 2) {
         RbParams rq[E2ETTS_MAX_RB_KERNELS];
-        bool st_ok = true;
+        bool all = false;
         double fl = 0;
-        for (int j = 0; j < nk && st_ok; ++j) {   // in j order: the kernel adds the ResBlocks' results as the join does, (S_0 + S_1) + S_2
-          st_ok = rb_params(i, j, co, n, XU, S, rq[j]);
-          if (st_ok) fl += rb_bf16_flops(rq[j]);
-        }
-        if (st_ok && rb_bf16_stage_supported(rq, nk)) {
-          char nm[48];
-          snprintf(nm, sizeof nm, "rb_bf16_stage_%d", co);
-          ProfScope ps(e, nm, fl, 4.0 * 2.0 * B * (double)n * co);
-          KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
-          grouped_stage = true;
-          joined_in_kernel = true;
-        }
-      }
-      if (!grouped_stage) {
-        RbParams rq[E2ETTS_MAX_RB_KERNELS];
-        bool rb_ok = e->fuse_pairs >= 2;
-        double fl = 0, by = 0;
-        for (int t = 0; t < nk && rb_ok; ++t) {
-          rb_ok = rb_params(i, order[t], co, n, XU, Sj[order[t]], rq[t]);
-          if (rb_ok) { fl += rb_bf16_flops(rq[t]); by += rb_bf16_bytes(rq[t]); }
-        }
-        if (rb_ok) {
-          char nm[48];
-          snprintf(nm, sizeof nm, "rb_bf16_group_%d", co);
-          ProfScope ps(e, nm, fl, by);
-          KCHK(e, launch_rb_bf16_group(rq, nk, e->stream));
-          grouped_stage = true;
-        }
+        RET(whole_stage(e, W, g, XU, S, rq, all, fl, joined_in_kernel));
+        if (!joined_in_kernel && all) RET(rb_group(e, W, g, P, rq, fl));
+        grouped_stage = joined_in_kernel || all;
       }
       // every member of every launch must be servable: decided before anything is launched
       bool ok = !grouped_stage;
       for (int j = 0; j < nk && ok; ++j)
-        for (int m = 0; m < c.voc_n_dil && ok; ++m) {
-          const int idx = i * nk + j;
-          auto i1 = e->bimg_of.find(e->rb_c1[idx][m].wx3), i2 = e->bimg_of.find(e->rb_c2[idx][m].wx3);
-          ok = i1 != e->bimg_of.end() && i2 != e->bimg_of.end();
-          if (!ok) break;
+        for (int m = 0; m < nd && ok; ++m) {
           if (as_pairs) {
-            PairParams q;
-            q.x = XU; q.out = Sj[j]; q.b1 = e->rb_c1[idx][m].b; q.b2 = e->rb_c2[idx][m].b; q.bimg1 = i1->second.first; q.bimg2 = i2->second.first;
-            q.B = B; q.T = (int)n; q.C = co; q.KW = c.voc_rb_kernel[j]; q.dil = c.voc_rb_dil[j][m]; q.x_bs = q.out_bs = (long long)n * co; q.mode = 2;
-            ok = pair_bf16_supported(q);
+            ok = pair_bf16_supported(pair_params(W, g, j, m));
           } else {
-            BConvParams q;
-            q.in = XU; q.wimg = i1->second.first; q.KWe = q.KW = c.voc_rb_kernel[j]; q.dil = c.voc_rb_dil[j][m]; q.pad = (q.KW * q.dil - q.dil) / 2;
-            q.out_b = T1j[j]; q.B = B; q.T = (int)n; q.Cin = q.Cout = co;
-            ok = conv_bf16_supported(q);
+            const RbBufs b = rb_bufs(P, j);
+            BConvParams a, z;
+            handover_params(W, g, j, m, XU, b.T1, b.S, a, z);
+            ok = a.wimg && z.wimg && conv_bf16_supported(a);
           }
         }
       if (ok) {
         grouped_stage = true;
         const float* curj[E2ETTS_MAX_RB_KERNELS];
         for (int j = 0; j < nk; ++j) curj[j] = XU;
-        for (int m = 0; m < c.voc_n_dil; ++m) {
-          const bool last = m == c.voc_n_dil - 1;
+        for (int m = 0; m < nd; ++m) {
           if (as_pairs) {
-            PairParams qs[E2ETTS_MAX_RB_KERNELS];
-            double fl = 0, by = 0;
-            for (int t = 0; t < nk; ++t) {
-              const int j = order[t], idx = i * nk + j;
-              PairParams& q = qs[t];
-              q = PairParams();
-              q.x = curj[j]; q.b1 = e->rb_c1[idx][m].b; q.b2 = e->rb_c2[idx][m].b;
-              q.bimg1 = e->bimg_of[e->rb_c1[idx][m].wx3].first; q.bimg2 = e->bimg_of[e->rb_c2[idx][m].wx3].first;
-              q.out = last ? Sj[j] : (curj[j] == CURj[j] ? T1j[j] : CURj[j]);   // x and out must differ: the running x ping-pongs CUR / T1
-              q.B = B; q.T = (int)n; q.C = co; q.KW = c.voc_rb_kernel[j]; q.dil = c.voc_rb_dil[j][m];
-              q.x_bs = q.out_bs = (long long)n * co; q.slope = 0.1f; q.mode = 2;
-              fl += resblock_pair_flops(q); by += resblock_pair_bytes(q);
-            }
-            char nm[48];
-            snprintf(nm, sizeof nm, "pair_bf16_group_%d", co);
-            ProfScope ps(e, nm, fl, by);
-            KCHK(e, launch_pair_bf16_group(qs, nk, e->stream));
-            for (int t = 0; t < nk; ++t) curj[order[t]] = qs[t].out;
-          } else {
-            BConvParams q1[E2ETTS_MAX_RB_KERNELS], q2[E2ETTS_MAX_RB_KERNELS];
-            double fl = 0, by = 0;
-            for (int t = 0; t < nk; ++t) {
-              const int j = order[t], idx = i * nk + j;
-              const int k = c.voc_rb_kernel[j], d = c.voc_rb_dil[j][m];
-              BConvParams& a = q1[t];   // xt = lrelu(c1(lrelu(x)) + b1), handed over as conv2's bf16 operand (V/layers.py:35-38)
-              a = BConvParams();
-              a.in = curj[j]; a.in_slope = 0.1f; a.wimg = e->bimg_of[e->rb_c1[idx][m].wx3].first; a.KWe = a.KW = k; a.dil = d; a.pad = (k * d - d) / 2;
-              a.bias = e->rb_c1[idx][m].b; a.act_slope = 0.1f; a.out_b = T1j[j]; a.B = B; a.T = (int)n; a.Cin = a.Cout = co;
-              BConvParams& z = q2[t];   // x = c2(xt) + x (:38-39)
-              z = BConvParams();
-              z.in = T1j[j]; z.in_bf16 = 1; z.wimg = e->bimg_of[e->rb_c2[idx][m].wx3].first; z.KWe = z.KW = k; z.dil = 1; z.pad = (k - 1) / 2;
-              z.bias = e->rb_c2[idx][m].b; z.res = curj[j]; z.out = last ? Sj[j] : CURj[j]; z.B = B; z.T = (int)n; z.Cin = z.Cout = co;
-              fl += 2.0 * B * (double)n * co * k * co; by += 4.0 * ((double)B * n * co * 2.0 + (double)co * k * co);
-            }
-            char nm[48];
-            snprintf(nm, sizeof nm, "conv_bf16_group_%d", co);
-            {
-              ProfScope ps(e, nm, fl, by);
-              KCHK(e, launch_conv_bf16_group(q1, nk, e->stream));
-            }
-            {
-              ProfScope ps(e, nm, fl, by * 1.5);
-              KCHK(e, launch_conv_bf16_group(q2, nk, e->stream));
-            }
-            for (int t = 0; t < nk; ++t) curj[order[t]] = q2[t].out;
+            RET(pair_group(e, W, g, P, m, order, curj));
+            continue;
           }
+          BConvParams q1[E2ETTS_MAX_RB_KERNELS], q2[E2ETTS_MAX_RB_KERNELS];
+          double fl = 0, by = 0;
+          for (int t = 0; t < nk; ++t) {
+            const int j = order[t], k = c.voc_rb_kernel[j];
+            const RbBufs b = rb_bufs(P, j);
+            handover_params(W, g, j, m, curj[j], b.T1, m == nd - 1 ? b.S : b.CUR, q1[t], q2[t]);
+            fl += 2.0 * B * (double)n * co * k * co; by += 4.0 * ((double)B * n * co * 2.0 + (double)co * k * co);
+          }
+          char nm[48];
+          snprintf(nm, sizeof nm, "conv_bf16_group_%d", co);
+          {
+            ProfScope ps(e, nm, fl, by);
+            KCHK(e, launch_conv_bf16_group(q1, nk, e->stream));
+          }
+          {
+            ProfScope ps(e, nm, fl, by * 1.5);
+            KCHK(e, launch_conv_bf16_group(q2, nk, e->stream));
+          }
+          for (int t = 0; t < nk; ++t) curj[order[t]] = q2[t].out;
         }
       }
     }
     if (conc && !grouped_stage) {  // fork: the side streams may start once the upsampler's output (and everything before it) is complete
-      HIPCHK(e, hipEventRecord(e->ev_fork, main_stream));
+      RET(side_streams());
+      HIPCHK(e, hipEventRecord(P.ev_fork, P.stream));
       drain.armed = true;
-      for (int j = 0; j + 1 < nk; ++j) HIPCHK(e, hipStreamWaitEvent(e->side[j], e->ev_fork, 0));
+      for (int j = 0; j + 1 < nk; ++j) HIPCHK(e, hipStreamWaitEvent(P.side[j], P.ev_fork, 0));
     }
-    float* const S_main = S;
-    float* const T1_main = T1;
-    float* const CUR_main = CUR;
     // Side by side, the ResBlocks are ENQUEUED last one first: at small windows (a 542-frame streaming window's 256-channel stage: six
     // launches of ~15 us per ResBlock) the host needs longer to enqueue a ResBlock's launches than the GPU to run them, so the stream
     // enqueued last starts late by the others' enqueue time -- and the last ResBlock has the largest kernel size, the stage's critical
     // path.  Which stream a ResBlock runs on, and every result bit, are unchanged.
     // Large grids, plain bf16, padded batch: the stage form of rb_bf16 (every ResBlock of the stage and their sum per workgroup: x read once,
     // the sum written once) where it exists (32 channels) -- there these stages run on the HBM roofline as pair launches.
-    bool whole_stage = false;
-    {
-      static const int stage_env = getenv("E2ETTS_BRB_STAGE_BIG") ? atoi(getenv("E2ETTS_BRB_STAGE_BIG")) : 1;   // tuning aid
-      if (stage_env && !grouped_stage && !conc && e->fuse_pairs >= 2 && !act_stage[i + 1] && nk <= BC_GROUP_MAX) {
-        RbParams rq[E2ETTS_MAX_RB_KERNELS];
-        bool st_ok = true;
-        double fl = 0;
-        for (int j = 0; j < nk && st_ok; ++j) {
-          st_ok = rb_params(i, j, co, n, XU, S, rq[j]);
-          if (st_ok) fl += rb_bf16_flops(rq[j]);
-        }
-        if (st_ok && rb_bf16_stage_supported(rq, nk)) {
-          char nm[48];
-          snprintf(nm, sizeof nm, "rb_bf16_stage_%d", co);
-          ProfScope ps(e, nm, fl, 4.0 * 2.0 * B * (double)n * co);
-          KCHK(e, launch_rb_bf16_stage(rq, nk, e->stream));
-          whole_stage = true;
-        }
-      }
-    }
-    for (int jj = 0; jj < c.voc_n_kernels && !grouped_stage && !whole_stage; ++jj) {
-      const int j = conc ? c.voc_n_kernels - 1 - jj : jj;
-      const int idx = i * c.voc_n_kernels + j;
+    bool whole_stage_done = false;
+    if (tune.brb_stage_big && !grouped_stage && !conc && e->fuse_pairs >= 2 && !act_stage[i + 1] && nk <= BC_GROUP_MAX)
+      RET(whole_stage(e, W, g, XU, S, whole_stage_done));
+    for (int jj = 0; jj < nk && !grouped_stage && !whole_stage_done; ++jj) {
+      const int j = conc ? nk - 1 - jj : jj;
+      const int idx = i * nk + j;
       const int k = c.voc_rb_kernel[j];
-      // this ResBlock's stream and buffers (shadowing the stage-wide names below)
+      // this ResBlock's stream and buffers (shadowing the stage-wide names)
       const bool aside = conc && j > 0;
-      float* const S = aside ? ptr<float>(e->vside[j - 1][0]) : S_main;
-      float* const T1 = aside ? ptr<float>(e->vside[j - 1][1]) : T1_main;
-      float* const CUR = aside ? ptr<float>(e->vside[j - 1][2]) : CUR_main;
-      e->stream = aside ? e->side[j - 1] : main_stream;
-      struct StreamGuard {  // whatever path leaves this iteration, the engine's stream is its own again
-        e2etts_engine* e; hipStream_t s;
-        ~StreamGuard() { e->stream = s; }
-      } guard{e, main_stream};
+      const RbBufs rb = rb_bufs(P, aside ? j : 0);
+      float *const S = rb.S, *const T1 = rb.T1, *const CUR = rb.CUR;
+      OnStream on(e, aside ? P.side[j - 1] : P.stream);   // whatever path leaves this iteration, the engine is back on the pass's stream
       const float* cur = XU;
       const bool f32 = e->voc_precision == E2ETTS_PRECISION_FP32;
       bool fused = e->fuse_pairs && e->stage_fused[i] && (!f32 || !e->rb_pair_frag32[idx].empty());
@@ -2070,23 +2127,18 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
       bool whole_rb = false;
       // (at large grids the pair / chain kernels, two or three workgroups per CU, are ahead of this one-workgroup-per-CU kernel:
       // measured 7.9 against 8.4 ms for the 60 s utterance in one call; E2ETTS_BRB_ALWAYS=1 takes it there too -- same bits)
-      static const bool rb_always = getenv("E2ETTS_BRB_ALWAYS") && atoi(getenv("E2ETTS_BRB_ALWAYS")) != 0;
-      if (rb_always && fused && e->fuse_pairs >= 2 && !act_stage[i + 1]) {
+      if (tune.brb_always && fused && e->fuse_pairs >= 2 && !act_stage[i + 1]) {
         RbParams rq;
-        if (rb_params(i, j, co, n, XU, S, rq)) {
-          rq.accumulate = !conc && j > 0;
-          if (j == c.voc_n_kernels - 1 && rq.accumulate) rq.out_div = (float)c.voc_n_kernels;
-          char nm[48];
-          snprintf(nm, sizeof nm, "rb_bf16_%d", co);
-          ProfScope ps(e, nm, rb_bf16_flops(rq), rb_bf16_bytes(rq));
-          KCHK(e, launch_rb_bf16(rq, e->stream));
+        if (rb_params(W, g, j, XU, S, rq)) {
+          RET(rb_single(e, W, g, rq, closing(j, true, nk, conc)));
           whole_rb = true;
           fused = false;   // nothing left for the pair / chain / two-launch forms below
         }
       }
       // the whole ResBlock in one launch (resblock_chain.hip) where it exists: kernel size 3 at 32 / 64 channels
-      const bool chained = fused && !f32 && e->fuse_pairs >= 2 && resblock_chain_supported(co, k, c.voc_rb_dil[j], c.voc_n_dil);
+      const bool chained = fused && !f32 && e->fuse_pairs >= 2 && resblock_chain_supported(co, k, c.voc_rb_dil[j], nd);
       if (chained) {
+        const Closing cl = closing(j, true, nk, conc);
         ChainParams q;
         q.x = XU; q.wfrag = e->rb_pair_frag[idx][0]; q.out = S;
         for (int m = 0; m < 3; ++m) { q.b1[m] = e->rb_c1[idx][m].b; q.b2[m] = e->rb_c2[idx][m].b; q.dil[m] = c.voc_rb_dil[j][m]; }
@@ -2094,63 +2146,43 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
         q.B = B; q.T = (int)n; q.C = co; q.KW = k;
         q.x_bs = q.out_bs = (long long)n * co;
         q.slope = 0.1f; q.mode = e->voc_precision;
-        q.accumulate = !conc && j > 0;
-        if (j == c.voc_n_kernels - 1 && q.accumulate) q.out_div = (float)c.voc_n_kernels;
+        q.accumulate = cl.accumulate; q.out_div = cl.out_div;
         char nm[48];
         snprintf(nm, sizeof nm, "resblock_chain_%d", co);
         ProfScope ps(e, nm, resblock_chain_flops(q), resblock_chain_bytes(q));
         KCHK(e, launch_resblock_chain(q, e->stream));
       }
-      for (int m = 0; m < c.voc_n_dil && fused && !chained; ++m) {
+      for (int m = 0; m < nd && fused && !chained; ++m) {
         // the whole pair in one launch (resblock_pair.hip); x and out must differ, so the running x ping-pongs CUR / T1
-        const bool last = m == c.voc_n_dil - 1;
-        PairParams q;
-        q.x = cur; q.wfrag = f32 ? e->rb_pair_frag32[idx][m] : e->rb_pair_frag[idx][m]; q.b1 = e->rb_c1[idx][m].b; q.b2 = e->rb_c2[idx][m].b;
-        q.out = last ? S : (cur == CUR ? T1 : CUR);
+        const Closing cl = closing(j, m == nd - 1, nk, conc);
+        PairParams q = pair_params(W, g, j, m);   // (plain bf16: with its conv_bf16.hip images, so that pair_bf16 may serve it -- same bits)
+        q.x = cur; q.out = m == nd - 1 ? S : (cur == CUR ? T1 : CUR);
         q.act_rows = act_stage[i + 1]; q.act_rows_host = act_stage_h[i + 1]; q.act_frac = vfs[i + 1];
-        q.B = B; q.T = (int)n; q.C = co; q.KW = k; q.dil = c.voc_rb_dil[j][m];
-        q.x_bs = q.out_bs = (long long)n * co;
-        q.slope = 0.1f; q.mode = e->voc_precision;
-        if (last) {
-          q.accumulate = !conc && j > 0;
-          if (j == c.voc_n_kernels - 1 && q.accumulate) q.out_div = (float)c.voc_n_kernels;
-        }
-        {
-          static const bool fine = getenv("E2ETTS_PROFILE_FINE") != nullptr;
-          char nm[48];
-          if (fine) snprintf(nm, sizeof nm, "pair %d k%d d%d r%lld%s", co, k, q.dil, (long long)B * n, q.accumulate ? "+a" : "");
-          else snprintf(nm, sizeof nm, f32 ? "resblock_pair_f32_%d" : "resblock_pair_%d", co);
-          if (q.mode == E2ETTS_PRECISION_BF16) {   // plain bf16: the same pair on conv_bf16.hip's machinery where it applies (same bits)
-            auto i1 = e->bimg_of.find(e->rb_c1[idx][m].wx3), i2 = e->bimg_of.find(e->rb_c2[idx][m].wx3);
-            if (i1 != e->bimg_of.end() && i2 != e->bimg_of.end()) { q.bimg1 = i1->second.first; q.bimg2 = i2->second.first; }
-          }
-          // (at large grids the two kernel families are level pair by pair; the whole 60 s utterance in one call: 7.69 ms with pair_bf16
-          // everywhere against 7.91 with resblock_pair.hip there, same box; E2ETTS_BPAIR_BIG=0 keeps the latter -- same bits)
-          static const bool bpair_big = !(getenv("E2ETTS_BPAIR_BIG") && atoi(getenv("E2ETTS_BPAIR_BIG")) == 0);
-          const bool bpair = (bpair_big || small_window) && pair_bf16_supported(q);
-          if (bpair && !fine) snprintf(nm, sizeof nm, "pair_bf16_%d", co);
-          ProfScope ps(e, nm, resblock_pair_flops(q), resblock_pair_bytes(q));
-          KCHK(e, bpair ? launch_pair_bf16(q, e->stream) : launch_resblock_pair(q, e->stream));
-        }
+        q.accumulate = cl.accumulate; q.out_div = cl.out_div;
+        // (at large grids the two kernel families are level pair by pair; the whole 60 s utterance in one call: 7.69 ms with pair_bf16
+        // everywhere against 7.91 with resblock_pair.hip there, same box; E2ETTS_BPAIR_BIG=0 keeps the latter -- same bits)
+        const bool bpair = (tune.bpair_big || small_window) && pair_bf16_supported(q);
+        char nm[48];
+        if (tune.profile_fine) snprintf(nm, sizeof nm, "pair %d k%d d%d r%lld%s", co, k, q.dil, (long long)B * n, q.accumulate ? "+a" : "");
+        else if (bpair) snprintf(nm, sizeof nm, "pair_bf16_%d", co);
+        else snprintf(nm, sizeof nm, f32 ? "resblock_pair_f32_%d" : "resblock_pair_%d", co);
+        ProfScope ps(e, nm, resblock_pair_flops(q), resblock_pair_bytes(q));
+        KCHK(e, bpair ? launch_pair_bf16(q, e->stream) : launch_resblock_pair(q, e->stream));
         cur = q.out;
       }
-      for (int m = 0; m < c.voc_n_dil && c.voc_resblock == 2; ++m) {
+      for (int m = 0; m < nd && c.voc_resblock == 2; ++m) {
         // ResBlock2 (V/layers.py:59-63): x = c(lrelu(x)) + x per dilation; the last one adds into the stage sum
-        const bool last = m == c.voc_n_dil - 1;
+        const bool last = m == nd - 1;
+        const Closing cl = closing(j, last, nk, conc);
         p = ConvParams();
         p.B = B; p.T = (int)n; p.act_rows = act_stage[i + 1]; p.act_rows_host = act_stage_h[i + 1]; p.act_frac = vfs[i + 1]; p.in = cur; setw(p, e->rb_c1[idx][m]); p.res = cur; p.Cin = co; p.Cout = co;
         p.KW = k; p.dil = c.voc_rb_dil[j][m]; p.pad = (k * p.dil - p.dil) / 2; p.in_slope = 0.1f;
-        if (last) {
-          p.out = S;
-          p.accumulate = !conc && j > 0;
-          if (j == c.voc_n_kernels - 1 && p.accumulate) p.out_div = (float)c.voc_n_kernels;
-        } else {
-          p.out = cur == CUR ? T1 : CUR;  // never in place: other workgroups still read the rows around this tile
-        }
+        p.out = last ? S : (cur == CUR ? T1 : CUR);  // never in place: other workgroups still read the rows around this tile
+        p.accumulate = cl.accumulate; p.out_div = cl.out_div;
         RET(conv(e, p));
         cur = p.out;
       }
-      for (int m = 0; m < c.voc_n_dil && !fused && !whole_rb && c.voc_resblock == 1; ++m) {
+      for (int m = 0; m < nd && !fused && !whole_rb && c.voc_resblock == 1; ++m) {
         const int d = c.voc_rb_dil[j][m];
         // xt = c1(lrelu(x)); the lrelu that feeds c2 is applied here, in c1's epilogue (V/layers.py:35-38)
         p = ConvParams();
@@ -2171,56 +2203,50 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
         RET(conv(e, p));
         // x = c2(xt) + x (:38-39); the last pair adds into the stage sum, and the last ResBlock divides by num_kernels
         // (V/generator.py:44-48)
-        const bool last = m == c.voc_n_dil - 1;
+        const bool last = m == nd - 1;
+        const Closing cl = closing(j, last, nk, conc);
         p = ConvParams();
         p.B = B; p.T = (int)n; p.act_rows = act_stage[i + 1]; p.act_rows_host = act_stage_h[i + 1]; p.act_frac = vfs[i + 1]; p.in = T1; setw(p, e->rb_c2[idx][m]); p.res = cur; p.Cin = co; p.Cout = co;
         p.in_bf16 = handover ? 1 : 0;
         p.KW = k; p.dil = 1; p.pad = (k - 1) / 2;
-        if (last) {
-          p.out = S;
-          p.accumulate = !conc && j > 0;
-          if (j == c.voc_n_kernels - 1 && !conc) p.out_div = (float)c.voc_n_kernels;
-        } else {
-          p.out = CUR;
-        }
+        p.out = last ? S : CUR;
+        p.accumulate = cl.accumulate; p.out_div = cl.out_div;
         RET(conv(e, p));
         cur = CUR;
       }
-      if (aside) HIPCHK(e, hipEventRecord(e->ev_join[j - 1], e->stream));
+      if (aside) HIPCHK(e, hipEventRecord(P.ev_join[j - 1], e->stream));
     }
     // A grouped stage leaves its join to the layer that reads the sum -- the next upsampler (conv_bf16.hip stages (S_0 + S_1 + S_2) / 3 from
     // the three tensors) or conv_post -- where that layer can take it: accum_div's additions and division in its order (same bits), without
     // its launch and its pass over four tensors (142 MB at the 32- and 64-channel stages of a 542-frame window at 48 kHz).
     bool deferred = false;
-    static const bool defer_env = !(getenv("E2ETTS_VOC_DEFER_JOIN") && atoi(getenv("E2ETTS_VOC_DEFER_JOIN")) == 0);   // tuning aid
     if (joined_in_kernel) deferred = true;   // nothing left to join
-    if (conc && grouped_stage && !joined_in_kernel && defer_env && nk <= 4) {
+    if (conc && grouped_stage && !joined_in_kernel && tune.defer_join && nk <= 4) {
       bool can = false;
       if (i + 1 < c.voc_stages) {
         ConvParams q;
         make_up(i + 1, n, ch, q);
         q.in_ld = q.Cin; q.out_ld = q.Cout; q.in_bs = (long long)q.T * q.Cin; q.out_bs = (long long)q.T * q.Cout;
-        q.in_add[0] = ptr<float>(e->vside[0][0]);
+        q.in_add[0] = rb_bufs(P, 1).S;
         BConvParams bq;
         can = bconv_params(q, bq);
       } else {
         can = !istft;
       }
       if (can) {
-        for (int j = 1; j < nk; ++j) pend_add[j - 1] = ptr<float>(e->vside[j - 1][0]);
+        for (int j = 1; j < nk; ++j) pend_add[j - 1] = rb_bufs(P, j).S;
         pend_div = (float)nk;
         deferred = true;
       }
     }
     if (conc && !deferred) {  // join: S = ((S_0 + S_1) + S_2 ...) / num_kernels, the accumulating epilogues' order
-      for (int j = 1; j < nk && !grouped_stage; ++j) HIPCHK(e, hipStreamWaitEvent(main_stream, e->ev_join[j - 1], 0));
+      for (int j = 1; j < nk && !grouped_stage; ++j) HIPCHK(e, hipStreamWaitEvent(P.stream, P.ev_join[j - 1], 0));
       for (int j = 1; j < nk; j += 2) {  // two side sums per pass: (S + S_j) + S_j+1, the same additions in the same order
         const bool two = j + 1 < nk;
         const bool closes = (two ? j + 1 : j) == nk - 1;
-        KCHK(e, launch_accum_div(S_main, ptr<float>(e->vside[j - 1][0]), (long long)B * n * co, closes ? (float)nk : 1.0f, main_stream,
-                                 two ? ptr<float>(e->vside[j][0]) : nullptr));
+        KCHK(e, launch_accum_div(S, rb_bufs(P, j).S, (long long)B * n * co, closes ? (float)nk : 1.0f, P.stream, two ? rb_bufs(P, j + 1).S : nullptr));
       }
-      drain.armed = false;  // every side stream's work is now ordered before the main stream's next launch
+      drain.armed = false;  // every side stream's work is now ordered before the pass's next launch
     }
   }
   if (istft) {
@@ -2228,30 +2254,29 @@ int vocoder_impl(e2etts_engine* e, const float* mel_btc, int B, int T, bool want
     // wav = istft(spec * exp(j phase), n_fft, hop, window = hann) (src/tools/stft.py:138-148)
     const long long F = n + 1;
     const int pc = (c.voc_istft_nfft + 2 + 3) / 4 * 4, bins = c.voc_istft_nfft / 2 + 1;
-    RET(ensure(e, e->istft_q, (size_t)B * F * pc * 4));
-    RET(ensure(e, e->istft_ri, (size_t)B * F * bins * 8));
-    RET(ensure(e, e->istft_sp, (size_t)B * F * bins * 2 * 4));
+    RET(ensure(e, P.istft_q, (size_t)B * F * pc * 4));
+    RET(ensure(e, P.istft_ri, (size_t)B * F * bins * 8));
+    RET(ensure(e, P.istft_sp, (size_t)B * F * bins * 2 * 4));
     {
       ProfScope ps(e, "misc", 0, 0);
       KCHK(e, launch_reflect_lrelu(S, XU, B, n, (int)ch, 0.01f, e->stream));
     }
     p = ConvParams();
-    p.B = B; p.T = (int)F; p.in = XU; setw(p, e->voc_post); p.out = ptr<float>(e->istft_q); p.Cin = (int)ch; p.Cout = pc; p.KW = 7; p.pad = 3;
+    p.B = B; p.T = (int)F; p.in = XU; setw(p, e->voc_post); p.out = ptr<float>(P.istft_q); p.Cin = (int)ch; p.Cout = pc; p.KW = 7; p.pad = 3;
     RET(conv(e, p));
     {
       ProfScope ps(e, "istft", 0, (double)B * F * pc * 4.0 + (double)B * nsamp * 6.0);
-      KCHK(e, launch_istft(ptr<float>(e->istft_q), pc, ptr<float>(e->istft_sp), ptr<float>(e->istft_ri), ptr<float>(WAV),
-                           ptr<int16_t>(PCM), B, F, c.voc_istft_nfft, c.voc_istft_hop, e->stream));
+      KCHK(e, launch_istft(ptr<float>(P.istft_q), pc, ptr<float>(P.istft_sp), ptr<float>(P.istft_ri), ptr<float>(P.wav),
+                           ptr<int16_t>(P.pcm), B, F, c.voc_istft_nfft, c.voc_istft_hop, e->stream));
     }
-    e->istft_B = B;
-    e->istft_F = F;
+    P.istft_B = B;
+    P.istft_F = F;
   } else {
     ProfScope ps(e, "conv_post", 2.0 * B * (double)n * 7 * ch, (double)B * n * (ch * 4.0 + 6.0));
-    KCHK(e, launch_conv_post(S, e->voc_post.w, e->voc_post.b, ptr<float>(WAV), ptr<int16_t>(PCM), B, n, (int)ch, 7, e->stream,
+    KCHK(e, launch_conv_post(S, e->voc_post.w, e->voc_post.b, ptr<float>(P.wav), ptr<int16_t>(P.pcm), B, n, (int)ch, 7, e->stream,
                              act_stage[c.voc_stages], act_stage_h[c.voc_stages], pend_add[0] ? pend_add : nullptr, pend_div));
   }
-  (void)want_wav; (void)want_pcm;
-  if (!own_out) {
+  if (P.resident) {
     e->voc_B = B; e->voc_T = T;
     e->have_wav = true;
   }
@@ -2478,6 +2503,8 @@ int e2etts_create(int device_id, const e2etts_config* cfg, e2etts_engine** out) 
     delete e;
     return E2ETTS_EHIP;
   }
+  e->voc.stream = e->dn_pass.stream = e->stream;
+  e->voc.resident = true;
   *out = e;
   return E2ETTS_OK;
 }
@@ -2487,7 +2514,7 @@ void e2etts_destroy(e2etts_engine* e) {
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);
   for (auto& sl : e->st_slot)
-    if (sl.ctx.stream) (void)hipStreamSynchronize(sl.ctx.stream);
+    if (sl.pass.stream) (void)hipStreamSynchronize(sl.pass.stream);
   for (DevBuf* b : e->owned)  // registered by ensure(): no hand-kept list to fall behind when a buffer is added
     if (b->p) (void)hipFree(b->p);
   for (auto& r : e->prof_recs) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
@@ -2498,18 +2525,15 @@ void e2etts_destroy(e2etts_engine* e) {
     if (sl.pin) (void)hipHostFree(sl.pin);
     if (sl.done) (void)hipEventDestroy(sl.done);
     if (sl.win_ready) (void)hipEventDestroy(sl.win_ready);
-    for (auto& st : sl.ctx.side)
-      if (st) (void)hipStreamDestroy(st);
-    if (sl.ctx.ev_fork) (void)hipEventDestroy(sl.ctx.ev_fork);
-    for (auto& ev : sl.ctx.ev_join)
-      if (ev) (void)hipEventDestroy(ev);
-    if (sl.ctx.stream) (void)hipStreamDestroy(sl.ctx.stream);
+    if (sl.pass.stream) (void)hipStreamDestroy(sl.pass.stream);
   }
-  for (auto& st : e->side)
-    if (st) (void)hipStreamDestroy(st);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  for (auto& ev : e->ev_join)
-    if (ev) (void)hipEventDestroy(ev);
+  for_each_pass(e, [](VocPass& P) {   // (their buffers are in e->owned)
+    for (auto& st : P.side)
+      if (st) (void)hipStreamDestroy(st);
+    if (P.ev_fork) (void)hipEventDestroy(P.ev_fork);
+    for (auto& ev : P.ev_join)
+      if (ev) (void)hipEventDestroy(ev);
+  });
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -2545,7 +2569,7 @@ static int bind_resident_blob(e2etts_engine* e, size_t nbytes) {
 // is closed (its chunks were computed with the old weights; the next _push says so).
 static int drain_stream_slots(e2etts_engine* e) {
   for (auto& sl : e->st_slot)
-    if (sl.ctx.stream) HIPCHK(e, hipStreamSynchronize(sl.ctx.stream));
+    if (sl.pass.stream) HIPCHK(e, hipStreamSynchronize(sl.pass.stream));
   e->st_open = false;
   e->st_pending = 0;
   return E2ETTS_OK;
@@ -2700,9 +2724,9 @@ int e2etts_fetch_tap(e2etts_engine* e, const char* which, float* out, size_t n_f
   size_t n = 0;
   if (!strcmp(which, "istft_spec_phase")) {
     if (!e->cfg.voc_istft_nfft || !e->have_wav) return e->fail(E2ETTS_ESTATE, "no iSTFT vocoder result resident");
-    n = (size_t)e->istft_B * e->istft_F * (e->cfg.voc_istft_nfft + 2);
+    n = (size_t)e->voc.istft_B * e->voc.istft_F * (e->cfg.voc_istft_nfft + 2);
     if (n_floats != n) return e->fail(E2ETTS_EINVAL, "tap '%s' holds %zu floats, caller asked for %zu", which, n, n_floats);
-    RET(copy_out(e, out, e->istft_sp.p, n * 4));
+    RET(copy_out(e, out, e->voc.istft_sp.p, n * 4));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return E2ETTS_OK;
   }
@@ -2758,10 +2782,10 @@ static int vocoder_entry(e2etts_engine* e, const float* mel, bool channels_first
     }
     src = btc;
   }
-  RET(vocoder_impl(e, src, B, T, wav_out != nullptr, pcm_out != nullptr));
+  RET(vocoder_impl(e, e->voc, src, B, T));
   const size_t ns = (size_t)B * T * e->cfg.hop_length;
-  if (wav_out) RET(copy_out(e, wav_out, e->wav.p, ns * 4));
-  if (pcm_out) RET(copy_out(e, pcm_out, e->pcm.p, ns * 2));
+  if (wav_out) RET(copy_out(e, wav_out, e->voc.wav.p, ns * 4));
+  if (pcm_out) RET(copy_out(e, pcm_out, e->voc.pcm.p, ns * 2));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
 }
@@ -2792,12 +2816,12 @@ static int synthesize_entry(e2etts_engine* e, const int64_t* ids, const int64_t*
   RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, ragged, ctl));
   ragged = ragged && e->rag_short;
   if (T_out) *T_out = e->last_T;
-  RET(vocoder_impl(e, ptr<float>(e->melpost), B, e->last_T, false, true, ragged ? ptr<int32_t>(e->mel32) : nullptr, ragged ? e->h_mel : nullptr));
+  RET(vocoder_impl(e, e->voc, ptr<float>(e->melpost), B, e->last_T, ragged ? ptr<int32_t>(e->mel32) : nullptr, ragged ? e->h_mel : nullptr));
   if (denoise) {  // each row's valid samples, before the int16 conversion: the resident PCM becomes the denoised one, the resident wav stays
     const long long n = (long long)e->last_T * e->cfg.hop_length;
     std::vector<long long> nv(B);
     for (int b = 0; b < B; ++b) nv[b] = std::min<long long>(std::max<long long>(e->h_mel[b], 0), e->last_T) * e->cfg.hop_length;
-    RET(denoise_impl(e, ptr<float>(e->wav), n, nv.data(), B, n, e->dn.strength, nullptr, ptr<int16_t>(e->pcm)));
+    RET(denoise_impl(e, ptr<float>(e->voc.wav), n, nv.data(), B, n, e->dn.strength, nullptr, ptr<int16_t>(e->voc.pcm)));
   }
   if (mel_lens_out) RET(copy_out(e, mel_lens_out, e->mel64.p, (size_t)B * 8));
   const size_t ns = (size_t)B * e->last_T * e->cfg.hop_length;
@@ -2806,7 +2830,7 @@ static int synthesize_entry(e2etts_engine* e, const int64_t* ids, const int64_t*
       HIPCHK(e, hipStreamSynchronize(e->stream));
       return e->fail(E2ETTS_EINVAL, "pcm buffer holds %zu samples, result has %zu (fetch it with e2etts_fetch_pcm)", pcm_capacity, ns);
     }
-    RET(copy_out(e, pcm_out, e->pcm.p, ns * 2));
+    RET(copy_out(e, pcm_out, e->voc.pcm.p, ns * 2));
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
@@ -2835,7 +2859,7 @@ int e2etts_fetch_pcm(e2etts_engine* e, int16_t* pcm_out, size_t capacity) {
   if (!e->have_wav) return e->fail(E2ETTS_ESTATE, "no vocoder result resident");
   const size_t ns = (size_t)e->voc_B * e->voc_T * e->cfg.hop_length;
   if (capacity < ns) return e->fail(E2ETTS_EINVAL, "buffer holds %zu samples, result has %zu", capacity, ns);
-  RET(copy_out(e, pcm_out, e->pcm.p, ns * 2));
+  RET(copy_out(e, pcm_out, e->voc.pcm.p, ns * 2));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
 }
@@ -2847,27 +2871,10 @@ int e2etts_fetch_wav(e2etts_engine* e, float* wav_out, size_t capacity) {
   if (!e->have_wav) return e->fail(E2ETTS_ESTATE, "no vocoder result resident");
   const size_t ns = (size_t)e->voc_B * e->voc_T * e->cfg.hop_length;
   if (capacity < ns) return e->fail(E2ETTS_EINVAL, "buffer holds %zu samples, result has %zu", capacity, ns);
-  RET(copy_out(e, wav_out, e->wav.p, ns * 4));
+  RET(copy_out(e, wav_out, e->voc.wav.p, ns * 4));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   return E2ETTS_OK;
 }
-
-// The engine works in ctx (stream, activations, side streams) while this object lives.
-struct CtxSwap {
-  e2etts_engine* e; e2etts_engine::VocCtx& c;
-  void swap() {
-    std::swap(e->stream, c.stream);
-    std::swap(e->v0, c.v0); std::swap(e->v1, c.v1); std::swap(e->v2, c.v2); std::swap(e->v3, c.v3);
-    for (int j = 0; j < E2ETTS_MAX_RB_KERNELS - 1; ++j) {
-      for (int k = 0; k < 3; ++k) std::swap(e->vside[j][k], c.vside[j][k]);
-      std::swap(e->side[j], c.side[j]);
-      std::swap(e->ev_join[j], c.ev_join[j]);
-    }
-    std::swap(e->ev_fork, c.ev_fork);
-  }
-  CtxSwap(e2etts_engine* e_, e2etts_engine::VocCtx& c_) : e(e_), c(c_) { swap(); }
-  ~CtxSwap() { swap(); }
-};
 
 // denoise_strength < 0: a plain stream; else a denoised one, *delay_out = its extra frames of context per side
 static int stream_begin(e2etts_engine* e, int B, float denoise_strength, int* delay_out) {
@@ -2889,17 +2896,9 @@ static int stream_begin(e2etts_engine* e, int B, float denoise_strength, int* de
   for (auto& sl : e->st_slot) {
     if (!sl.done) HIPCHK(e, hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     if (!sl.win_ready) HIPCHK(e, hipEventCreateWithFlags(&sl.win_ready, hipEventDisableTiming));
-    if (!sl.ctx.stream) {
-      HIPCHK(e, hipStreamCreateWithFlags(&sl.ctx.stream, hipStreamNonBlocking));
-      // a slot's workspace is grown by ensure() while it is swapped into the engine, i.e. under the engine members' addresses: the
-      // slot's own DevBufs are what e2etts_destroy must free
-      DevBuf* mine[] = {&sl.ctx.v0, &sl.ctx.v1, &sl.ctx.v2, &sl.ctx.v3};
-      for (DevBuf* b : mine) e->owned.push_back(b);
-      for (auto& row : sl.ctx.vside)
-        for (auto& b : row) e->owned.push_back(&b);
-    }
+    if (!sl.pass.stream) HIPCHK(e, hipStreamCreateWithFlags(&sl.pass.stream, hipStreamNonBlocking));
     // chunks of an abandoned stream may still be in flight: nothing of theirs is delivered
-    HIPCHK(e, hipStreamSynchronize(sl.ctx.stream));
+    HIPCHK(e, hipStreamSynchronize(sl.pass.stream));
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
   e->st_head = 0;
@@ -2991,18 +2990,18 @@ int e2etts_vocoder_stream_push(e2etts_engine* e, const float* mel_btc, int n, in
   if (last) e->st_done = true;
   if (n_emit > 0) {
     HIPCHK(e, hipEventRecord(sl.win_ready, cp));
-    HIPCHK(e, hipStreamWaitEvent(sl.ctx.stream, sl.win_ready, 0));
-    hipStream_t const cs = sl.ctx.stream;
+    hipStream_t const cs = sl.pass.stream;
+    HIPCHK(e, hipStreamWaitEvent(cs, sl.win_ready, 0));
     int rc;
     {
-      CtxSwap in_slot(e, sl.ctx);
-      rc = vocoder_impl(e, ptr<float>(sl.win), B, total, true, true, nullptr, nullptr, &sl.wav, &sl.pcm);
+      OnStream in_slot(e, cs);   // the pass and the denoiser's launches behind it
+      rc = vocoder_impl(e, sl.pass, ptr<float>(sl.win), B, total);
       if (rc == E2ETTS_OK && e->st_dn) {
         // the window's samples from st_delay frames before the emitted range to st_delay frames after it (or to the stream's ends): all of
         // them have the vocoder's full halo in the window, i.e. are the one-shot vocoder's samples
         const long long hl = e->cfg.hop_length;
         const int d_lo = std::max(0, left_ctx - e->st_delay), d_hi = std::min(total, emit_end + e->st_delay);
-        rc = denoise_stream_impl(e, sl, ptr<float>(sl.wav) + (size_t)d_lo * hl, (long long)total * hl, B, (long long)(d_hi - d_lo) * hl,
+        rc = denoise_stream_impl(e, sl, ptr<float>(sl.pass.wav) + (size_t)d_lo * hl, (long long)total * hl, B, (long long)(d_hi - d_lo) * hl,
                                  (win_abs0 + d_lo) * hl, last && d_hi == total, (long long)(left_ctx - d_lo) * hl, (long long)n_emit * hl, e->st_strength);
       }
     }
@@ -3035,7 +3034,7 @@ int e2etts_vocoder_stream_fetch(e2etts_engine* e, float* wav_out, int16_t* pcm_o
   if (capacity < (size_t)e->st_B * ns) return e->fail(E2ETTS_EINVAL, "buffer holds %zu samples, chunk has %zu", capacity, (size_t)e->st_B * ns);
   // a denoised stream's slot holds the emitted samples alone, [B, ns] compact
   const size_t src_row = e->st_dn ? ns : (size_t)sl.win_n * hop, off = e->st_dn ? 0 : (size_t)sl.emit_off * hop;
-  DevBuf &src_wav = e->st_dn ? sl.dn_wav : sl.wav, &src_pcm = e->st_dn ? sl.dn_pcm : sl.pcm;
+  DevBuf &src_wav = e->st_dn ? sl.dn_wav : sl.pass.wav, &src_pcm = e->st_dn ? sl.dn_pcm : sl.pass.pcm;
   HIPCHK(e, hipStreamWaitEvent(e->stream, sl.done, 0));
   if (wav_out)
     HIPCHK(e, hipMemcpy2DAsync(wav_out, ns * 4, ptr<float>(src_wav) + off, src_row * 4, ns * 4, e->st_B, hipMemcpyDefault, e->stream));
@@ -3163,22 +3162,13 @@ int e2etts_denoiser_calibrate(e2etts_engine* e, const float* mel_btc_or_null, in
   RET(ensure(e, e->dn_mel, nm));
   if (mel_btc_or_null) RET(copy_in(e, e->dn_mel.p, mel_btc_or_null, nm));
   else HIPCHK(e, hipMemsetAsync(e->dn_mel.p, 0, nm, e->stream));
-  {
-    // the vocoder writes into buffers of this call; the iSTFT tail's tap buffers are stood in for, so every resident result (the wav and
-    // PCM of the last call, the "istft_spec_phase" tap) is what it was
-    struct TapSwap {
-      e2etts_engine* e; int B; long long F;
-      void swap() { std::swap(e->istft_q, e->dn_iq); std::swap(e->istft_ri, e->dn_iri); std::swap(e->istft_sp, e->dn_isp); }
-      TapSwap(e2etts_engine* e_) : e(e_), B(e_->istft_B), F(e_->istft_F) { swap(); }
-      ~TapSwap() { swap(); e->istft_B = B; e->istft_F = F; }
-    } keep(e);
-    RET(vocoder_impl(e, ptr<float>(e->dn_mel), 1, T, true, false, nullptr, nullptr, &e->dn_cwav, &e->dn_cpcm));
-  }
+  // the pass works in buffers of its own, so every resident result (the wav and PCM of the last call, the "istft_spec_phase" tap) is what it was
+  RET(vocoder_impl(e, e->dn_pass, ptr<float>(e->dn_mel), 1, T));
   const long long nv = ns;
   int F_max = 0;
   bool ragged = false;
   RET(denoise_table(e, &nv, 1, &F_max, &ragged));
-  RET(denoise_forward(e, ptr<float>(e->dn_cwav), ns, 1, F_max, false));
+  RET(denoise_forward(e, ptr<float>(e->dn_pass.wav), ns, 1, F_max, false));
   KCHK(e, launch_bias_frame(ptr<float>(e->dn_spec), ptr<float>(e->dn_bias), e->dn.nfft, e->stream));   // magnitudes of frame 0 (V/denoiser.py:179)
   if (bias_out_or_null) RET(copy_out(e, bias_out_or_null, e->dn_bias.p, (size_t)(e->dn.nfft / 2 + 1) * 4));
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -3217,7 +3207,7 @@ int e2etts_denoise(e2etts_engine* e, const float* wav_in_or_null, const int64_t*
     if (nv[b] < 0 || nv[b] > n || nv[b] % e->dn.hop)
       return e->fail(E2ETTS_EINVAL, "row %d: %lld valid samples must lie in [0, %lld] and be a multiple of the denoiser hop %d", b, nv[b], (long long)n, e->dn.hop);
   const size_t ns = (size_t)B * (size_t)n;
-  const float* in = ptr<float>(e->wav);
+  const float* in = ptr<float>(e->voc.wav);
   if (wav_in_or_null) {
     RET(ensure(e, e->dn_in, ns * 4));
     RET(copy_in(e, e->dn_in.p, wav_in_or_null, ns * 4));
@@ -3290,26 +3280,32 @@ int e2etts_debug_poison_workspace(e2etts_engine* e) {
   // what the workspaces held is gone: taps, fetches and vocoder(NULL) must say so instead of handing out the pattern
   e->have_acoustic = false;
   e->have_wav = false;
-  DevBuf* bufs[] = {&e->xa, &e->xb, &e->xs, &e->xp, &e->tmp, &e->qkv, &e->att, &e->hid, &e->p1, &e->p2, &e->attws, &e->ffpool, &e->dx, &e->dxb, &e->mel,
-                    &e->melpost, &e->pn1, &e->pn2, &e->melin, &e->v0, &e->v1, &e->v2, &e->v3, &e->wav, &e->pcm, &e->istft_q, &e->istft_ri, &e->istft_sp};
-  for (DevBuf* b : bufs)
-    if (b->p) HIPCHK(e, hipMemsetAsync(b->p, 0x4B, b->cap, e->stream));
-  for (auto& row : e->vside)
-    for (DevBuf& b : row)
-      if (b.p) HIPCHK(e, hipMemsetAsync(b.p, 0x4B, b.cap, e->stream));
+  auto poison = [&](DevBuf& b) -> int {
+    if (b.p) HIPCHK(e, hipMemsetAsync(b.p, 0x4B, b.cap, e->stream));
+    return E2ETTS_OK;
+  };
+  auto poison_work = [&](VocPass& P) -> int {   // a pass's activations
+    for (DevBuf* b : {&P.v0, &P.v1, &P.v2, &P.v3}) RET(poison(*b));
+    for (auto& row : P.vside)
+      for (DevBuf& b : row) RET(poison(b));
+    return E2ETTS_OK;
+  };
+  auto poison_out = [&](VocPass& P) -> int {   // its outputs and the iSTFT tail's taps
+    for (DevBuf* b : {&P.wav, &P.pcm, &P.istft_q, &P.istft_ri, &P.istft_sp}) RET(poison(*b));
+    return E2ETTS_OK;
+  };
+  for (DevBuf* b : {&e->xa, &e->xb, &e->xs, &e->xp, &e->tmp, &e->qkv, &e->att, &e->hid, &e->p1, &e->p2, &e->attws, &e->ffpool, &e->dx, &e->dxb, &e->mel,
+                    &e->melpost, &e->pn1, &e->pn2, &e->melin})
+    RET(poison(*b));
+  RET(poison_work(e->voc));
+  RET(poison_out(e->voc));
   // the stream slots' workspaces too (their outputs and windows only when nothing awaits a fetch)
   for (auto& sl : e->st_slot) {
-    if (sl.ctx.stream) HIPCHK(e, hipStreamSynchronize(sl.ctx.stream));
-    DevBuf* ws[] = {&sl.ctx.v0, &sl.ctx.v1, &sl.ctx.v2, &sl.ctx.v3};
-    for (DevBuf* b : ws)
-      if (b->p) HIPCHK(e, hipMemsetAsync(b->p, 0x4B, b->cap, e->stream));
-    for (auto& row : sl.ctx.vside)
-      for (DevBuf& b : row)
-        if (b.p) HIPCHK(e, hipMemsetAsync(b.p, 0x4B, b.cap, e->stream));
+    if (sl.pass.stream) HIPCHK(e, hipStreamSynchronize(sl.pass.stream));
+    RET(poison_work(sl.pass));
     if (e->st_pending == 0) {
-      DevBuf* outs[] = {&sl.wav, &sl.pcm, &sl.win};
-      for (DevBuf* b : outs)
-        if (b->p) HIPCHK(e, hipMemsetAsync(b->p, 0x4B, b->cap, e->stream));
+      RET(poison_out(sl.pass));
+      RET(poison(sl.win));
     }
   }
   HIPCHK(e, hipStreamSynchronize(e->stream));
@@ -3362,7 +3358,7 @@ int e2etts_sync(e2etts_engine* e) {
   HIPCHK(e, hipSetDevice(e->device));
   HIPCHK(e, hipStreamSynchronize(e->stream));
   for (auto& sl : e->st_slot)
-    if (sl.ctx.stream) HIPCHK(e, hipStreamSynchronize(sl.ctx.stream));
+    if (sl.pass.stream) HIPCHK(e, hipStreamSynchronize(sl.pass.stream));
   return E2ETTS_OK;
 }
 

@@ -273,3 +273,44 @@ def test_bad_arguments_return_their_codes(gold):
     with pytest.raises(RuntimeError):
         fresh.denoise(x, nv, 0.1)
     fresh.close()
+
+
+def test_calibration_leaves_the_istft_vocoders_resident_results_alone():
+    """The iSTFT tail keeps tap buffers besides wav and PCM: a calibration pass works in buffers of its own, so all three resident results
+    read the same bytes after it as before, and a second identical calibration allocates nothing."""
+    from e2e_tts_amd import packer
+    from e2e_tts_amd._lib import Engine
+    cfg = cfgmod.tiny_config()
+    dims = cfgmod.dims_from_config(cfg, cfgmod.DEFAULT_STATS, 4, vocoder="istft")
+    eng = Engine(dims, 0)
+    eng.load_weights(packer.pack(dims, sw.make_acoustic_state(cfg, cfgmod.DEFAULT_STATS, 4, seed=21, mode="varied"),
+                                 sw.make_vocoder_state(cfg, seed=22, vocoder="istft")))
+    N = 1024
+    dhop = load_geometry(eng, N, 4)
+    B, T = 2, 8
+    mel = np.random.Generator(np.random.PCG64(31)).standard_normal((B, T, dims.n_mel)).astype(np.float32)
+    up = dims.hop_length // dims.voc_istft_hop
+    tap_shape = (B, T * up + 1, dims.voc_istft_nfft + 2)
+
+    def resident():
+        pcm = np.empty((B, T * dims.hop_length), np.int16)
+        assert eng.lib.e2etts_fetch_pcm(eng._h, _addr(pcm), pcm.size) == E_OK
+        return eng.fetch_wav(B, T), pcm, eng.fetch_tap("istft_spec_phase", tap_shape)
+
+    wav0, pcm0 = eng.vocoder(mel, B, T, channels_first=False, wav=True, pcm=True)
+    before = resident()
+    np.testing.assert_array_equal(before[0], wav0)
+    np.testing.assert_array_equal(before[1], pcm0)
+    assert np.abs(before[2]).max() > 0
+    # the smallest frame count the call accepts: a multiple of the denoiser hop in samples, above filter_length / 2
+    T_c = next(t for t in range(1, N) if (t * dims.hop_length) % dhop == 0 and t * dims.hop_length > N // 2)
+    assert eng.lib.e2etts_denoiser_calibrate(eng._h, None, T_c - 1, None) == E_INVAL
+    eng.denoiser_calibrate(None, T_c)
+    for a, b in zip(resident(), before):
+        assert a.tobytes() == b.tobytes()
+    held = eng.device_bytes()
+    eng.denoiser_calibrate(None, T_c)
+    assert eng.device_bytes() == held
+    for a, b in zip(resident(), before):
+        assert a.tobytes() == b.tobytes()
+    eng.close()
