@@ -1059,7 +1059,16 @@ const char* launch_conv_post_bf16(const void* x, const float* w16, const float* 
   if ((uintptr_t)x & 7) return "conv_post_bf16: x must be 8-byte aligned";
   constexpr int TPB = 256;
   const size_t lds = ((size_t)(TPB + KW - 1) * (C + 4) + (size_t)KW * C) * sizeof(float);
-  if (lds > 64 * 1024) return "conv_post_bf16: LDS tile exceeds 64 KiB";
+  // as launch_conv_post: the engine's tails (32 channels) fit the default limit; wider ones (128 channels, k = 7: 139 KB) opt in to the CU's
+  // 160 KiB once per instantiation
+  if (lds > 160 * 1024) return "conv_post_bf16: LDS tile exceeds the CU's 160 KiB";
+  if (lds > 64 * 1024) {
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_post_bf16_kernel<TPB, false>),
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    static const hipError_t attr16 = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_post_bf16_kernel<TPB, true>),
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (attr != hipSuccess || attr16 != hipSuccess) return "conv_post_bf16: cannot raise the dynamic LDS limit";
+  }
   if (fp16)
     hipLaunchKernelGGL((conv_post_bf16_kernel<TPB, true>), dim3((unsigned)((N + TPB - 1) / TPB), B), dim3(TPB), lds, s, reinterpret_cast<const __bf16*>(x), w16,
                        bias16, wav, pcm, N, C, KW);

@@ -263,3 +263,76 @@ CHAIN_CASES = [
     dict(name="chain_c32", B=2, T=700, C=32, KW=3, dil=[1, 3, 5], accumulate=False, out_div=1.0),
     dict(name="chain_c64_acc", B=1, T=513, C=64, KW=3, dil=[1, 3, 5], accumulate=True, out_div=3.0),
 ]
+
+
+# ---- conv_bf16 with 16-bit activations (BConvParams::act16 = 1 bf16, 2 fp16; every case runs at both).  Small launches: the large tiles are
+# reached through rows_hint (bc_choose counts it instead of B x T).  in16: the input is a 16-bit tensor (else fp32: conv_pre taking the
+# mel); n_add / in_div: the join of 16-bit inputs; act_slope: 1.0 = none.  The exact tier's data grids (kernel_ref.a16_grids): xg / wg / ag
+# = (kmax, exponent) of x, w and the addends, neg = the negatives x may take (a non-dyadic staging slope), fb = bits an fp32 input carries
+# past the element type, fine16 = the fp16 grids are finer by 2^-2.  special: 'inf' -- sums past 65504, which fp16 must turn into
+# infinities; 'sub' -- inputs and results that are fp16 subnormals.  kmin: the smallest |k| of the x grid (a join with in_div whose
+# roundings change the sums: x far from zero keeps the lowest set bit of r(x / 3) coarse, the addends' finer grid makes r(in + a) round).
+def _acase(name, cls, B, T, Cin, Cout, KW=1, dil=1, pad="c", in16=True, n_add=0, in_div=1.0, rows_hint=0, act_slope=1.0, xg=(48, -4), wg=(16, -6),
+           ag=None, neg=None, fb=None, fine16=True, special=None, kmin=0, **o):
+    c = _case(name, B, T, Cin, Cout, KW, dil, pad, in_pad=0, out_pad=0, res_pad=0, reach=dict(bcls=cls), bias=True, **o)
+    c.update(in16=in16, n_add=n_add, in_div=in_div, rows_hint=rows_hint, act_slope=act_slope, xg=xg, wg=wg, ag=ag, neg=neg, fb=fb, fine16=fine16,
+             special=special, kmin=kmin)
+    assert in16 or not n_add
+    return c
+
+
+_ENGINE = dict(res=True, accumulate=True, out_div=3.0)                      # the engine's own combination: residual + sum + division
+_COARSE = dict(xg=(6, 0), wg=(4, -6), ag=(6, 0), fine16=False)                        # integers: what a division by 3 or a slope of 0.1 can still sum exactly
+_NEG01 = dict(in_slope=0.1, neg=(-1, -2, -4), **_COARSE)                    # the engine's staging slope on 16-bit inputs
+A16_CASES = [
+    # ---- 128 x 32 (Cout % 64 != 0, few rows)
+    _acase("a_128x32_t1", "conv_bf16_128x32", 2, 1, 8, 32, 3, **_NEG01),
+    _acase("a_128x32_t31", "conv_bf16_128x32", 3, 31, 40, 96, 3, 5, in16=False, in_slope=0.25, act_slope=0.1),
+    _acase("a_128x32_t33_pre", "conv_bf16_128x32", 2, 33, 80, 32, 7, in16=False),                                   # conv_pre taking the mel
+    _acase("a_128x32_t127", "conv_bf16_128x32", 2, 127, 32, 32, 3, act_slope=0.0, res=True),
+    _acase("a_128x32_t128", "conv_bf16_128x32", 1, 128, 32, 96, 3, 1, "L", in_slope=0.25, act_slope=0.1, res=True, accumulate=True),
+    _acase("a_128x32_t129_add1", "conv_bf16_128x32", 2, 129, 8, 32, 3, n_add=1, in_slope=0.25, act_slope=0.1, **_ENGINE),
+    # ---- 256 x 32
+    _acase("a_256x32_t255", "conv_bf16_256x32", 1, 255, 40, 32, 3, 5, in16=False, in_slope=0.25, rows_hint=12288, **_ENGINE),
+    _acase("a_256x32_t256_add2_div", "conv_bf16_256x32", 1, 256, 8, 32, 3, n_add=2, in_div=3.0, in_slope=0.25, rows_hint=12288,
+           xg=(48, 0), kmin=32, wg=(4, -6), ag={1: (48, -4), 2: (384, -7)}, fine16=False),        # the join's roundings bite here
+    _acase("a_256x32_t257", "conv_bf16_256x32", 1, 257, 64, 32, act_slope=0.0, in_slope=0.25, rows_hint=12288),
+    # ---- 512 x 32
+    _acase("a_512x32_t511", "conv_bf16_512x32", 1, 511, 8, 32, 3, act_slope=0.1, res=True, rows_hint=32768),
+    _acase("a_512x32_t512", "conv_bf16_512x32", 1, 512, 32, 32, 3, 1, "L", in16=False, rows_hint=32768),
+    _acase("a_512x32_t513", "conv_bf16_512x32", 1, 513, 40, 32, 3, in_slope=0.25, rows_hint=32768, **_ENGINE),
+    # ---- 64 x 64
+    _acase("a_64x64_t33_add3_div", "conv_bf16_64x64", 3, 33, 8, 64, 3, n_add=3, in_div=3.0, in_slope=0.25, act_slope=0.1, **_ENGINE, **_COARSE),
+    _acase("a_64x64_t63", "conv_bf16_64x64", 2, 63, 64, 64, 7, 3, in_slope=0.25, act_slope=0.1, **_ENGINE),
+    _acase("a_64x64_t64_halo64", "conv_bf16_64x64", 2, 64, 32, 64, 9, 8, "0", in16=False, in_slope=0.25),
+    _acase("a_64x64_t65", "conv_bf16_64x64", 2, 65, 80, 64, 7, in16=False, act_slope=0.1),
+    _acase("a_64x64_inf", "conv_bf16_64x64", 2, 65, 32, 64, 3, xg=(48, 4), wg=(16, 0), fine16=False, special="inf", act_slope=0.1, **_ENGINE),
+    _acase("a_64x64_sub", "conv_bf16_64x64", 2, 65, 32, 64, 3, xg=(48, -24), wg=(16, -3), fine16=False, special="sub", in_slope=0.25, act_slope=0.1,
+           res=True),
+    # ---- 128 x 64
+    _acase("a_128x64_t127", "conv_bf16_128x64", 1, 127, 32, 64, 3, in16=False, in_slope=0.25, act_slope=0.0, res=True, rows_hint=6144),
+    _acase("a_128x64_t128_add3", "conv_bf16_128x64", 1, 128, 8, 64, 3, n_add=3, in_slope=0.25, rows_hint=6144),
+    _acase("a_128x64_t129", "conv_bf16_128x64", 2, 129, 64, 64, 3, 5, **_ENGINE, rows_hint=6144),
+    # ---- 256 x 64
+    _acase("a_256x64_t255_add1_div", "conv_bf16_256x64", 1, 255, 8, 64, 3, n_add=1, in_div=3.0, in_slope=0.25, rows_hint=12288, **_COARSE),
+    _acase("a_256x64_t256", "conv_bf16_256x64", 1, 256, 32, 64, 3, in16=False, in_slope=0.25, act_slope=0.1, res=True, accumulate=True, rows_hint=12288),
+    _acase("a_256x64_t257", "conv_bf16_256x64", 1, 257, 32, 64, 3, 1, "0", in_slope=0.25, act_slope=0.1, rows_hint=12288),
+    # ---- 32 x 128
+    _acase("a_32x128_t1", "conv_bf16_32x128", 3, 1, 32, 128, 3, in16=False, in_slope=0.25, act_slope=0.1),
+    _acase("a_32x128_t31_add2", "conv_bf16_32x128", 2, 31, 8, 128, 3, n_add=2, in_slope=0.25, res=True),
+    _acase("a_32x128_t32", "conv_bf16_32x128", 2, 32, 32, 256, 3, act_slope=0.1, **_ENGINE),
+    _acase("a_32x128_t33_s01", "conv_bf16_32x128", 2, 33, 32, 128, 3, act_slope=0.1, res=True, **_NEG01),
+    _acase("a_32x128_poly", "conv_bf16_32x128", 2, 127, 64, 128, 3, in_slope=0.25, zts=64),
+    _acase("a_32x128_long_k", "conv_bf16_32x128", 1, 129, 256, 128, 11, 5, in_slope=0.25, act_slope=0.1, **_ENGINE),   # the longest K of the matrix: 2816
+    # ---- 64 x 128
+    _acase("a_64x128_t63", "conv_bf16_64x128", 1, 63, 32, 128, 3, in16=False, in_slope=0.25, res=True, rows_hint=3072),
+    _acase("a_64x128_t64", "conv_bf16_64x128", 1, 64, 256, 128, 3, in_slope=0.25, act_slope=0.1, rows_hint=3072),
+    _acase("a_64x128_t65", "conv_bf16_64x128", 2, 65, 32, 128, 7, 1, "L", **_ENGINE, rows_hint=3072),
+    # ---- 128 x 128
+    _acase("a_128x128_t127", "conv_bf16_128x128", 1, 127, 32, 256, 3, in_slope=0.25, act_slope=0.0, rows_hint=3072),
+    _acase("a_128x128_t128", "conv_bf16_128x128", 1, 128, 32, 128, 3, in16=False, in_slope=0.25, act_slope=0.1, **_ENGINE, rows_hint=6144),
+    _acase("a_128x128_t129", "conv_bf16_128x128", 2, 129, 32, 128, 3, 5, in_slope=0.25, res=True, rows_hint=6144),
+]
+A16_BY_NAME = {c["name"]: c for c in A16_CASES}
+assert len(A16_BY_NAME) == len(A16_CASES)
+A16_BM = lambda c: int(c["reach"]["bcls"].split("_")[-1].split("x")[0])   # noqa: E731  -- rows of the tile a case names

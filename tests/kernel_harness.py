@@ -1,4 +1,4 @@
-"""ctypes binding of libe2etts_kernels_test.so (tests/csrc/kernel_harness.hip): the e2ekt_* entry points around the launch wrappers of
+"""ctypes binding of libe2etts_kernels_test.so (tests/csrc/kernel_harness.hip, kernel_harness_act16.hip): the e2ekt_* entry points around the launch wrappers of
 csrc/kernels.h.  Device buffers are passed as `torch.Tensor.data_ptr()` integers (or None); every launch entry returns the wrapper's
 message (None = launched).  The host-only entries (conv_gemm_class, *_supported, *_bytes) work without a GPU."""
 from __future__ import annotations
@@ -27,6 +27,8 @@ PAIR_ARGS = [("x", P), ("wfrag", P), ("b1", P), ("b2", P), ("out", P), ("act_row
              ("KW", I), ("dil", I), ("x_bs", LL), ("out_bs", LL), ("slope", F), ("accumulate", I), ("out_div", F), ("mode", I), ("bimg1", P),
              ("bimg2", P)]
 PAIR_DEFAULTS = dict(wfrag=None, act_rows=None, act_rows_host=None, slope=0.1, accumulate=0, out_div=1.0, mode=1, bimg1=None, bimg2=None)
+BCONV_GROUP_ARGS = [a for a in BCONV_ARGS if a[0] != "rows_hint"]       # e2ekt_conv_bf16_group: one array of n per argument
+PAIR_GROUP_ARGS = [a for a in PAIR_ARGS if a[0] not in ("wfrag", "act_rows", "act_rows_host", "x_bs", "out_bs")]
 RB_ARGS = [("n", I), ("x", P), ("out", P), ("bimg", P), ("b1", P), ("b2", P), ("dil", P), ("KW", P), ("accumulate", P), ("out_div", P),
            ("n_pairs", I), ("B", I), ("T", I), ("C", I), ("x_bs", LL), ("out_bs", LL), ("slope", F), ("act16", I)]
 RB_MAX_PAIRS = 4
@@ -54,6 +56,7 @@ def load() -> C.CDLL:
 
     conv, bconv, pair, rb = ([t for _, t in a] for a in (CONV_ARGS, BCONV_ARGS, PAIR_ARGS, RB_ARGS))
     bind("e2ekt_version", S, [])
+    bind("e2ekt_act16_version", S, [])
     for n in ("conv_gemm", "conv_ksplit", "conv_rows"):
         bind("e2ekt_" + n, S, conv + [P])
     bind("e2ekt_conv_gemm_class", S, conv)
@@ -62,6 +65,9 @@ def load() -> C.CDLL:
     bind("e2ekt_conv_bf16", S, bconv + [P])
     bind("e2ekt_conv_bf16_supported", I, bconv)
     bind("e2ekt_conv_bf16_class", S, bconv)
+    bind("e2ekt_conv_bf16_group", S, [I] + [P] * len(BCONV_GROUP_ARGS) + [P])
+    bind("e2ekt_pair_bf16_group", S, [I] + [P] * len(PAIR_GROUP_ARGS) + [P])
+    bind("e2ekt_conv_post_bf16", S, [P, P, P, P, P, I, LL, I, I, P, I])
     bind("e2ekt_x3_frag_bytes", SZ, [I, I, I])
     bind("e2ekt_x3_to_frag", S, [P, P, I, I, I, P])
     bind("e2ekt_f32_to_frag", S, [P, P, I, I, I, P])
@@ -155,6 +161,33 @@ def conv_bf16_supported(**kw) -> bool:
 
 def conv_bf16_class(**kw) -> str:
     return load().e2ekt_conv_bf16_class(*_flat(BCONV_ARGS, BCONV_DEFAULTS, kw)).decode()
+
+
+def _group_call(fn, spec, defaults, members, stream):
+    """One ctypes array of len(members) per argument of `spec`, in its order."""
+    n = len(members)
+    names = {nm for nm, _ in spec}
+    bad = {k for m in members for k in m if k not in names}
+    missing = {nm for m in members for nm in names if nm not in m and nm not in defaults}
+    if bad or missing:
+        raise TypeError(f"unknown arguments {sorted(bad)}, missing arguments {sorted(missing)}")
+    keep = []
+    for name, t in spec:
+        vals = [{**defaults, **m}[name] for m in members]
+        keep.append((t * n)(*vals))
+    r = fn(n, *[C.addressof(a) for a in keep], stream)
+    del keep
+    return _msg(r)
+
+
+def conv_bf16_group(members, stream=None):
+    """members: 1 .. 4 dicts of conv_bf16's arguments (rows_hint is the group's own)."""
+    return _group_call(load().e2ekt_conv_bf16_group, BCONV_GROUP_ARGS, BCONV_DEFAULTS, members, stream)
+
+
+def pair_bf16_group(members, stream=None):
+    """members: 1 .. 4 dicts of pair_bf16's arguments (dense tensors: x_bs = out_bs = T * C; no wfrag / act_rows)."""
+    return _group_call(load().e2ekt_pair_bf16_group, PAIR_GROUP_ARGS, PAIR_DEFAULTS, members, stream)
 
 
 def x3_frag_bytes(Cout, KW, Cin) -> int:
@@ -293,6 +326,10 @@ def conv_post(x, w, bias, wav, pcm, B, N, C_, KW, stream=None, act_rows=None, ac
     r = load().e2ekt_conv_post(x, w, bias, wav, pcm, B, N, C_, KW, stream, act_rows, addr, C.addressof(xa) if xa is not None else None, x_div)
     del keep
     return _msg(r)
+
+
+def conv_post_bf16(x, w16, bias16, wav, pcm, B, N, C_, KW, fp16=False, stream=None):
+    return _msg(load().e2ekt_conv_post_bf16(x, w16, bias16, wav, pcm, B, N, C_, KW, stream, int(fp16)))
 
 
 def dwconv_swish(x, w, bias, out, B, N, C_, k, stream=None):

@@ -15,7 +15,14 @@ blocked in K by 32 as the kernel chunks: the factor 4 is a margin over that eval
 over the kernel's.  Where this departs from "one aggregate bar per launch": it is applied to launches of at least AGG_MIN_ELEMS elements (an
 RMS over a handful of elements is noise: with 4 elements a correct result misses a factor 4 by chance); launches with a tanh / swish / GELU
 epilogue carry it on the same launch with the activation switched off; and the yardstick's statistic is taken on the first utterances of
-a launch, YARD_MAX_ROWS rows at most (it is a property of the operand model and the data's distribution, which every utterance shares)."""
+a launch, YARD_MAX_ROWS rows at most (it is a property of the operand model and the data's distribution, which every utterance shares).
+
+16-bit activations (precisions "bf16_act" / "fp16_act"; the last section).  A 16-bit output leaves no room for such bars -- gamma_n S is a
+sizeable part of a bf16 ulp at realistic K and more than an fp16 ulp -- so these kernels are judged in two tiers.  Exact tier: inputs from
+dyadic grids whose partial sums are all exactly representable in float32 (act16_exactness states the precondition), so the output must
+equal a16_exact() bit for bit.  General tier: Gaussian data under an interval rule (the epilogue is monotone: chain(ref - bar) <= out <=
+chain(ref + bar), no element excluded) and an aggregate rule (the share of elements whose bits differ from chain(fl32(ref)) against the
+same share of the float32 yardstick)."""
 from __future__ import annotations
 
 import zlib
@@ -635,3 +642,382 @@ def dw_reference(c, x, w, bias):
     pre32 = lin.astype(np.float32)
     dev = act_deviation(pre32, ACT_SWISH, 0.0)
     return act64(lin, ACT_SWISH, 0.0), LIPSCHITZ[ACT_SWISH] * gamma(k + 1) * S + AGG_FACTOR * dev, dev
+
+
+# ---------------------------------------------------------------- 16-bit activations (precisions "bf16_act" / "fp16_act")
+# Written from BConvParams / PairParams (csrc/kernels.h) and the rounding tables of include/e2etts.h.  A 16-bit tensor is handled here as a
+# float32 array that holds 16-bit values (exact both ways); bits16 / from_bits16 move between that and the uint16 patterns the kernels see.
+#
+# Exact tier.  Activations, weights and bias are drawn from small dyadic grids, so every product is a multiple of one `unit` and every
+# partial sum of an output element, in ANY order, is a multiple of `unit` below 2^24 units: exactly representable in float32.  An
+# fp32-accumulating kernel must then deliver the exact sum whatever its order of terms, and the elementwise tail (one float32 operation on
+# 16-bit values and one nearest-even rounding per step) is fully determined: the kernel's output equals a16_exact() bit for bit.  The
+# precondition max S / unit < 2^24 (S = sum of |terms| of an element, bias included; unit = lowest set bit over the staged activations x
+# lowest set bit over the weights, and it divides the bias) is what act16_exactness() returns; tests/test_kernel_ref_host.py asserts it for
+# every case.  Residual and running sum enter after the accumulation and are arbitrary 16-bit data.
+#
+# General tier.  Gaussian data (non-dyadic conversions, rounding of the staged operands) under two rules: the interval rule -- every step of
+# the tail is monotone non-decreasing, so with ref the float64 sum over the staged 16-bit operands and bar = gamma_n S each output lies in
+# [chain(ref - bar), chain(ref + bar)], endpoints rounded outward to float32, no element excluded --, and the aggregate rule -- the share of
+# elements whose bits differ from chain(fl32(ref)) is at most AGG_FACTOR x the same share of conv_eval32 (blocked order) plus one element.
+# The aggregate rule needs flips to count, so its data carry a per-channel mean that the bias cancels (a16_data); plain zero-mean Gaussian
+# data, the distribution the engine sees and the one with the tightest intervals, goes under the interval rule at the case's own size.
+A16_BF16, A16_FP16 = 1, 2
+A16_NAME = {A16_BF16: "bf16_act", A16_FP16: "fp16_act"}
+A16_EXACT_LIMIT = 2.0 ** 24
+A16_GENERAL_MEAN = 6.0
+
+
+def act16_round(x, kind, how="rne"):
+    """float32 -> the nearest value of the element type (1: bf16, 2: IEEE binary16), ties to even, overflow to infinity, subnormals kept;
+    returned as float32.  how (mutations, tests only): 'rtz' rounds toward zero, 'rha' sends ties away from zero, 'sat' saturates fp16 overflow at 65504, 'ftz' flushes
+    fp16 subnormal results to zero."""
+    x = np.ascontiguousarray(x, np.float32)
+    if how == "rha":             # mutation: ties away from zero instead of to even
+        if kind == A16_BF16:
+            u = x.view(np.uint32)
+            return (((u + np.uint32(0x8000)) >> np.uint32(16)) << np.uint32(16)).view(np.float32)
+        with np.errstate(over="ignore"):
+            r = x.astype(np.float16)
+            dn = np.where(np.abs(r.astype(np.float32)) > np.abs(x), np.nextafter(r, np.float16(0)), r)
+            up = np.nextafter(dn, np.copysign(np.float16(np.inf), x).astype(np.float16))
+            tie = np.isfinite(up) & (np.abs(x.astype(np.float64) - dn.astype(np.float64)) == np.abs(up.astype(np.float64) - x.astype(np.float64)))
+        return np.where(tie, up, r).astype(np.float32)
+    if how == "rtz":
+        if kind == A16_BF16:
+            return bf16_trunc(x)
+        with np.errstate(over="ignore"):
+            r = x.astype(np.float16).astype(np.float32)
+            back = np.nextafter(x.astype(np.float16), np.float16(0)).astype(np.float32)
+        return np.where(np.abs(r) > np.abs(x), back, r).astype(np.float32)
+    if kind == A16_BF16:
+        return bf16_round(x)
+    with np.errstate(over="ignore"):
+        r = x.astype(np.float16).astype(np.float32)
+    if how == "sat":
+        r = np.where(np.isinf(r) & np.isfinite(x), np.sign(x) * np.float32(65504.0), r).astype(np.float32)
+    if how == "ftz":
+        r = np.where(np.abs(r) < np.float32(2.0 ** -14), np.copysign(np.float32(0), r), r).astype(np.float32)
+    return r
+
+
+def bits16(x, kind):
+    """float32 holding 16-bit values -> their uint16 patterns (rounds to nearest-even when it does not)."""
+    if kind == A16_FP16:
+        with np.errstate(over="ignore"):
+            return np.ascontiguousarray(np.asarray(x, np.float32).astype(np.float16)).view(np.uint16)
+    return (np.ascontiguousarray(bf16_round(x)).view(np.uint32) >> np.uint32(16)).astype(np.uint16)
+
+
+def from_bits16(u, kind):
+    u = np.ascontiguousarray(u, np.uint16)
+    return u.view(np.float16).astype(np.float32) if kind == A16_FP16 else (u.astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def _lrelu32(v, slope):
+    """max(v, v * slope) in float32: BConvParams::act_slope / in_slope (slope in [0, 1]; 1 = identity)."""
+    return np.maximum(v, v * np.float32(slope)).astype(np.float32)
+
+
+def act16_stage(c, kind, x, adds=(), how="rne", drop_join=None):
+    """The operand a convolution stages from its input, float32 holding 16-bit values; the three forms of BConvParams:
+    fp32 input: round(lrelu(x)); 16-bit input: round(lrelu(x)), a slope of 1 copies; 16-bit join (in_add): x = r(r(r(in + a0) + a1) + a2),
+    then r(x / in_div), then r(lrelu(x)).  drop_join (mutation): index of a join rounding to leave out."""
+    r = lambda v: act16_round(v, kind, how)   # noqa: E731
+    x = np.asarray(x, np.float32)
+    slope = c["in_slope"]
+    if not c["in16"]:
+        assert not adds
+        return r(_lrelu32(x, slope) if slope != 1.0 else x)
+    if not adds:
+        return x if slope == 1.0 else r(_lrelu32(x, slope))
+    v = x
+    for i, a in enumerate(adds):
+        v = (v + np.asarray(a, np.float32)).astype(np.float32)
+        if drop_join != i:
+            v = r(v)
+    if c["in_div"] != 1.0:
+        v = r((v / np.float32(c["in_div"])).astype(np.float32))
+    return r(_lrelu32(v, slope))
+
+
+def act16_chain(pre32, c, res16, old16, kind, how="rne", mut=None):
+    """The epilogue of conv_bf16_kernel with 16-bit activations on pre32 = fl32(accumulator + bias): round; activation, round; + residual,
+    round; + running sum, round; / out_div, round -- each step present only when the launch asks for it.  mut (tests only): 'drop_bias_round',
+    'res_before_act', 'div_before'."""
+    r = lambda v: act16_round(v, kind, how)   # noqa: E731
+    v = np.asarray(pre32, np.float32)
+    if mut != "drop_bias_round":
+        v = r(v)
+    if mut == "res_before_act" and res16 is not None:
+        v = r((v + res16).astype(np.float32))
+    if c["act_slope"] != 1.0:
+        v = r(_lrelu32(v, c["act_slope"]))
+    if res16 is not None and mut != "res_before_act":
+        v = r((v + res16).astype(np.float32))
+    dv = np.float32(c["out_div"])
+    if mut == "div_before":
+        assert old16 is not None and c["out_div"] != 1.0
+        return r((old16 + r((v / dv).astype(np.float32))).astype(np.float32))
+    if old16 is not None:
+        v = r((v + old16).astype(np.float32))
+        if c["out_div"] != 1.0:
+            v = r((v / dv).astype(np.float32))
+    return v
+
+
+def _grid(r, shape, kmax, exp, neg=None, kmin=0):
+    k = r.integers(-kmax, kmax + 1, shape)
+    if kmin:                     # |k| in [kmin, kmax]
+        k = r.integers(kmin, kmax + 1, shape) * r.choice(np.array([-1, 1]), shape)
+    if neg is not None:          # negatives restricted to a few coarse values (a non-dyadic staging slope)
+        k = np.where(k < 0, np.asarray(neg)[r.integers(0, len(neg), shape)], k)
+    return (k * 2.0 ** exp).astype(np.float32)
+
+
+def a16_grids(c, kind):
+    """(x, w, addend, fine bits of an fp32 input) grids of a case as (kmax, exponent).  Default: x in {-48..48} 2^-4, w in {-16..16} 2^-6,
+    bias on the x grid; for fp16 both finer by 2^-2 (unless the case says fine16 = False).  Addends of a join lie on a finer grid than x so
+    that the join's roundings change their sums; an fp32 input carries `fb` more bits than the element type keeps, for the same reason."""
+    sh = -2 if (kind == A16_FP16 and c["fine16"]) else 0
+    xg = (c["xg"][0], c["xg"][1] + sh)
+    wg = (c["wg"][0], c["wg"][1] + sh)
+    ag = c["ag"][kind] if isinstance(c["ag"], dict) else c["ag"] if c["ag"] is not None else ((48, xg[1] - 3) if kind == A16_BF16 else (48, xg[1] - 7))
+    fb = c["fb"] if c["fb"] is not None else (3 if kind == A16_BF16 else 6)
+    return xg, wg, ag, fb
+
+
+def a16_data(c, kind, tier="exact"):
+    """Seeded inputs of a 16-bit-activation case: x [B, T, Cin] (float32; 16-bit values when the case's input is 16-bit), adds, w
+    [Cout, KW, Cin] float32, bias, res, old (16-bit values).  tier 'exact': grid data; 'general': Gaussian about a per-channel mean;
+    'zero_mean': plain Gaussian."""
+    r = rng_of(f"{c['name']}/{kind}/{tier}")
+    B, T, Cin, Cout, KW = c["B"], c["T"], c["Cin"], c["Cout"], c["KW"]
+    rnd = lambda v: act16_round(v, kind)   # noqa: E731
+    if tier == "exact":
+        xg, wg, ag, fb = a16_grids(c, kind)
+        if c["in16"]:
+            x = _grid(r, (B, T, Cin), xg[0], xg[1], c["neg"], c["kmin"])
+            assert np.array_equal(x, rnd(x)), "the x grid is not representable in the element type"
+        else:
+            x = _grid(r, (B, T, Cin), xg[0] << fb, xg[1] - fb)
+        adds = [_grid(r, (B, T, Cin), ag[0], ag[1]) for _ in range(c["n_add"])]
+        w = _grid(r, (Cout, KW, Cin), wg[0], wg[1])
+        assert np.array_equal(w, rnd(w)) and all(np.array_equal(a, rnd(a)) for a in adds)
+        bias = _grid(r, (Cout,), xg[0], xg[1]) if c["bias"] else None
+        rs = np.float32(c["xg"][0] * 2.0 ** xg[1] / 3)          # residual / running sum: arbitrary 16-bit data of the x grid's magnitude
+    else:
+        # Gaussian about a mean of A16_GENERAL_MEAN standard deviations whose sign goes with the channel, in x and in w alike: the products
+        # of a channel then share a sign, the partial sums grow an order of magnitude past the result, and the bias (below) takes the
+        # columns' mean sum away again.  Zero-mean data leaves a float32 order difference so little room to move a 16-bit result (a share
+        # of 4e-6 for bf16) that the aggregate rule would compare counts of 0, 1 and 2.
+        # tier 'zero_mean': plain Gaussian data, the ordinary distribution; judged by the interval rule alone.
+        mean = 0.0 if tier == "zero_mean" else A16_GENERAL_MEAN
+        sgn = r.choice(np.array([-1.0, 1.0], np.float32), Cin)
+        x = (r.standard_normal((B, T, Cin), np.float32) + np.float32(mean) * sgn).astype(np.float32)
+        x = rnd(x) if c["in16"] else x
+        adds = [rnd(r.standard_normal((B, T, Cin), np.float32)) for _ in range(c["n_add"])]
+        w = ((r.standard_normal((Cout, KW, Cin), np.float32) + np.float32(mean) * sgn) / np.float32(max(mean, 1.0) * np.sqrt(KW * Cin)))
+        bias = r.standard_normal(Cout, np.float32) if c["bias"] else None
+        rs = np.float32(1.0)
+    if c["zts"]:
+        w[:c["zts"], 2, :] = 0
+        w[c["zts"]:, 0, :] = 0
+    if tier != "exact" and bias is not None:
+        cc = dict(c, B=min(B, 4))
+        lin = a16_sum64(cc, kind, dict(x=x[:4], adds=[a[:4] for a in adds], w=w, bias=None))[0]
+        bias = (bias - lin.mean((0, 1))).astype(np.float32)
+    res = rnd(rs * r.standard_normal((B, T, Cout), np.float32)) if c["res"] else None
+    old = rnd(rs * r.standard_normal((B, T, Cout), np.float32)) if c["accumulate"] else None
+    return dict(x=x, adds=adds, w=w, bias=bias, res=res, old=old)
+
+
+def _a16_operands(c, kind, d, how="rne", drop_join=None):
+    """(A [B T, K] float32, W [Cout, K] float32): the staged 16-bit operands, gathered tap-major."""
+    st = act16_stage(c, kind, d["x"], d["adds"], how, drop_join)
+    a = conv_gather(dict(c, in_slope=1.0), st)
+    return a.reshape(c["B"] * c["T"], c["KW"] * c["Cin"]), act16_round(d["w"], kind).reshape(c["Cout"], c["KW"] * c["Cin"])
+
+
+def _lsb(v):
+    """The lowest set bit over the nonzero elements of a float32 array (inf when there is none)."""
+    v = np.abs(np.asarray(v, np.float64).ravel())
+    v = v[v > 0]
+    if v.size == 0:
+        return np.inf
+    m, e = np.frexp(v)
+    q = np.round(m * 2.0 ** 53).astype(np.int64)
+    return float(np.min((q & -q).astype(np.float64) * 2.0 ** (e - 53)))
+
+
+def act16_exactness(c, kind, d=None):
+    """max over the output elements of S / unit for the exact-tier data of a case (A16_EXACT_LIMIT = 2^24 is the precondition of the
+    tier); inf when the bias is no multiple of the unit.  Returns (ratio, unit)."""
+    d = d or a16_data(c, kind)
+    a, w = _a16_operands(c, kind, d)
+    unit = _lsb(a) * _lsb(w)
+    S = np.abs(a.astype(np.float64)) @ np.abs(w.astype(np.float64)).T
+    if d["bias"] is not None:
+        q = d["bias"].astype(np.float64) / unit
+        if not np.array_equal(q, np.round(q)):
+            return np.inf, unit
+        S = S + np.abs(d["bias"]).astype(np.float64)
+    return float(S.max() / unit), unit
+
+
+def a16_sum64(c, kind, d, how="rne", drop_join=None):
+    """(ref, S, n): the float64 sum over the staged 16-bit operands plus the bias [B, T, Cout], the sum of |terms|, the number of terms."""
+    a, w = _a16_operands(c, kind, d, how, drop_join)
+    a, w = a.astype(np.float64), w.astype(np.float64)
+    ref, S = a @ w.T, np.abs(a) @ np.abs(w).T
+    n = c["KW"] * c["Cin"]
+    if d["bias"] is not None:
+        ref, S, n = ref + d["bias"].astype(np.float64), S + np.abs(d["bias"]).astype(np.float64), n + 1
+    shp = (c["B"], c["T"], c["Cout"])
+    return ref.reshape(shp), S.reshape(shp), n
+
+
+def a16_exact(c, kind, d):
+    """The exact tier's expected output (float32 holding 16-bit values): the exact sum, which under the tier's precondition is a float32,
+    through the epilogue."""
+    ref, _, _ = a16_sum64(c, kind, d)
+    pre32 = ref.astype(np.float32)
+    assert np.array_equal(pre32.astype(np.float64), ref), "the exact sum is no float32: the exactness condition does not hold"
+    return act16_chain(pre32, c, d["res"], d["old"], kind)
+
+
+def a16_eval32(c, kind, d, order="blocked", mut=None):
+    """A float32 evaluation of the launch (conv_eval32's orders on the staged operands), through the epilogue.  mut (tests only):
+    drop_bias_round, rtz, rha, res_before_act, div_before, drop_join, drop_tap_last_row, tail_not_zeroed, sat, ftz."""
+    how = mut if mut in ("rtz", "rha", "sat", "ftz") else "rne"
+    st = act16_stage(c, kind, d["x"], d["adds"], how, 0 if mut == "drop_join" else None)
+    w16 = act16_round(d["w"], kind)
+    cc = dict(c, in_slope=1.0, act=ACT_NONE, lens=None)
+    dd = dict(x=st, w=w16, bias=None, res=None, old=None)
+    if mut == "drop_tap_last_row":       # the slab's last row is never seen by the last tap: one output row loses one tap
+        t = c["T"] - 1 + c["pad"] - (c["KW"] - 1) * c["dil"]
+        assert 0 <= t < c["T"]
+        acc = conv_eval32(dict(cc, accumulate=False, out_div=1.0), dd, 0, order)
+        a_last = st[:, c["T"] - 1, :]                                     # [B, Cin]
+        acc[:, t, :] = (acc[:, t, :] - a_last @ w16[:, c["KW"] - 1, :].T).astype(np.float32)
+    else:
+        acc = conv_eval32(dict(cc, accumulate=False, out_div=1.0), dd, 0, order)
+    if mut == "tail_not_zeroed":         # the channels past Cin of the last 32-channel chunk hold the slab's clamped read instead of zeros
+        assert c["Cin"] % 32
+        ph = conv_gather(cc, st)[:, :, :, -8:].reshape(c["B"], c["T"], -1) @ w16[:, :, -8:].reshape(c["Cout"], -1).T
+        acc = (acc + ph).astype(np.float32)
+    pre32 = (acc + d["bias"]).astype(np.float32) if d["bias"] is not None else acc
+    cm = mut if mut in ("drop_bias_round", "res_before_act", "div_before") else None
+    return act16_chain(pre32, c, d["res"], d["old"], kind, how, cm)
+
+
+def _outward32(v, up):
+    f = v.astype(np.float32)
+    with np.errstate(over="ignore"):
+        if up:
+            return np.where(f.astype(np.float64) < v, np.nextafter(f, np.float32(np.inf)), f).astype(np.float32)
+        return np.where(f.astype(np.float64) > v, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def a16_general_reference(c, kind, d):
+    """dict(lo, hi, mid, one_value): the interval rule's endpoints [chain(ref - bar), chain(ref + bar)] (outward-rounded float32 through the
+    epilogue), mid = chain(fl32(ref)), and the share of elements whose interval holds one value."""
+    ref, S, n = a16_sum64(c, kind, d)
+    bar = gamma(n) * S
+    lo = act16_chain(_outward32(ref - bar, False), c, d["res"], d["old"], kind)
+    hi = act16_chain(_outward32(ref + bar, True), c, d["res"], d["old"], kind)
+    mid = act16_chain(ref.astype(np.float32), c, d["res"], d["old"], kind)
+    return dict(lo=lo, hi=hi, mid=mid, one_value=float(np.mean(lo == hi)))
+
+
+def flip_share(got, mid, kind):
+    return float(np.mean(bits16(got, kind) != bits16(mid, kind)))
+
+
+A16_GENERAL_ELEMS = (2 ** 18, 2 ** 17)     # K < 1024, K >= 1024
+
+
+def a16_general_case(c):
+    """The launch the general tier judges: the case with as many utterances as give the aggregate rule a count to compare -- a share of
+    flips of 1e-4 (the float32 yardstick's at K = 24 with bf16 elements: u sqrt(K) against an ulp of 2^-8) is 0, 1 or 2 elements of a
+    launch of 8192 by chance alone, whatever computed it; of 2^18 elements it is some twenty.  Same T, channels, kernel and options."""
+    want = A16_GENERAL_ELEMS[0 if c["KW"] * c["Cin"] < 1024 else 1]
+    per = c["T"] * c["Cout"]
+    return dict(c, B=max(c["B"], -(-want // per)), rows_hint=c["rows_hint"] or c["B"] * c["T"])    # rows_hint: the tile shape the case names
+
+
+def check_a16_interval(c, kind, d, got):
+    """The interval rule alone (launches of zero-mean Gaussian data, at the case's own size): (elements outside, one-value share)."""
+    ref = a16_general_reference(c, kind, d)
+    with np.errstate(invalid="ignore"):
+        inside = (got >= ref["lo"]) & (got <= ref["hi"])
+    return int(np.sum(~inside)), ref["one_value"]
+
+
+def check_a16_general(c, kind, d, got, ref=None, yard=None):
+    """Both rules of the general tier on `got` (float32 holding 16-bit values).  yard: the flip share of conv_eval32's blocked order
+    (computed when not given).  The aggregate rule applies to launches of at least AGG_MIN_ELEMS elements."""
+    ref = ref or a16_general_reference(c, kind, d)
+    with np.errstate(invalid="ignore"):
+        inside = (got >= ref["lo"]) & (got <= ref["hi"])
+    share = flip_share(got, ref["mid"], kind)
+    agg_ok, ys = True, None
+    if got.size >= AGG_MIN_ELEMS:
+        ys = flip_share(a16_eval32(c, kind, d), ref["mid"], kind) if yard is None else yard
+        agg_ok = share <= AGG_FACTOR * ys + 1.0 / got.size
+    ok = bool(np.all(inside)) and agg_ok
+    why = "" if ok else f"{int(np.sum(~inside))} elements outside their interval; flip share {share:.4g} against the yardstick's {ys}"
+    return dict(ok=ok, outside=int(np.sum(~inside)), share=share, yard=ys, one_value=ref["one_value"], why=why)
+
+
+def a16_image_reference(w, kind, tap_split=0):
+    """The weight image of launch_bf16_image / launch_f16_image as uint16 [Cout / 32][chunk][tap slot][k-step 0..1][lane 0..63][8]: lane l of
+    tile t holds output channel 32 t + l % 32, input channels 32 chunk + 16 k-step + 8 (l / 32) + 0..7, zeros past Cin; with tap_split
+    (KW == 3) tap slot s of tile t is tap s + (32 t >= tap_split)."""
+    Cout, KW, Cin = w.shape
+    nch, KWe = (Cin + 31) // 32, (2 if tap_split else KW)
+    wp = np.zeros((Cout, KW, nch * 32), np.float32)
+    wp[:, :, :Cin] = w
+    img = np.zeros((Cout // 32, nch, KWe, 2, 64, 8), np.uint16)
+    b = bits16(wp, kind).reshape(Cout // 32, 32, KW, nch, 2, 2, 8)        # [tile, n, tap, chunk, k-step, half, 8]
+    for t in range(Cout // 32):
+        j0 = 1 if (tap_split and 32 * t >= tap_split) else 0
+        for s in range(KWe):
+            # -> [chunk, k-step, half, n, 8] -> lanes = half * 32 + n
+            img[t, :, s] = b[t, :, s + j0].transpose(1, 2, 3, 0, 4).reshape(nch, 2, 64, 8)
+    return img
+
+
+# conv_post with 16-bit activations (launch_conv_post_bf16): x = r(lrelu_0.01(x)); y = r(conv + b); wav = r(tanh(y))
+def post16_data(c, kind):
+    r = rng_of(f"{c['name']}/post16/{kind}")
+    B, N, C, KW = c["B"], c["N"], c["C"], c["KW"]
+    rnd = lambda v: act16_round(v, kind)   # noqa: E731
+    return dict(x=rnd(r.standard_normal((B, N, C), np.float32)), w=rnd((r.standard_normal((KW, C)) * 0.6 / np.sqrt(KW * C)).astype(np.float32)),
+                bias=rnd(np.array([0.05], np.float32)))
+
+
+def post16_reference(c, kind, d):
+    """(lo, hi, dev): the interval of wav.  The pre-tanh sum is bracketed by gamma_n S, rounded; tanh is monotone, so wav lies in
+    [r(tanh(r(ref - bar)) - a), r(tanh(r(ref + bar)) + a)], a = AGG_FACTOR x the float32 tanh's largest deviation from float64 on this
+    case (post_reference's allowance for the device's tanhf)."""
+    rnd = lambda v: act16_round(v, kind)   # noqa: E731
+    x = d["x"]
+    x = rnd(np.where(x >= 0, x, x * np.float32(0.01)).astype(np.float32))
+    B, N, C, KW = c["B"], c["N"], c["C"], c["KW"]
+    pad = (KW - 1) // 2
+    xp = np.zeros((B, N + KW - 1, C), np.float64)
+    xp[:, pad:pad + N] = x
+    w = d["w"].astype(np.float64)
+    lin, S = np.zeros((B, N)), np.zeros((B, N))
+    for j in range(KW):
+        lin += xp[:, j:j + N] @ w[j]
+        S += np.abs(xp[:, j:j + N]) @ np.abs(w[j])
+    lin, S = lin + np.float64(d["bias"][0]), S + abs(float(d["bias"][0]))
+    bar = gamma(KW * C + 1) * S
+    ylo, yhi = rnd(_outward32(lin - bar, False)), rnd(_outward32(lin + bar, True))
+    dev = float(max(np.max(np.abs(np.tanh(y).astype(np.float64) - np.tanh(y.astype(np.float64)))) for y in (ylo, yhi)))
+    a = AGG_FACTOR * dev
+    lo = rnd(_outward32(np.tanh(ylo.astype(np.float64)) - a, False))
+    hi = rnd(_outward32(np.tanh(yhi.astype(np.float64)) + a, True))
+    return lo, hi, dev

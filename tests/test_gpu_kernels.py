@@ -10,7 +10,14 @@ An access outside a buffer but inside the band is therefore caught by value; not
 Rows past act_rows: the kernels skip whole TILES past act_rows[b]; the rows of the last tile past it may be written (with the value the
 padded launch gives them).  So rows < act_rows[b] are judged by the bars, rows >= act_rows[b] rounded up to the row tile of the kernel that
 runs must hold the sentinel, and the rows between must hold either.  The same goes for conv_post's 256-sample blocks and for the query blocks of
-attention under lens_host."""
+attention under lens_host.
+
+16-bit activations (precisions "bf16_act" / "fp16_act": launch_conv_bf16 with act16, launch_pair_bf16 in modes 3 / 4, launch_conv_post_bf16).
+A 16-bit output leaves no room for an error bar, so these are judged in two tiers (tests/kernel_ref.py, last section).  Exact tier: inputs
+from dyadic grids whose partial sums are exact in float32 in any order -- the output must equal the restatement bit for bit, on every
+element.  General tier: Gaussian data under an interval rule (each output between the epilogue of ref - bar and of ref + bar, no element
+excluded) and an aggregate rule (the share of elements that differ from the epilogue of fl32(ref), against 4 x the float32 yardstick's
+share plus one element).  The fused forms are tied to that reference bit for bit: pair = two convolutions, rb = three pairs, stage = rb's."""
 import json
 import os
 import subprocess
@@ -51,6 +58,7 @@ def kh():
     import kernel_harness
     import __graft_entry__ as g
     assert g.built_harness_hash() == g.harness_hash(), "libe2etts_kernels_test.so was not built from this tree: run build()"
+    assert g.built_harness_act16_hash() == g.harness_act16_hash(), "libe2etts_kernels_test.so was not built from this tree: run build()"
     kernel_harness.load()
     return kernel_harness
 
@@ -641,6 +649,366 @@ def test_act16_pair_chain_and_stage_forms_agree(kh, c, act16):
         assert kh.rb_bf16_group(mems, 3, B, T, C, T * C, T * C, act16=act16, stage=True) is None
         gst, ok2 = st.fetch()
         assert ok and ok2 and np.array_equal(gst, wants), "rb_bf16_stage with 16-bit activations differs from the accumulated rb_bf16 launches"
+
+
+# ---------------------------------------------------------------- 16-bit activations, per element (kernel_ref's last section)
+KINDS = [kr.A16_BF16, kr.A16_FP16]
+KIND_IDS = ["bf16_act", "fp16_act"]
+
+
+def _g16(x, kind):
+    return Guarded(kr.bits16(x, kind))
+
+
+def _out16(shape, old=None, kind=None):
+    return _g16(old, kind) if old is not None else Guarded(shape=shape, dtype=np.uint16, sentinel=SENT16)
+
+
+def _wimage(kh, w, kind, tap_split=0):
+    """(source buffer, image buffer as uint16) of weights [Cout, KW, Cin]: launch_f16_image from the fp32 weights for fp16, else
+    launch_bf16_image from the split-precision image (kind 0 = mode 2 and bf16 activations share it)."""
+    Cout, KW, Cin = w.shape
+    fp16 = kind == kr.A16_FP16
+    src = Guarded(w.reshape(Cout, KW * Cin) if fp16 else kr.pack_x3(w))
+    img = Guarded(shape=(kh.bf16_image_bytes(Cout, KW, Cin, tap_split) // 2,), dtype=np.uint16, sentinel=SENT16)
+    msg = (kh.f16_image if fp16 else kh.bf16_image)(src.ptr, img.ptr, Cout, KW, Cin, tap_split)
+    assert msg is None, msg
+    bits, ok = img.fetch()
+    assert ok and src.unchanged(), "the image maker wrote outside its buffer or changed its input"
+    img.host = img.dev.cpu().numpy().copy()          # an input from here on
+    return src, img, bits.reshape(-1)
+
+
+class A16Rig:
+    """Device buffers of one 16-bit-activation launch of conv_bf16 (a case of kernel_cases.A16_CASES, data of kernel_ref.a16_data)."""
+
+    def __init__(self, kh, c, kind, d):
+        self.kh, self.c, self.kind, self.d = kh, c, kind, d
+        self.x = _g16(d["x"], kind) if c["in16"] else Guarded(d["x"])
+        self.adds = [_g16(a, kind) for a in d["adds"]]
+        self.src, self.img, self.img_bits = _wimage(kh, d["w"], kind, c["zts"])
+        self.bias = Guarded(d["bias"]) if d["bias"] is not None else None
+        self.res = _g16(d["res"], kind) if d["res"] is not None else None
+
+    def args(self, out):
+        c = self.c
+        ad = [a.ptr for a in self.adds] + [None] * 3
+        return dict(**{"in": self.x.ptr}, in_bf16=int(c["in16"]), in_slope=c["in_slope"], in_add0=ad[0], in_add1=ad[1], in_add2=ad[2], in_div=c["in_div"],
+                    wimg=self.img.ptr, KWe=2 if c["zts"] else c["KW"], tap_split=c["zts"], bias=self.bias.ptr if self.bias else None,
+                    act_slope=c["act_slope"], res=self.res.ptr if self.res else None, accumulate=int(c["accumulate"]), out_div=c["out_div"], out_b=out.ptr,
+                    B=c["B"], T=c["T"], Cin=c["Cin"], Cout=c["Cout"], KW=c["KW"], dil=c["dil"], pad=c["pad"], rows_hint=c["rows_hint"], act16=self.kind)
+
+    def inputs_unchanged(self):
+        return all(g is None or g.unchanged() for g in [self.x, self.src, self.img, self.bias, self.res] + self.adds)
+
+    def run(self):
+        """Launch; the output as float32 holding 16-bit values.  Bands intact, inputs unchanged."""
+        c = self.c
+        out = _out16((c["B"], c["T"], c["Cout"]), self.d["old"], self.kind)
+        assert self.kh.conv_bf16_class(**self.args(out)) == c["reach"]["bcls"]
+        msg = self.kh.conv_bf16(**self.args(out))
+        assert msg is None, (c["name"], msg)
+        got, ok = out.fetch()
+        assert ok, f"{c['name']}: wrote outside the output (guard band changed)"
+        assert self.inputs_unchanged(), f"{c['name']}: an input buffer changed"
+        return kr.from_bits16(got, self.kind)
+
+
+def _describe_mismatch(got, want, kind):
+    bad = np.argwhere(kr.bits16(got, kind) != kr.bits16(want, kind))
+    first = [(tuple(int(i) for i in ix), float(got[tuple(ix)]), float(want[tuple(ix)])) for ix in bad[:6]]
+    return f"{len(bad)} of {got.size} elements differ; rows {sorted({int(i[1]) for i in bad})[:12]}, columns {sorted({int(i[2]) for i in bad})[:12]}; (index, got, want) {first}"
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("c", kc.A16_CASES, ids=lambda c: c["name"])
+def test_conv_bf16_act16_exact_and_general(kh, c, kind):
+    """launch_conv_bf16 with 16-bit activations.  Exact tier: on grid data whose sums are exact in float32 in any order, every output
+    element equals the restatement bit for bit.  General tier (launches of at least AGG_MIN_ELEMS elements): zero-mean Gaussian data under the
+    interval rule at the case's own size; Gaussian data about a cancelling mean, in a launch large enough to count flips, under the interval
+    rule on every element and the aggregate rule on the share of flipped elements."""
+    d = kr.a16_data(c, kind)
+    want = kr.a16_exact(c, kind, d)
+    got = A16Rig(kh, c, kind, d).run()
+    same = kr.bits16(got, kind) == kr.bits16(want, kind)
+    print(f"conv_bf16 act16 {c['name']} {kr.A16_NAME[kind]}: exact tier {int(np.sum(~same))} of {same.size} elements differ")
+    record("act16_exact", case=c["name"], kind=kind, differ=int(np.sum(~same)), elems=int(same.size))
+    assert np.all(same), (c["name"], kr.A16_NAME[kind], _describe_mismatch(got, want, kind))
+    if same.size < kr.AGG_MIN_ELEMS:
+        return
+    z = kr.a16_data(c, kind, "zero_mean")          # plain Gaussian data at the case's own size: the interval rule alone
+    outside, one_value = kr.check_a16_interval(c, kind, z, A16Rig(kh, c, kind, z).run())
+    print(f"conv_bf16 act16 {c['name']} {kr.A16_NAME[kind]}: zero-mean data: {outside} of {same.size} outside their interval, one-value intervals {one_value:.3g}")
+    record("act16_zero_mean", case=c["name"], kind=kind, outside=outside, one_value=one_value, elems=int(same.size))
+    assert outside == 0, (c["name"], kr.A16_NAME[kind], outside)
+    cg = kr.a16_general_case(c)
+    g = kr.a16_data(cg, kind, "general")
+    gg = A16Rig(kh, cg, kind, g).run()
+    r = kr.check_a16_general(cg, kind, g, gg)
+    print(f"conv_bf16 act16 {c['name']} {kr.A16_NAME[kind]}: general tier over {gg.size} elements: {r['outside']} outside their interval, flip share "
+          f"{r['share']:.3g} (yardstick {r['yard']:.3g}), one-value intervals {r['one_value']:.3g}")
+    record("act16_general", case=c["name"], kind=kind, outside=r["outside"], share=r["share"], yard=r["yard"], one_value=r["one_value"], elems=int(gg.size))
+    assert r["ok"], (c["name"], kr.A16_NAME[kind], r["why"])
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("name", ["a_128x32_t1", "a_128x32_t31", "a_128x32_t33_pre", "a_32x128_poly", "a_64x128_t64"])
+def test_weight_images_hold_the_rounded_weights_in_the_documented_order(kh, name, kind):
+    """launch_bf16_image / launch_f16_image: the image decoded on the host is the weights rounded once, in kernels.h's order (Cin 8, 40 and 80:
+    the zeroed channel tail; the polyphase image's two live taps per tile)."""
+    c = kc.A16_BY_NAME[name]
+    w = kr.a16_data(c, kind, "general")["w"]
+    _, _, bits = _wimage(kh, w, kind, c["zts"])
+    want = kr.a16_image_reference(w, kind, c["zts"]).reshape(-1)
+    assert bits.shape == want.shape
+    bad = np.flatnonzero(bits != want)
+    assert bad.size == 0, f"{bad.size} image elements differ, first at {bad[:8]}"
+
+
+def _bconv2(kh, c, img, **a):
+    act_slope = {kc.ACT_NONE: 1.0, kc.ACT_RELU: 0.0, kc.ACT_LRELU: c["act_slope"]}[c["act"]]
+    base = dict(wimg=img.ptr, KWe=2 if c["zts"] else c["KW"], tap_split=c["zts"], act_slope=act_slope, accumulate=int(c["accumulate"]), out_div=c["out_div"],
+                B=c["B"], T=c["T"], Cin=c["Cin"], Cout=c["Cout"], KW=c["KW"], dil=c["dil"], pad=c["pad"], in_slope=c["in_slope"])
+    return kh.conv_bf16(**{**base, **a})
+
+
+def test_conv_bf16_mode2_handovers(kh):
+    """Mode 2's options that no other kernel-level test launches, each against a launch that test_conv_bf16 holds to float64: a bf16 input
+    (in_bf16) gives the bits of the fp32 launch on the same bf16 values; in_add / in_div gives the bits of a launch on the input summed
+    beforehand in numpy float32 (the polyphase case); out_b is bf16(max(v, v * outb_slope)) of the same launch's fp32 out."""
+    by = {c["name"]: c for c in kc.BCONV_CASES}
+    # ---- in_bf16 (taken as it is: no input activation)
+    c = dict(by["b_64x64"], in_slope=1.0)
+    d = kr.conv_data(c)
+    x16 = kr.bf16_round(d["x"])
+    _, img, _ = _wimage(kh, d["w"], 0)
+    bias, res = Guarded(d["bias"]), Guarded(d["res"])
+    xa, xb = Guarded(x16), _g16(x16, kr.A16_BF16)
+    outs = []
+    for x, flag in ((xa, 0), (xb, 1)):
+        o = Guarded(shape=(c["B"], c["T"], c["Cout"]), sentinel=SENTINEL)
+        assert _bconv2(kh, c, img, **{"in": x.ptr}, in_bf16=flag, bias=bias.ptr, res=res.ptr, out=o.ptr) is None
+        got, ok = o.fetch()
+        assert ok and x.unchanged() and np.all(np.isfinite(got))
+        outs.append(got)
+    assert np.all(bits_equal(outs[0], outs[1])), "a bf16 input does not give the bits of the fp32 launch on the same values"
+    # ---- in_add / in_div on the polyphase case
+    c = by["b_poly"]
+    d = kr.conv_data(c)
+    r = kr.rng_of("b_poly_adds")
+    addh = [r.standard_normal(d["x"].shape, np.float32) for _ in range(3)]
+    _, img, _ = _wimage(kh, d["w"], 0, c["zts"])
+    bias = Guarded(d["bias"])
+    for n_add, div in ((1, 1.0), (2, 3.0), (3, 3.0)):
+        pre = d["x"]
+        for a in addh[:n_add]:
+            pre = (pre + a).astype(np.float32)
+        if div != 1.0:
+            pre = (pre / np.float32(div)).astype(np.float32)
+        x, xs, adds = Guarded(d["x"]), Guarded(pre), [Guarded(a) for a in addh[:n_add]]
+        ad = [a.ptr for a in adds] + [None] * 3
+        o1, o2 = (Guarded(shape=(c["B"], c["T"], c["Cout"]), sentinel=SENTINEL) for _ in range(2))
+        assert _bconv2(kh, c, img, **{"in": x.ptr}, in_add0=ad[0], in_add1=ad[1], in_add2=ad[2], in_div=div, bias=bias.ptr, out=o1.ptr) is None
+        assert _bconv2(kh, c, img, **{"in": xs.ptr}, bias=bias.ptr, out=o2.ptr) is None
+        (g1, ok1), (g2, ok2) = o1.fetch(), o2.fetch()
+        assert ok1 and ok2 and x.unchanged() and all(a.unchanged() for a in adds) and np.all(np.isfinite(g1))
+        assert np.all(bits_equal(g1, g2)), f"in_add x {n_add} / in_div {div} differs from the launch on the summed input"
+    # ---- out_b beside out
+    c = by["b_128x32"]
+    d = kr.conv_data(c)
+    _, img, _ = _wimage(kh, d["w"], 0)
+    x, bias = Guarded(d["x"]), Guarded(d["bias"])
+    for slope in (1.0, 0.1):
+        o, ob = Guarded(shape=(c["B"], c["T"], c["Cout"]), sentinel=SENTINEL), _out16((c["B"], c["T"], c["Cout"]))
+        assert _bconv2(kh, c, img, **{"in": x.ptr}, bias=bias.ptr, out=o.ptr, out_b=ob.ptr, outb_slope=slope) is None
+        (g, ok1), (gb, ok2) = o.fetch(), ob.fetch()
+        assert ok1 and ok2 and np.all(np.isfinite(g))
+        want = kr.bits16(np.maximum(g, g * np.float32(slope)).astype(np.float32), kr.A16_BF16)
+        assert np.array_equal(gb, want), "out_b is not bf16(max(v, v * outb_slope)) of the launch's own fp32 out"
+        ob2 = _out16((c["B"], c["T"], c["Cout"]))      # out_b alone
+        assert _bconv2(kh, c, img, **{"in": x.ptr}, bias=bias.ptr, out_b=ob2.ptr, outb_slope=slope) is None
+        assert np.array_equal(ob2.fetch()[0], want)
+
+
+PAIR16_CASES = kc.PAIR_CASES + [dict(kc.PAIR_CASES[0], name="pair_c32_t1", T=1), dict(kc.PAIR_CASES[1], name="pair_c64_t33", T=33),
+                                dict(kc.PAIR_CASES[2], name="pair_c128_t129", T=129)]
+
+
+def _pair16_setup(kh, name, B, T, C, KW, kind):
+    """Gaussian 16-bit x and running sum, weights and images of one pair; kind 0: mode 2 (fp32 tensors)."""
+    r = kr.rng_of(f"{name}/{kind}/{KW}")
+    xh, oldh = r.standard_normal((B, T, C), np.float32), r.standard_normal((B, T, C), np.float32)
+    pw = _pair_weights(f"{name}_w{KW}", C, KW, 1)[0]
+    k1, k2 = _wimage(kh, pw["w1"], kind), _wimage(kh, pw["w2"], kind)
+    if kind:
+        xh, oldh = kr.act16_round(xh, kind), kr.act16_round(oldh, kind)
+    return dict(xh=xh, oldh=oldh, x=_g16(xh, kind) if kind else Guarded(xh), b1=Guarded(pw["b1"]), b2=Guarded(pw["b2"]), i1=k1[1], i2=k2[1], keep=(k1, k2), pw=pw)
+
+
+def _pair_out(s, kind, accumulate, shape):
+    if kind:
+        return _out16(shape, s["oldh"] if accumulate else None, kind)
+    return Guarded(s["oldh"]) if accumulate else Guarded(shape=shape, sentinel=SENTINEL)
+
+
+def _pair_args(s, out, B, T, C, KW, dil, kind, accumulate, out_div):
+    return dict(x=s["x"].ptr, b1=s["b1"].ptr, b2=s["b2"].ptr, out=out.ptr, B=B, T=T, C=C, KW=KW, dil=dil, slope=0.1, accumulate=int(accumulate), out_div=out_div,
+                mode=2 + kind, bimg1=s["i1"].ptr, bimg2=s["i2"].ptr)
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("c", PAIR16_CASES, ids=lambda c: c["name"])
+def test_pair_bf16_act16_is_two_conv_bf16_launches(kh, c, kind):
+    """launch_pair_bf16 in mode 3 / 4 bit for bit against two launch_conv_bf16 launches with 16-bit activations -- launches of the kind
+    test_conv_bf16_act16_exact_and_general pins per element: h = r(lrelu(r(c1(r(lrelu(x))) + b1))), out = r(r(c2(h) + b2) + x) (+ sum, / div).
+    With test_act16_pair_chain_and_stage_forms_agree this ties rb_bf16 and rb_bf16_stage to the same reference."""
+    B, T, C, KW, dil = c["B"], c["T"], c["C"], c["KW"], c["dil"]
+    s = _pair16_setup(kh, c["name"], B, T, C, KW, kind)
+    fused = _pair_out(s, kind, c["accumulate"], (B, T, C))
+    pa = _pair_args(s, fused, B, T, C, KW, dil, kind, c["accumulate"], c["out_div"])
+    assert kh.pair_bf16_supported(x_bs=T * C, out_bs=T * C, **pa)
+    assert kh.pair_bf16(x_bs=T * C, out_bs=T * C, **pa) is None
+    got, ok = fused.fetch()
+    assert ok and s["x"].unchanged()
+    h = _out16((B, T, C))
+    two = _pair_out(s, kind, c["accumulate"], (B, T, C))
+    common = dict(in_bf16=1, B=B, T=T, Cin=C, Cout=C, KW=KW, KWe=KW, act16=kind)
+    assert kh.conv_bf16(**{"in": s["x"].ptr}, in_slope=0.1, wimg=s["i1"].ptr, bias=s["b1"].ptr, act_slope=0.1, out_b=h.ptr, dil=dil, pad=dil * (KW - 1) // 2, **common) is None
+    assert kh.conv_bf16(**{"in": h.ptr}, wimg=s["i2"].ptr, bias=s["b2"].ptr, res=s["x"].ptr, accumulate=int(c["accumulate"]), out_div=c["out_div"], out_b=two.ptr,
+                        dil=1, pad=(KW - 1) // 2, **common) is None
+    want, ok2 = two.fetch()
+    assert ok2 and h.fetch()[1] and np.all(np.isfinite(kr.from_bits16(want, kind)))
+    assert np.array_equal(got, want), _describe_mismatch(kr.from_bits16(got, kind), kr.from_bits16(want, kind), kind)
+
+
+GROUP_MEMBERS = [(3, 1), (7, 1), (11, 5), (3, 5)]       # (KW, dilation) of the members, longest halo not first
+
+
+@pytest.mark.parametrize("kind", [0] + KINDS, ids=["bf16"] + KIND_IDS)
+@pytest.mark.parametrize("n", [2, 4])
+def test_conv_bf16_group_members_get_what_they_get_alone(kh, n, kind):
+    """launch_conv_bf16_group in mode 2 and with 16-bit activations: members of different kernel size, dilation, weights and buffers; each
+    result is the member's own launch_conv_bf16, bit for bit (the group may run another tile shape: same order of terms)."""
+    B, T, Cin, Cout = 2, 129, 32, 64
+    mems, outs, rigs = [], [], []
+    for i, (KW, dil) in enumerate(GROUP_MEMBERS[:n]):
+        c = kc._acase(f"grp{i}", "", B, T, Cin, Cout, KW, dil, in_slope=0.1, act_slope=0.1 if i % 2 else 1.0, res=True, accumulate=bool(i % 2), out_div=3.0 if i % 2 else 1.0)
+        if kind:
+            d = kr.a16_data(c, kind, "general")
+            rig = A16Rig(kh, c, kind, d)
+            mk = lambda d=d, c=c: _out16((B, T, Cout), d["old"], kind)   # noqa: E731
+            base = {k: v for k, v in rig.args(mk()).items() if k != "rows_hint"}
+        else:
+            cd = dict(c, bias=True)
+            d = kr.conv_data(cd)
+            _, img, _ = _wimage(kh, d["w"], 0)
+            x, bias, res = Guarded(d["x"]), Guarded(d["bias"]), Guarded(d["res"])
+            rig = (x, bias, res, img)
+            mk = lambda d=d, c=c: Guarded(d["old"]) if c["accumulate"] else Guarded(shape=(B, T, Cout), sentinel=SENTINEL)   # noqa: E731
+            base = dict(**{"in": x.ptr}, in_slope=0.1, wimg=img.ptr, KWe=KW, bias=bias.ptr, act_slope=c["act_slope"], res=res.ptr, accumulate=int(c["accumulate"]),
+                        out_div=c["out_div"], B=B, T=T, Cin=Cin, Cout=Cout, KW=KW, dil=dil, pad=c["pad"])
+        alone, grouped = mk(), mk()
+        key = "out_b" if kind else "out"
+        assert kh.conv_bf16(**{**base, key: alone.ptr}) is None
+        mems.append({**base, key: grouped.ptr})
+        outs.append((alone, grouped))
+        rigs.append(rig)
+    assert kh.conv_bf16_group(mems) is None
+    for i, (alone, grouped) in enumerate(outs):
+        (a, ok1), (g, ok2) = alone.fetch(), grouped.fetch()
+        assert ok1 and ok2
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(g).view(np.uint8)), f"member {i} of {n} differs from its own launch"
+
+
+@pytest.mark.parametrize("kind", [0] + KINDS, ids=["bf16"] + KIND_IDS)
+@pytest.mark.parametrize("n", [2, 4])
+def test_pair_bf16_group_members_get_what_they_get_alone(kh, n, kind):
+    B, T, C = 2, 129, 32
+    mems, outs, keep = [], [], []
+    for i, (KW, dil) in enumerate(GROUP_MEMBERS[:n]):
+        s = _pair16_setup(kh, f"pgrp{i}", B, T, C, KW, kind)
+        acc, div = bool(i % 2), 3.0 if i % 2 else 1.0
+        alone, grouped = (_pair_out(s, kind, acc, (B, T, C)) for _ in range(2))
+        pa = _pair_args(s, alone, B, T, C, KW, dil, kind, acc, div)
+        assert kh.pair_bf16(x_bs=T * C, out_bs=T * C, **pa) is None
+        mems.append(dict(pa, out=grouped.ptr))
+        outs.append((alone, grouped))
+        keep.append(s)
+    assert kh.pair_bf16_group(mems) is None
+    for i, (alone, grouped) in enumerate(outs):
+        (a, ok1), (g, ok2) = alone.fetch(), grouped.fetch()
+        assert ok1 and ok2 and keep[i]["x"].unchanged()
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(g).view(np.uint8)), f"member {i} of {n} differs from its own launch"
+
+
+@pytest.mark.parametrize("kind", [0] + KINDS, ids=["bf16"] + KIND_IDS)
+def test_rb_bf16_group_of_three_members_get_what_they_get_alone(kh, kind):
+    """launch_rb_bf16_group with three members (kernel sizes 3, 7, 11; their own inputs, weights and dilations): each member's launch alone."""
+    B, T, C, n_pairs = 2, 257, 32, 3
+    mems, outs, keep = [], [], []
+    for i, (KW, dils) in enumerate([(3, [1, 3, 5]), (7, [1, 3, 5]), (11, [5, 1, 3])]):
+        ss = [_pair16_setup(kh, f"rbgrp{i}_{m}", B, T, C, KW, kind) for m in range(n_pairs)]
+        acc, div = bool(i % 2), 3.0 if i % 2 else 1.0
+        alone, grouped = (_pair_out(ss[0], kind, acc, (B, T, C)) for _ in range(2))
+        mem = dict(x=ss[0]["x"].ptr, bimg=[(s["i1"].ptr, s["i2"].ptr) for s in ss], b1=[s["b1"].ptr for s in ss], b2=[s["b2"].ptr for s in ss], dil=dils, KW=KW,
+                   accumulate=int(acc), out_div=div)
+        assert kh.rb_bf16_supported([dict(mem, out=alone.ptr)], n_pairs, B, T, C, T * C, T * C, act16=kind)
+        assert kh.rb_bf16_group([dict(mem, out=alone.ptr)], n_pairs, B, T, C, T * C, T * C, act16=kind) is None
+        mems.append(dict(mem, out=grouped.ptr))
+        outs.append((alone, grouped))
+        keep.append(ss)
+    assert kh.rb_bf16_group(mems, n_pairs, B, T, C, T * C, T * C, act16=kind) is None
+    for i, (alone, grouped) in enumerate(outs):
+        (a, ok1), (g, ok2) = alone.fetch(), grouped.fetch()
+        assert ok1 and ok2 and keep[i][0]["x"].unchanged()
+        assert np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(g).view(np.uint8)), f"member {i} differs from its own launch"
+
+
+def test_mixed_groups_are_refused_and_write_nothing(kh):
+    """A group whose members differ in element kind or geometry returns the documented message before any launch."""
+    B, T, Cin, Cout = 2, 65, 32, 64
+    c = kc._acase("grp_refuse", "", B, T, Cin, Cout, 3)
+    rigs = [A16Rig(kh, c, kind, kr.a16_data(c, kind, "general")) for kind in KINDS]
+    outs = [_out16((B, T, Cout)) for _ in rigs]
+    ms = [{k: v for k, v in r.args(o).items() if k != "rows_hint"} for r, o in zip(rigs, outs)]
+    share = "the members of a group share"
+    assert share in kh.conv_bf16_group(ms)                                                        # bf16 beside fp16
+    assert share in kh.conv_bf16_group([ms[0], dict(ms[0], T=T - 1)])                             # another T
+    assert share in kh.conv_bf16_group([ms[0], dict(ms[0], Cin=Cin - 8)])
+    assert "1 .. 4 members" in kh.conv_bf16_group([ms[0]] * 5)
+    assert "16-bit activations write the 16-bit output alone" in kh.conv_bf16_group([ms[0], dict(ms[0], out=outs[0].ptr)])
+    ss = [_pair16_setup(kh, "pgrp_refuse", B, T, 32, 3, kind) for kind in KINDS]
+    pouts = [_out16((B, T, 32)) for _ in ss]
+    pm = [_pair_args(s, o, B, T, 32, 3, 1, kind, False, 1.0) for s, o, kind in zip(ss, pouts, KINDS)]
+    assert share in kh.pair_bf16_group(pm) and share in kh.pair_bf16_group([pm[0], dict(pm[0], T=T - 1)])
+    for o in outs + pouts:
+        got, ok = o.fetch()
+        assert ok and np.all(got == SENT16), "a refused group wrote something"
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+@pytest.mark.parametrize("c", kc.POST_CASES, ids=lambda c: c["name"])
+def test_conv_post_act16(kh, c, kind):
+    """launch_conv_post_bf16 in both element types (POST_CASES geometry, no join): wav holds 16-bit values inside the interval the rounded
+    pre-tanh bounds give through tanh (widened by AGG_FACTOR x the float32 tanh's own deviation, post_reference's allowance for the device's
+    tanhf); pcm is kr.pcm_of the kernel's own wav, exactly."""
+    B, N, C, KW = c["B"], c["N"], c["C"], c["KW"]
+    d = kr.post16_data(c, kind)
+    lo, hi, dev = kr.post16_reference(c, kind, d)
+    x, w, bias = _g16(d["x"], kind), Guarded(d["w"]), Guarded(d["bias"])
+    wav = Guarded(shape=(1, B, N), sentinel=SENTINEL)
+    pcm = Guarded(shape=(1, B, N), dtype=np.int16, sentinel=np.int16(-7777))
+    msg = kh.conv_post_bf16(x.ptr, w.ptr, bias.ptr, wav.ptr, pcm.ptr, B, N, C, KW, fp16=kind == kr.A16_FP16)
+    assert msg is None, msg
+    (gw, ok_w), (gp, ok_p) = wav.fetch(), pcm.fetch()
+    gw, gp = gw[0], gp[0]
+    assert ok_w and ok_p and x.unchanged() and w.unchanged() and bias.unchanged()
+    assert np.array_equal(gw, kr.act16_round(gw, kind)), "wav holds values that are no 16-bit values"
+    inside = (gw >= lo) & (gw <= hi)
+    print(f"conv_post_bf16 {c['name']} {kr.A16_NAME[kind]}: tanh deviation {dev:.3g}, {int(np.sum(~inside))} of {gw.size} outside, one-value intervals {np.mean(lo == hi):.3g}")
+    record("conv_post_act16", case=c["name"], kind=kind, dev=dev, outside=int(np.sum(~inside)), one_value=float(np.mean(lo == hi)))
+    assert np.all(inside), f"{int(np.sum(~inside))} samples outside their interval"
+    assert np.array_equal(gp, kr.pcm_of(gw)), "pcm is not (int16)(int32)(wav * 32768) of the kernel's own wav"
 
 
 # ---------------------------------------------------------------- refusals: nothing is launched

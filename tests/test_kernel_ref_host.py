@@ -39,6 +39,7 @@ def cpu_twin(c):
 def kh():
     import __graft_entry__ as g
     assert g.built_harness_hash() == g.harness_hash(), "libe2etts_kernels_test.so is missing or stale: run `python __graft_entry__.py`"
+    assert g.built_harness_act16_hash() == g.harness_act16_hash(), "libe2etts_kernels_test.so is missing or stale: run `python __graft_entry__.py`"
     import kernel_harness
     kernel_harness.load()
     return kernel_harness
@@ -66,9 +67,10 @@ def test_harness_library_exports_only_its_own_entry_points(kh):
     for want in ("e2ekt_conv_gemm", "e2ekt_conv_ksplit", "e2ekt_conv_rows", "e2ekt_conv_bf16", "e2ekt_attention", "e2ekt_rel_attention",
                  "e2ekt_layernorm", "e2ekt_resblock_pair", "e2ekt_resblock_chain", "e2ekt_pair_bf16", "e2ekt_rb_bf16_group", "e2ekt_rb_bf16_stage",
                  "e2ekt_conv_post", "e2ekt_dwconv_swish", "e2ekt_dwconv_glu_swish", "e2ekt_glu", "e2ekt_x3_to_frag", "e2ekt_f32_to_frag",
-                 "e2ekt_bf16_image", "e2ekt_f16_image"):
+                 "e2ekt_bf16_image", "e2ekt_f16_image", "e2ekt_conv_post_bf16", "e2ekt_conv_bf16_group", "e2ekt_pair_bf16_group"):
         assert want in syms, want
     assert g.harness_hash() in kh.version()          # the harness's own staleness marker
+    assert g.harness_act16_hash() in kh.load().e2ekt_act16_version().decode()      # ... and its second source's
     assert g.built_hash() == g.source_hash()         # the product library's marker keeps its meaning: the harness is not part of it
 
 
@@ -452,3 +454,223 @@ def test_wrappers_refuse_bad_arguments_before_any_launch(kh):
     assert "in-place" in kh.resblock_pair(C=32, **dict(pr, out=one)) and "mode" in kh.resblock_pair(C=32, mode=3, **pr)
     assert "bad dims" in kh.conv_post(one, one, one, one, None, 1, 8, 30, 7) and "front" in kh.conv_post(one, one, one, one, None, 1, 8, 32, 7, x_add=[None, one])
     assert "kernel odd" in kh.dwconv_swish(one, one, one, 2 * one, 1, 8, 40, 4) and "bad arguments" in kh.glu(one, one, 8, 30)
+
+
+# ---------------------------------------------------------------- 16-bit activations: the case matrix, the restatement, the two tiers
+KINDS = [kr.A16_BF16, kr.A16_FP16]
+
+
+def _a16_host_args(c, kind):
+    one = 16
+    return dict(**{"in": one}, in_bf16=int(c["in16"]), in_slope=c["in_slope"], in_add0=one if c["n_add"] > 0 else None,
+                in_add1=one if c["n_add"] > 1 else None, in_add2=one if c["n_add"] > 2 else None, in_div=c["in_div"], wimg=one,
+                KWe=2 if c["zts"] else c["KW"], tap_split=c["zts"], bias=one, act_slope=c["act_slope"], res=one if c["res"] else None,
+                accumulate=int(c["accumulate"]), out_div=c["out_div"], out_b=one, B=c["B"], T=c["T"], Cin=c["Cin"], Cout=c["Cout"], KW=c["KW"],
+                dil=c["dil"], pad=c["pad"], rows_hint=c["rows_hint"], act16=kind)
+
+
+@pytest.mark.parametrize("c", kc.A16_CASES, ids=lambda c: c["name"])
+def test_a16_case_is_supported_reaches_its_class_and_sums_exactly(kh, c):
+    for kind in KINDS:
+        a = _a16_host_args(c, kind)
+        assert kh.conv_bf16_supported(**a), (c["name"], kind)
+        assert kh.conv_bf16_class(**a) == c["reach"]["bcls"], (c["name"], kh.conv_bf16_class(**a))
+        d = kr.a16_data(c, kind)
+        ratio, unit = kr.act16_exactness(c, kind, d)
+        assert ratio < kr.A16_EXACT_LIMIT, (c["name"], kind, np.log2(ratio))       # the precondition of the exact tier
+        pre, want = kr.a16_sum64(c, kind, d)[0], kr.a16_exact(c, kind, d)
+        if c["special"] is None:   # the data exercises what the tier is for: the 16-bit rounding changes most sums
+            assert np.mean(kr.act16_round(pre.astype(np.float32), kind) != pre) > 0.5, c["name"]
+        if c["special"] == "inf" and kind == kr.A16_FP16:
+            assert 0.02 < np.mean(np.isinf(want)) < 0.5 and not np.any(np.isnan(want))
+        if c["special"] == "sub" and kind == kr.A16_FP16:
+            st = kr.act16_stage(c, kind, d["x"], d["adds"])
+            assert np.all(np.abs(st) < 2.0 ** -14) and np.mean((np.abs(want) < 2.0 ** -14) & (want != 0)) > 0.9
+
+
+def test_a16_matrix_covers_every_axis():
+    cs = kc.A16_CASES
+    assert {c["reach"]["bcls"] for c in cs} == kc.ALL_BCONV_CLASSES
+    for cls in kc.ALL_BCONV_CLASSES:          # every tile shape at both input kinds, and at its row edges
+        mine = [c for c in cs if c["reach"]["bcls"] == cls]
+        assert {c["in16"] for c in mine} == {True, False}, cls
+        bm = int(cls.split("_")[-1].split("x")[0])
+        assert {bm - 1, bm, bm + 1} <= {c["T"] for c in mine}, cls
+    assert {1, 31, 33} <= {c["T"] for c in cs}
+    halo = {c["dil"] * (c["KW"] - 1) for c in cs}
+    assert 0 in halo and kc.MAX_HALO in halo
+    pads = {("c" if c["pad"] == c["dil"] * (c["KW"] - 1) // 2 else "0" if c["pad"] == 0 else "L") for c in cs if c["KW"] > 1}
+    assert pads == {"c", "0", "L"}
+    assert {8, 40, 80, 32, 64, 256} <= {c["Cin"] for c in cs} and {32, 96, 64, 128, 256} <= {c["Cout"] for c in cs}
+    assert any(not c["in16"] and c["Cin"] == 80 and c["KW"] == 7 for c in cs)                     # conv_pre taking the mel
+    assert any(c["zts"] == 64 and c["KW"] == 3 for c in cs)
+    assert any(c["KW"] * c["Cin"] == 2816 for c in cs)
+    assert any(c["in16"] and c["in_slope"] == 1.0 and not c["n_add"] for c in cs) and any(c["in16"] and c["in_slope"] == 0.25 and not c["n_add"] for c in cs)
+    assert any(c["in16"] and c["in_slope"] == 0.1 for c in cs)                                       # the engine's staging slope
+    assert {(c["n_add"], c["in_div"]) for c in cs if c["n_add"]} >= {(1, 1.0), (2, 1.0), (3, 1.0), (1, 3.0), (2, 3.0), (3, 3.0)}
+    ep = {(c["act_slope"] != 1.0, c["res"], c["accumulate"], c["out_div"] != 1.0) for c in cs}
+    assert ep >= {(False, False, False, False), (True, False, False, False), (True, True, False, False), (True, True, True, False),
+                  (True, True, True, True), (False, True, True, True)}
+    assert {0.1, 0.0} <= {c["act_slope"] for c in cs}
+    assert {c["special"] for c in cs} == {None, "inf", "sub"}
+
+
+def _vocoder_lines(dtype, w, b):
+    """An Act16Vocoder (tests/act16_ref.py) around given 16-bit weights and biases, accumulating in float64."""
+    import torch
+    import act16_ref
+    v = object.__new__(act16_ref.Act16Vocoder)
+    v.hg, v.dtype, v.acc, v.drop = {"resblock": 1}, dtype, torch.float64, set()
+    v.w = {k: torch.from_numpy(np.ascontiguousarray(x.transpose(0, 2, 1))) for k, x in w.items()}      # [Cout, KW, Cin] -> [Cout, Cin, KW]
+    v.b = {k: torch.from_numpy(x) for k, x in b.items()}
+    return v
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=["bf16_act", "fp16_act"])
+def test_act16_chain_and_stage_are_the_lines_of_act16_ref(kind):
+    """One ResBlock1 pair of act16_ref.Act16Vocoder (torch casts: xt = r(lrelu(x)); r(c1 + b1); r(lrelu); r(c2 + b2); x = r(xt + x)) against
+    two convolutions restated with act16_stage / act16_chain, and the stage sum (xs = r(xs + rb_j); x = r(xs / n); r(lrelu)) against the
+    joined staging form.  Grid data (negatives on coarse values: the slope is 0.1) and float64 accumulation on both sides, so both sum exactly."""
+    import torch
+    dtype = torch.bfloat16 if kind == kr.A16_BF16 else torch.float16
+    c1 = kc._acase("ref_c1", "", 2, 33, 32, 32, 3, 3, act_slope=0.1, **kc._NEG01)
+    d1 = kr.a16_data(c1, kind)
+    assert kr.act16_exactness(c1, kind, d1)[0] < kr.A16_EXACT_LIMIT
+    h = kr.a16_exact(c1, kind, d1)                                     # r(lrelu(r(c1 + b1)))
+    c2 = kc._acase("ref_c2", "", 2, 33, 32, 32, 3, 1, res=True, **kc._COARSE)
+    d2 = dict(kr.a16_data(c2, kind), x=h, res=d1["x"])
+    # conv2's input is no grid any more (r(0.1 v)), but 96 products of 16-bit values sum exactly in float64 on both sides; one rounding to float32
+    second = lambda dd: kr.act16_chain(kr.a16_sum64(c2, kind, dd)[0].astype(np.float32), c2, dd["res"], None, kind)   # noqa: E731
+    mine = second(d2)
+    v = _vocoder_lines(dtype, {"resblocks.0.convs1.0": d1["w"], "resblocks.0.convs2.0": d2["w"]},
+                       {"resblocks.0.convs1.0": d1["bias"], "resblocks.0.convs2.0": d2["bias"]})
+    theirs = v._resblock(0, torch.from_numpy(np.ascontiguousarray(d1["x"].transpose(0, 2, 1))), 3, [3]).numpy().transpose(0, 2, 1)
+    assert np.array_equal(kr.bits16(mine, kind), kr.bits16(theirs, kind))
+    v.drop = {"c1"}                                                    # act16_ref's own mutation is the chain's 'drop_bias_round'
+    dropped = v._resblock(0, torch.from_numpy(np.ascontiguousarray(d1["x"].transpose(0, 2, 1))), 3, [3]).numpy().transpose(0, 2, 1)
+    pre1 = kr.a16_sum64(c1, kind, d1)[0].astype(np.float32)
+    h_drop = kr.act16_chain(pre1, c1, None, None, kind, mut="drop_bias_round")
+    assert np.array_equal(kr.bits16(second(dict(d2, x=h_drop)), kind), kr.bits16(dropped, kind))
+    assert not np.array_equal(h_drop, h)
+    # the stage sum and the next layer's activation: Gaussian 16-bit tensors
+    r = v.r
+    cj = kc._acase("ref_join", "", 2, 33, 32, 32, 1, n_add=2, in_div=3.0, in_slope=0.1)
+    dj = kr.a16_data(cj, kind, "general")
+    xs = [torch.from_numpy(t) for t in [dj["x"]] + dj["adds"]]
+    want = r(xs[0] + xs[1])
+    want = r(want + xs[2])
+    want = r(want / 3)
+    import act16_ref
+    want = r(act16_ref.lrelu(want, 0.1)).numpy()
+    assert np.array_equal(kr.bits16(kr.act16_stage(cj, kind, dj["x"], dj["adds"]), kind), kr.bits16(want, kind))
+    assert np.array_equal(kr.act16_round(dj["w"], kind), r(torch.from_numpy(dj["w"])).numpy())
+    big = np.array([65519.9, 65520.0, -1e6, 3e38, 2.0 ** -25, 2.0 ** -24 * 1.5, 2.0 ** -24 * 2.5, 1e-9], np.float32)   # overflow, subnormals, ties
+    assert np.array_equal(kr.bits16(kr.act16_round(big, kind), kind), kr.bits16(r(torch.from_numpy(big)).numpy(), kind))
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("c", kc.A16_CASES, ids=lambda c: c["name"])
+def test_a16_float32_evaluations_pass_both_tiers(c):
+    """float32 evaluations in the three orders equal the exact tier's expectation bit for bit, and pass both rules of the general tier."""
+    for kind in KINDS:
+        d = kr.a16_data(c, kind)
+        want = kr.bits16(kr.a16_exact(c, kind, d), kind)
+        z = kr.a16_data(c, kind, "zero_mean")
+        for order in ("blocked", "sequential", "matmul"):
+            assert kr.check_a16_interval(c, kind, z, kr.a16_eval32(c, kind, z, order))[0] == 0, (c["name"], kind, order)
+        cg = kr.a16_general_case(c)
+        g = kr.a16_data(cg, kind, "general")
+        ref = kr.a16_general_reference(cg, kind, g)
+        yard = kr.flip_share(kr.a16_eval32(cg, kind, g), ref["mid"], kind)
+        for order in ("blocked", "sequential", "matmul"):
+            assert np.array_equal(kr.bits16(kr.a16_eval32(c, kind, d, order), kind), want), (c["name"], kind, order)
+            rr = kr.check_a16_general(cg, kind, g, kr.a16_eval32(cg, kind, g, order), ref, yard)
+            print(f"{c['name']} {kr.A16_NAME[kind]} {order}: flip share {rr['share']:.3g} (yardstick {rr['yard']:.3g}), one-value intervals {rr['one_value']:.3g}")
+            assert rr["ok"], (c["name"], kind, order, rr["why"])
+
+
+# the smallest case in which each mutation exists, and the K = 2816 one (the channel-tail mutation at 11 x 80 = 880, as above)
+A16_MUT_SMALL = kc._acase("mut16_small", "", 2, 33, 8, 32, 3, n_add=2, in_slope=0.25, act_slope=0.1, res=True, accumulate=True, out_div=3.0)
+A16_MUT_LARGE = kc._acase("mut16_k2816", "", 1, 65, 256, 128, 11, 5, n_add=2, ag={1: (96, -6), 2: (2047, -9)}, wg=(1, -6), fine16=False, in_slope=0.25, act_slope=0.1, res=True,
+                          accumulate=True, out_div=3.0)
+A16_MUT_LARGE_TAIL = kc._acase("mut16_k880", "", 1, 65, 80, 128, 11, 5, in_slope=0.25, act_slope=0.1, res=True)
+A16_MUT_INF = kc.A16_BY_NAME["a_64x64_inf"]
+A16_MUT_SUB = kc.A16_BY_NAME["a_64x64_sub"]
+A16_MUT_LARGE_INF = dict(kc.A16_BY_NAME["a_32x128_long_k"], name="mut16_k2816_inf", xg=(48, 3), wg=(16, -1), fine16=False)
+A16_MUT_LARGE_SUB = dict(kc.A16_BY_NAME["a_32x128_long_k"], name="mut16_k2816_sub", xg=(48, -24), wg=(16, -5), fine16=False)
+# (mutation, cases, kinds, caught by the general tier as well -- on the first case, Gaussian data)
+A16_MUTATIONS = [
+    ("drop_bias_round", (A16_MUT_SMALL, A16_MUT_LARGE), KINDS),
+    ("rtz", (A16_MUT_SMALL, A16_MUT_LARGE), KINDS),
+    ("res_before_act", (A16_MUT_SMALL, A16_MUT_LARGE), KINDS),
+    ("div_before", (A16_MUT_SMALL, A16_MUT_LARGE), KINDS),
+    ("drop_join", (A16_MUT_SMALL, A16_MUT_LARGE, kc.A16_BY_NAME["a_256x32_t256_add2_div"]), KINDS),     # ... and on the in_div path
+    ("drop_tap_last_row", (A16_MUT_SMALL, A16_MUT_LARGE), KINDS),
+    ("tail_not_zeroed", (A16_MUT_SMALL, A16_MUT_LARGE_TAIL), KINDS),
+    ("sat", (A16_MUT_INF, A16_MUT_LARGE_INF), [kr.A16_FP16]),
+    ("ftz", (A16_MUT_SUB, A16_MUT_LARGE_SUB), [kr.A16_FP16]),
+]
+
+
+@pytest.mark.parametrize("mut,cases,kinds", A16_MUTATIONS, ids=[m[0] for m in A16_MUTATIONS])
+def test_every_a16_mutation_fails_the_exact_tier(mut, cases, kinds):
+    for c in cases:
+        for kind in kinds:
+            d = kr.a16_data(c, kind)
+            assert kr.act16_exactness(c, kind, d)[0] < kr.A16_EXACT_LIMIT, (c["name"], kind)
+            want = kr.bits16(kr.a16_exact(c, kind, d), kind)
+            assert np.array_equal(kr.bits16(kr.a16_eval32(c, kind, d), kind), want)
+            assert not np.array_equal(kr.bits16(kr.a16_eval32(c, kind, d, mut=mut), kind), want), (mut, c["name"], kind)
+
+
+def test_a16_wrappers_and_groups_refuse_before_any_launch(kh):
+    """The 16-bit launches and the group launchers validate on the host (made-up addresses: nothing reaches the GPU runtime)."""
+    one = 4096
+    c = kc.A16_BY_NAME["a_64x64_t63"]
+    a = {k: v for k, v in _a16_host_args(c, kr.A16_BF16).items() if k != "rows_hint"}
+    a = {k: (one if v == 16 else v) for k, v in a.items()}
+    alone = "16-bit activations write the 16-bit output alone"
+    assert alone in kh.conv_bf16(**dict(a, out=one)) and alone in kh.conv_bf16(**dict(a, outb_slope=0.5))
+    assert alone in kh.conv_bf16(**dict(a, in_bf16=0, in_add0=one))                      # a join of fp32 inputs
+    assert "act16 is 0" in kh.conv_bf16(**dict(a, act16=3))
+    assert "front" in kh.conv_bf16(**dict(a, in_add1=one)) and "out_div needs accumulate" in kh.conv_bf16(**dict(a, accumulate=0))
+    assert "needs an fp32 input" in kh.conv_bf16(**dict(a, act16=0, out=one, out_b=None, in_add0=one, res=None))
+    share = "the members of a group share"
+    assert share in kh.conv_bf16_group([a, dict(a, act16=kr.A16_FP16)]) and share in kh.conv_bf16_group([a, dict(a, T=c["T"] + 1)])
+    assert share in kh.conv_bf16_group([a, dict(a, in_bf16=0)]) and "1 .. 4 members" in kh.conv_bf16_group([a] * 5)
+    assert "unsupported shape" in kh.conv_bf16_group([a, dict(a, Cout=48)]) and alone in kh.conv_bf16_group([a, dict(a, out=one)])
+    p = dict(x=one, b1=one, b2=one, out=2 * one, B=2, T=65, C=32, KW=3, dil=1, mode=3, bimg1=one, bimg2=one)
+    assert share in kh.pair_bf16_group([p, dict(p, mode=4)]) and share in kh.pair_bf16_group([p, dict(p, C=64)])
+    assert "in-place" in kh.pair_bf16_group([p, dict(p, out=one)]) and "out_div" in kh.pair_bf16_group([p, dict(p, out_div=3.0)])
+    assert "unsupported" in kh.pair_bf16_group([p, dict(p, KW=4)]) and "1 .. 4 members" in kh.pair_bf16_group([p] * 5)
+    assert "null pointer" in kh.conv_post_bf16(None, one, one, one, None, 1, 8, 32, 7) and "bad dims" in kh.conv_post_bf16(one, one, one, one, None, 1, 8, 30, 7)
+    assert "bad dims" in kh.conv_post_bf16(one, one, one, one, None, 1, 8, 256, 7, fp16=True) and "8-byte aligned" in kh.conv_post_bf16(one + 4, one, one, one, None, 1, 8, 32, 7)
+
+
+def _general_verdict(c, kind, mut):
+    cg = kr.a16_general_case(c)
+    g = kr.a16_data(cg, kind, "general")
+    return kr.check_a16_general(cg, kind, g, kr.a16_eval32(cg, kind, g, mut=mut))
+
+
+@pytest.mark.slow
+def test_which_a16_mutations_the_general_tier_also_catches():
+    """On Gaussian data the general tier catches every mutation of the list but the two that need fp16's range (the Gaussian data stays
+    inside it): a saturated overflow and a flushed subnormal are left to the exact tier's 'inf' and 'sub' cases."""
+    for mut, cases, kinds in A16_MUTATIONS:
+        for kind in kinds:
+            r = _general_verdict(cases[0], kind, mut)
+            assert r["ok"] == (mut in ("sat", "ftz")), (mut, kind, r)
+
+
+def test_a_wrong_tie_rule_needs_the_exact_tier():
+    """What the exact tier is for.  Ties sent away from zero instead of to even, fp16, a convolution with its bias alone: the grid data's
+    sums are exact ties in a tenth of the elements, and the exact tier fails on each; a Gaussian sum is never a tie, so the general tier
+    sees the float32 yardstick's own share of flips, no element outside its interval, and passes."""
+    c, kind = kc._acase("rha_bias_only", "", 2, 65, 32, 64, 3), kr.A16_FP16
+    d = kr.a16_data(c, kind)
+    assert kr.act16_exactness(c, kind, d)[0] < kr.A16_EXACT_LIMIT
+    differ = np.mean(kr.bits16(kr.a16_eval32(c, kind, d, mut="rha"), kind) != kr.bits16(kr.a16_exact(c, kind, d), kind))
+    assert differ > 0.02, differ
+    r = _general_verdict(c, kind, "rha")
+    assert r["ok"] and r["outside"] == 0, r
