@@ -175,6 +175,40 @@ class TTS:
             pos += k + distance
         return out
 
+    @staticmethod
+    def _combine_samples(pcms: List[np.ndarray], n_samples: List[int], distance: int) -> np.ndarray:
+        """_combine_pcm with the utterances' lengths given in samples (utterances converted to another rate)."""
+        out = np.zeros(sum(int(k) + distance for k in n_samples), dtype=np.int16)
+        pos = 0
+        for pcm, k in zip(pcms, n_samples):
+            out[pos:pos + int(k)] = pcm[:int(k)]
+            pos += int(k) + distance
+        return out
+
+    def resampler(self, output_rate: int):
+        """The handle that converts the model's rate to ``output_rate`` on the engine's GPU (default filter), made at first use."""
+        from .resample import Resampler
+        cache = self.__dict__.setdefault("_resamplers", {})
+        if int(output_rate) not in cache:
+            cache[int(output_rate)] = Resampler(self.sample_rate, int(output_rate), device=self._device_index)
+        return cache[int(output_rate)]
+
+    def _synthesize_at_rate(self, rs, b, p):
+        """One batch whose PCM never visits the host at the model's rate: the engine's resident int16 rows go to a device tensor
+        (e2etts_fetch_pcm takes a device pointer), the resampler's stream is ordered after the engine's, and only the converted PCM is
+        copied out.  -> (pcm rows at the output rate, their lengths in samples)."""
+        import torch
+        from ._lib import _addr
+        eng = self.engine
+        _, mel_lens, T = eng.synthesize(b["ids"], b["lens"], b["speaker"], b["duration_control"], p, b["energy_control"], fetch_pcm=False)
+        B = int(b["ids"].shape[0])
+        dev = torch.empty((B, T * self.hop_length), dtype=torch.int16, device=f"cuda:{self._device_index}")
+        eng._check(eng.lib.e2etts_fetch_pcm(eng._h, _addr(dev), dev.numel()), "e2etts_fetch_pcm")
+        rs.load()
+        rs.order_after_stream(eng.stream())
+        out = rs.forward(dev, n_valid=np.asarray(mel_lens, np.int64) * self.hop_length, want=("pcm",))
+        return list(out["pcm"]), [int(k) for k in out["n_out"]]
+
     @classmethod
     def plan_requests(cls, sequences: Sequence[Sequence[int]], max_len: int, speaker=0, duration_control=1.0, pitch_control=1.0,
                       energy_control=1.0):
@@ -261,12 +295,19 @@ class TTS:
         self.engine.denoiser_calibrated = self.denoiser_geometry
 
     def inference_ids(self, sequences: Sequence[Sequence[int]], speaker_id, pitch_control=1.0, energy_control=1.0,
-                      duration_control=1.0, silence_distance: float = 0.5, denoise_strength: float = 0.0) -> np.ndarray:
+                      duration_control=1.0, silence_distance: float = 0.5, denoise_strength: float = 0.0,
+                      output_rate: Optional[int] = None) -> np.ndarray:
         """TTS.inference from phoneme-id sequences (the part after text_to_sequence).  ``speaker_id`` and each control may be a list with
         one entry per sequence (a control entry may also be an array of per-phoneme values): requests with different settings share
         batches (plan_requests).  ``denoise_strength > 0`` subtracts that much of the vocoder's bias spectrum from every utterance
-        (_prepare_denoiser: the reference's defaults, calibrated on the engine's own vocoder); 0, the default, is the path without a denoiser."""
+        (_prepare_denoiser: the reference's defaults, calibrated on the engine's own vocoder); 0, the default, is the path without a denoiser.
+        ``output_rate`` (None or the model's rate: today's path, bit for bit): every utterance's PCM -- denoised, when that is asked for --
+        is converted to that rate on the GPU (e2e_tts_amd.resample, n_valid = mel_lens * hop) and the silence between utterances is
+        int(silence_distance * output_rate) samples."""
         denoise_strength = float(denoise_strength)
+        rs = None
+        if output_rate is not None and int(output_rate) != int(self.sample_rate):
+            rs = self.resampler(output_rate)
         if denoise_strength < 0:
             raise ValueError("denoise_strength must be >= 0")
         if isinstance(speaker_id, (list, tuple)):
@@ -287,6 +328,11 @@ class TTS:
                     p = b["pitch_control"]
                     if uv and isinstance(p, np.ndarray):
                         p = p[..., None]   # the reference's [B, 1, 1] / [B, L, 1]: one factor for the f0 and the uv column
+                    if rs is not None:
+                        pcm, n_samples = self._synthesize_at_rate(rs, b, p)
+                        pcms.extend(pcm)
+                        lengths.extend(n_samples)
+                        continue
                     pcm, mel_lens, T = self.engine.synthesize(b["ids"], b["lens"], b["speaker"], b["duration_control"], p, b["energy_control"])
                     pcms.extend(list(pcm))
                     lengths.extend(int(x) for x in mel_lens)
@@ -295,11 +341,13 @@ class TTS:
                     self.engine.set_denoise(0.0)
         pcms = [pcms[i] for i in revert.tolist()]
         lengths = [lengths[i] for i in revert.tolist()]
+        if rs is not None:
+            return self._combine_samples(pcms, lengths, int(silence_distance * int(output_rate)))
         return self._combine_pcm(pcms, lengths, int(silence_distance * self.sample_rate))
 
     def inference(self, texts: list, speaker_id, pitch_control=1.0, energy_control=1.0, duration_control=1.0,
-                  silence_distance: float = 0.5, denoise_strength: float = 0.0) -> np.ndarray:
-        """reference API/utils.py:119-160 -> 1-D np.int16.  ``speaker_id`` and each control may also be a list with one entry (a name /
+                  silence_distance: float = 0.5, denoise_strength: float = 0.0, output_rate: Optional[int] = None) -> np.ndarray:
+        """reference API/utils.py:119-160 -> 1-D np.int16 (at ``output_rate`` when one is given: see ``inference_ids``).  ``speaker_id`` and each control may also be a list with one entry (a name /
         a number) per text: every piece arrange_text cuts from a text inherits that text's entry."""
         if isinstance(texts, str):
             texts = [texts]  # API/inference.py:39-40 passes a bare str, which the reference would iterate per character
@@ -316,8 +364,8 @@ class TTS:
         seqs = [list(self.text_to_sequence(t)) for t in pieces]
         generated_audio = self.inference_ids(seqs, follow(speaker_id, "speaker_id"), follow(pitch_control, "pitch_control"),
                                              follow(energy_control, "energy_control"), follow(duration_control, "duration_control"),
-                                             silence_distance, denoise_strength)
-        print(f"Audio Saved: {time.strftime('%H:%M:%S', time.gmtime(generated_audio.size / self.sample_rate))}")
+                                             silence_distance, denoise_strength, output_rate)
+        print(f"Audio Saved: {time.strftime('%H:%M:%S', time.gmtime(generated_audio.size / (output_rate or self.sample_rate)))}")
         return generated_audio
 
 
@@ -408,8 +456,9 @@ class Synthesizer:
         return self.synthesis(text, file_path, speed)
 
     def synthesis(self, text: str, save_filepath: str = None, speed: float = 1, speaker_id: str = "hn_minhphuong", sr: int = 22050,
-                  speed_mode: str = "duration", denoise_strength: float = 0.0):
-        """reference API/inference.py:24-50.  ``denoise_strength``: see ``TTS.inference_ids`` (0 = off).  ``speed != 1``: the reference synthesises at normal tempo and then runs ffmpeg's
+                  speed_mode: str = "duration", denoise_strength: float = 0.0, resample: bool = False):
+        """reference API/inference.py:24-50.  ``sr`` only labels the file, as in the reference (the samples stay at the model's rate);
+        with ``resample=True`` the audio is converted to ``sr`` on the GPU before it is written (``TTS.inference(output_rate=sr)``).  ``denoise_strength``: see ``TTS.inference_ids`` (0 = off).  ``speed != 1``: the reference synthesises at normal tempo and then runs ffmpeg's
         ``atempo`` on the file (API/utils.py:163-172).  Here, by default (``speed_mode="duration"``), the tempo goes into the
         model instead -- ``duration_control = 1 / speed`` (U/layers.py:218-221), i.e. the phonemes are simply generated shorter
         or longer on the GPU path, with no vocoded-audio artefacts; ``speed_mode="wsola"`` post-processes the file like the
@@ -426,7 +475,8 @@ class Synthesizer:
         audio = self.model.inference(texts=[text], speaker_id=speaker_id, pitch_control=1.0, energy_control=1.0,
                                      duration_control=(1.0 / float(speed)) if in_model else 1.0, silence_distance=0.5,
                                      # (handed on only when set: self.model may be any object with the reference's TTS.inference signature)
-                                     **({"denoise_strength": denoise_strength} if denoise_strength else {}))
+                                     **({"denoise_strength": denoise_strength} if denoise_strength else {}),
+                                     **({"output_rate": int(sr)} if resample else {}))
         write_wav(save_filepath, audio, sr)
         if in_model:
             file_type = save_filepath.split(".")[-1]

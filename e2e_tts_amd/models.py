@@ -236,7 +236,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
                                           au["signal"]["sampling_rate"], au["mel"]["mel_fmin"], au["mel"]["mel_fmax"], device=self._device)
         return stft
 
-    def align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior=None, return_energy=False, stft=None):
+    def align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior=None, return_energy=False, stft=None, wav_rate=None):
         """Forced alignment of RECORDINGS: wavs [B, n] (float32 in [-1, 1] or int16 PCM; numpy or torch, host or GPU), wav_lens [B] samples
         -> ``align``'s tuple (attn_soft, attn_hard, attn_hard_dur, attn_logprob), plus the frame energies [B, T] when ``return_energy``.
         The mel is computed on the device by the mel library, every row over its own length (mel_lens = wav_lens // hop, as
@@ -244,7 +244,10 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         to use (e.g. one holding librosa's own filterbank); by default one is built from this model's audio configuration with
         ``mel.mel_filterbank`` (see its docstring: unpinned against librosa) -- the shipped 22.05 kHz defaults, or what
         ``set_audio_config`` was given; a model built with another sampling rate or hop and no audio configuration raises instead of
-        guessing a transform."""
+        guessing a transform.  ``wav_rate``: the sampling rate of ``wavs`` when it is not the transform's (studio recordings are usually 44.1
+        or 48 kHz): the recordings are converted to the transform's rate on the device (e2e_tts_amd.resample, default filter), the mel
+        library reads the result where it lies, and mel_lens follow from the converted lengths ceil(wav_lens * L / M).  None: the
+        recordings are taken to be at the transform's rate, as before."""
         from . import aligner as al
         torch = _torch()
         if stft is None:
@@ -264,6 +267,16 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         fe = stft.frontend
         x = stft._audio(wavs)
         wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
+        if wav_rate is not None and int(wav_rate) != int(stft.sampling_rate):
+            from .resample import Resampler
+            cache = self.__dict__.setdefault("_resamplers", {})
+            key = (int(wav_rate), int(stft.sampling_rate), self._device)
+            if key not in cache:
+                cache[key] = Resampler(key[0], key[1], device=self._device)
+            rsm = cache[key]
+            wl = rsm.forward(x, n_valid=wl, want=())["n_out"]   # raises ValueError on a bad length before anything is enqueued
+            x = rsm.resident()[0]                                # [B, width] float32 in the resampler's HBM, until its next forward
+            fe._call("order_after", rsm.hip_stream())           # the mel's stream after the resampler's
         energy = None
         if return_energy:
             energy = torch.zeros((B, max(1, int(wl.max()) // fe.hop)), dtype=torch.float32, device=dev)
@@ -553,12 +566,14 @@ class Denoiser:
 
     __call__ = forward
 
-    def stream(self, mel_chunks, strength: float = 0.1, want_pcm: bool = False):
+    def stream(self, mel_chunks, strength: float = 0.1, want_pcm: bool = False, output_rate: Optional[int] = None, source_rate: int = 22050):
         """Generator over channels-last mel chunks [B, n, n_mel] (numpy / torch) on the vocoder's engine: yields numpy pieces
         [B, n_emit * hop] (float32, or int16 with ``want_pcm``) that concatenate to ``forward(vocoder(whole mel), strength)`` bit for bit
         while HBM use stays bounded by the chunk (e2etts_vocoder_stream_begin_denoised).  An EXTENSION: the reference has no stream --
         its Denoiser takes the whole waveform.  B is read from the first chunk; the bases and the bias cannot be replaced (another
-        Denoiser on the same vocoder) until the generator is exhausted."""
+        Denoiser on the same vocoder) until the generator is exhausted.  ``output_rate`` (None: the pieces as they are): the denoised fp32
+        pieces, at ``source_rate``, go through ``resample.Resampler.stream`` on the same GPU and the pieces yielded are at ``output_rate``
+        ([B, n_ready] each; they concatenate to the one-shot conversion of the whole denoised waveform bit for bit)."""
         eng = self._vocoder.engine
         it = iter(mel_chunks)
         first = next(it, None)
@@ -571,7 +586,12 @@ class Denoiser:
             yield first
             yield from it
 
-        yield from eng.vocoder_stream(chunks(), int(first.shape[0]), want_pcm=want_pcm, denoise_strength=float(strength))
+        if output_rate is None or int(output_rate) == int(source_rate):
+            yield from eng.vocoder_stream(chunks(), int(first.shape[0]), want_pcm=want_pcm, denoise_strength=float(strength))
+            return
+        from .resample import Resampler
+        pieces = eng.vocoder_stream(chunks(), int(first.shape[0]), want_pcm=False, denoise_strength=float(strength))
+        yield from Resampler(source_rate, output_rate, device=eng.device).stream(pieces, want_pcm=want_pcm)
 
 
 class TorchSTFT:
