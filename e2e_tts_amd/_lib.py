@@ -398,6 +398,76 @@ class Engine:
         return out
 
     @_locked
+    def acoustic_forced(self, ids, lens, speaker, durations=None, attn_soft=None, mel_lens=None, f0=None, uv=None, pitch=None, energy=None,
+                        pitch_frames=False, energy_frames=False, T=None, d_control=1.0, p_control=1.0, e_control=1.0,
+                        want=("dur", "mel_lens")):
+        """The teacher-forced pass (e2etts_acoustic_forced of the companion library libe2etts_forced.so, include/e2etts_forced.h, on this
+        engine; reference UnsupervisedFastSpeech2.forward in eval()): ``durations`` [B, L]
+        float32 (the aligner's MAS), ``attn_soft`` [B, T, L] float32 with ``mel_lens`` [B] int64 for the soft expansion, pitch targets
+        (``f0`` and ``uv``, or ``pitch`` for a pitch_no_uv model) and ``energy`` -- each None or a numpy array / torch tensor, host or
+        device; ``pitch_frames`` / ``energy_frames``: the target is frame-resolved [B, T] (averaged per phoneme for a phoneme_level
+        feature).  ``T``: columns of the [B, T] arrays (taken from ``attn_soft`` when that is given).  With nothing given the call is
+        `acoustic` with array controls.  Returns what `acoustic` returns; mel, taps ("pitch_target", "energy_target", "dec_in") and
+        `vocoder(None, ...)` read the resident results."""
+        B, L = int(ids.shape[0]), int(ids.shape[1])
+        n_spk = int(speaker.shape[0])
+        _expect(ids, "ids", "int64", B * L)
+        _expect(lens, "lens", "int64", B)
+        _expect(speaker, "speaker", "int64", n_spk)
+        if n_spk not in (1, B):
+            raise ValueError(f"speaker holds {n_spk} ids, expected 1 or {B}")
+        if attn_soft is not None:
+            if len(attn_soft.shape) != 3 or int(attn_soft.shape[0]) != B or int(attn_soft.shape[2]) != L:
+                raise ValueError(f"attn_soft: shape {tuple(attn_soft.shape)}, expected [B={B}, T, L={L}]")
+            if T is not None and int(T) != int(attn_soft.shape[1]):
+                raise ValueError(f"T = {T}, attn_soft has {int(attn_soft.shape[1])} rows per utterance")
+            T = int(attn_soft.shape[1])
+        T = 0 if T is None else int(T)
+        pf, ef = bool(self.dims.pitch_frame), bool(self.dims.energy_frame)
+        _expect(durations, "durations", "float32", B * L)
+        _expect(attn_soft, "attn_soft", "float32", B * T * L)
+        _expect(mel_lens, "mel_lens", "int64", B)
+        for x, name, bt in ((f0, "f0", pitch_frames or pf), (uv, "uv", pitch_frames or pf), (pitch, "pitch", pitch_frames or pf),
+                            (energy, "energy", energy_frames or ef)):
+            if x is not None and bt and T <= 0:
+                raise ValueError(f"{name}: a [B, T] target needs T")
+            _expect(x, name, "float32", B * (T if bt else L))
+        ctl = self._controls(d_control, p_control, e_control, B, L)
+        if ctl is None:
+            ctl = [(np.array([float(v)], np.float32), 1) for v in (d_control, p_control, e_control)]
+        self._order(ids, lens, speaker, durations, attn_soft, mel_lens, f0, uv, pitch, energy, *(c[0] for c in ctl))
+        from . import forced as fzlib   # (the companion's binding imports this module)
+        flib = fzlib.load_library()
+        fz = fzlib.CForced(C.sizeof(fzlib.CForced), T, _addr(durations), _addr(attn_soft), _addr(mel_lens), _addr(f0), _addr(uv), _addr(pitch), _addr(energy),
+                     int(bool(pitch_frames)), int(bool(energy_frames)))
+        bufs = dict(
+            dur=np.empty((B, L), np.float32) if "dur" in want else None,
+            mel_lens=np.empty((B,), np.int64) if "mel_lens" in want else None,
+            pitch_idx=np.empty((B, L), np.int32) if "pitch_idx" in want and not pf else None,
+            energy_idx=np.empty((B, L), np.int32) if "energy_idx" in want and not ef else None,
+            log_d=np.empty((B, L), np.float32) if "log_d" in want else None,
+            pitch_pred=np.empty((B, L) if self.dims.pitch_no_uv else (B, L, 2), np.float32) if "pitch_pred" in want and not pf else None,
+            energy_pred=np.empty((B, L), np.float32) if "energy_pred" in want and not ef else None,
+        )
+        Tn = C.c_int(0)
+        rc = flib.e2etts_acoustic_forced(self._h, _addr(ids), _addr(lens), B, L, _addr(speaker), n_spk,
+                                         *(a for v, n in ctl for a in (_addr(v), n)), C.byref(fz),
+                                         _addr(bufs["dur"]), _addr(bufs["mel_lens"]), C.byref(Tn), _addr(bufs["pitch_idx"]),
+                                         _addr(bufs["energy_idx"]), _addr(bufs["log_d"]), _addr(bufs["pitch_pred"]), _addr(bufs["energy_pred"]))
+        self._check(rc, "e2etts_acoustic_forced")
+        out = {k: v for k, v in bufs.items() if v is not None}
+        out["T"], out["B"] = Tn.value, B
+        for name, frame, shape, dt in (("pitch_idx", pf, (B, Tn.value), np.int32), ("energy_idx", ef, (B, Tn.value), np.int32),
+                                       ("pitch_pred", pf, (B, Tn.value) if self.dims.pitch_no_uv else (B, Tn.value, 2), np.float32),
+                                       ("energy_pred", ef, (B, Tn.value), np.float32)):
+            if frame and name in want:
+                a = np.empty(shape, dt)
+                fn = self.lib.e2etts_fetch_tap_i32 if dt is np.int32 else self.lib.e2etts_fetch_tap
+                self._check(fn(self._h, name.encode(), _addr(a), a.size), "e2etts_fetch_tap")
+                out[name] = a
+        return out
+
+    @_locked
     def fetch_mel(self, B: int, T: int, mel=True, mel_post=True, out_mel=None, out_mel_post=None):
         m = out_mel if out_mel is not None else (np.empty((B, T, self.dims.n_mel), np.float32) if mel else None)
         mp = out_mel_post if out_mel_post is not None else (np.empty((B, T, self.dims.n_mel), np.float32) if mel_post else None)

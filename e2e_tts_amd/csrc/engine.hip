@@ -19,6 +19,7 @@
 
 #include "../../include/e2etts.h"
 #include "host_logic.h"
+#include "forced_entry.h"
 #ifndef E2ETTS_ST_DEPTH
 #define E2ETTS_ST_DEPTH 2   // chunks the streaming vocoder keeps in flight (tuning builds: 3)
 #endif
@@ -141,6 +142,11 @@ struct e2etts_engine {
   DevBuf ffpool;  // Fastformer: pooled query | pooled key [2][B, H]
   DevBuf logd, durf, cum, mel64, mel32, posbuf, ppred, epred, pidx, eidx;
   DevBuf ctlbuf;  // [3][B * L] fp32: the d / p / e controls of the _ctl entry points (grows with B * L only)
+  // e2etts_acoustic_forced: a host map's copy [B, T, L], the given mel lengths, the frame-resolved targets [3][B, T] awaiting their
+  // per-phoneme means, the targets at the model's level [3][B, N] (f0 or pitch | uv | energy), the decoder's input (tap "dec_in")
+  DevBuf fattn, fmel64, ftgf, ftg, decin;
+  bool forced_last = false, forced_pitch = false, forced_energy = false;   // what the taps of the last acoustic pass can hand out
+  int forced_T = 0;   // columns of its [B, T] targets
   DevBuf dx, dxb, mel, melpost, pn1, pn2;
   DevBuf melin;
   // Everything one vocoder pass works in besides the weights; vocoder_impl / vocoder_act16 are handed one and touch no other pass.  The
@@ -1172,8 +1178,85 @@ int check_controls(e2etts_engine* e, const CtlArgs& ctl, int B, int L) {
   return E2ETTS_OK;
 }
 
+// What e2etts_acoustic_forced asked for, resolved against the model (forced_plan; the struct itself passed host_logic.h: forced_check).
+struct ForcedPlan {
+  const e2etts_forced* f = nullptr;
+  bool soft = false;                 // attn_soft: the soft expansion, T and mel_lens as given
+  bool has_p = false, has_e = false; // a pitch / an energy target
+  bool p_avg = false, e_avg = false; // ... frame-resolved, for a phoneme_level feature: averaged over the durations
+  int T = 0;
+  const int64_t* mel_lens_host = nullptr;
+};
+
+// The variance adaptor's teacher-forced steps (U/layers.py:202-241 with attn_prior): the durations as given, their scan in
+// launch_duration's output format, the targets brought to the model's level.  Called where the predicted pass calls launch_duration.
+int forced_durations_and_targets(e2etts_engine* e, const ForcedPlan& fp, int B, int L, float d_control, const CtlRef& d_ctl) {
+  const auto& c = e->cfg;
+  const e2etts_forced& f = *fp.f;
+  const size_t BL = (size_t)B * L, BT = (size_t)B * std::max(fp.T, 1);
+  if (f.durations) RET(copy_in(e, e->durf.p, f.durations, BL * 4));
+  else KCHK(e, launch_duration(ptr<float>(e->logd), d_control, ptr<float>(e->durf), ptr<int32_t>(e->cum), ptr<int64_t>(e->mel64),
+                               ptr<int32_t>(e->mel32), B, L, e->stream, d_ctl));
+  TeacherScanParams sp;
+  sp.dur = ptr<float>(e->durf); sp.txt_lens = ptr<int32_t>(e->lens32); sp.cum = ptr<int32_t>(e->cum);
+  sp.mel64 = ptr<int64_t>(e->mel64); sp.mel32 = ptr<int32_t>(e->mel32);
+  sp.B = B; sp.L = L; sp.T = fp.T;
+  if (fp.soft) {
+    RET(ensure(e, e->fmel64, (size_t)B * 8));
+    RET(copy_in(e, e->fmel64.p, f.mel_lens, (size_t)B * 8));
+    sp.mel_given = ptr<int64_t>(e->fmel64);
+  }
+  // targets: slot 0 = f0 or pitch, 1 = uv, 2 = energy; each [B, N] at the model's level, N = L (phoneme_level) or T columns (frame_level)
+  if (fp.has_p || fp.has_e) {
+    const size_t n_lvl = std::max(BL, BT);
+    RET(ensure(e, e->ftg, 3 * n_lvl * 4));
+    if (fp.p_avg || fp.e_avg) RET(ensure(e, e->ftgf, 3 * BT * 4));
+    const float* src[3] = {c.pitch_no_uv ? f.pitch : f.f0, c.pitch_no_uv ? nullptr : f.uv, f.energy};
+    for (int k = 0; k < 3; ++k) {
+      if (!src[k]) continue;
+      const bool avg = k < 2 ? fp.p_avg : fp.e_avg;
+      const bool frame = k < 2 ? c.pitch_frame != 0 : c.energy_frame != 0;
+      float* lvl = ptr<float>(e->ftg) + k * n_lvl;
+      if (avg) {
+        float* fr = ptr<float>(e->ftgf) + k * BT;
+        RET(copy_in(e, fr, src[k], BT * 4));
+        sp.tg[sp.n_tg].src = fr; sp.tg[sp.n_tg].dst = lvl; sp.tg[sp.n_tg].uv = k == 1;
+        ++sp.n_tg;
+      } else {
+        RET(copy_in(e, lvl, src[k], (frame ? BT : BL) * 4));
+      }
+    }
+  }
+  KCHK(e, launch_teacher_scan(sp, e->stream));
+  return E2ETTS_OK;
+}
+
+// launch_variance_embed of one level ([B, N] rows of x) with the features of `feat` that have a target embedded from it
+int forced_embed(e2etts_engine* e, const ForcedPlan& fp, float* x, int B, int L, int N, int tld, int feat, float p_control, float e_control,
+                 int pitch_mode, const VarCtl& vc) {
+  const auto& c = e->cfg;
+  const size_t n_lvl = std::max((size_t)B * L, (size_t)B * std::max(fp.T, 1));
+  TargetEmbedParams q;
+  if ((feat & 1) && fp.has_p) { q.pitch_t = ptr<float>(e->ftg); if (!c.pitch_no_uv) q.uv_t = ptr<float>(e->ftg) + n_lvl; }
+  if ((feat & 2) && fp.has_e) q.energy_t = ptr<float>(e->ftg) + 2 * n_lvl;
+  if (!q.pitch_t && !q.energy_t) {   // nothing of this level has a target: the predicted pass's own launch
+    KCHK(e, launch_variance_embed(x, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std, e->energy_bins, c.n_bins,
+                                  e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx), ptr<int32_t>(e->eidx), B, N, c.hidden, e->stream, pitch_mode,
+                                  e->pitch_bins, feat, vc));
+    return E2ETTS_OK;
+  }
+  q.tld = tld; q.N = N; q.H = c.hidden;
+  q.p_control = p_control; q.e_control = e_control; q.f0_mean = c.f0_mean; q.f0_std = c.f0_std;
+  q.energy_bins = e->energy_bins; q.pitch_bins = e->pitch_bins; q.n_bins = c.n_bins; q.pitch_mode = pitch_mode; q.feat = feat;
+  q.pitch_emb = e->pitch_emb; q.energy_emb = e->energy_emb; q.pitch_idx = ptr<int32_t>(e->pidx); q.energy_idx = ptr<int32_t>(e->eidx);
+  q.ctl = vc;
+  KCHK(e, launch_target_embed(x, ptr<float>(e->ppred), ptr<float>(e->epred), q, B, e->stream));
+  return E2ETTS_OK;
+}
+
 int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
-                  int n_spk_ids, float d_control, float p_control, float e_control, bool ragged = false, const CtlArgs* ctl = nullptr) {
+                  int n_spk_ids, float d_control, float p_control, float e_control, bool ragged = false, const CtlArgs* ctl = nullptr,
+                  const ForcedPlan* fp = nullptr) {
   const auto& c = e->cfg;
   if (!e->ac_loaded) return e->fail(E2ETTS_ESTATE, "acoustic weights not loaded");
   if (!ids || !lens || !speaker) return e->fail(E2ETTS_EINVAL, "ids / lens / speaker must not be NULL");
@@ -1224,6 +1307,7 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   RET(ensure(e, e->eidx, BL * 4));
 
   e->have_acoustic = false;
+  e->forced_last = e->forced_pitch = e->forced_energy = false;
   RET(copy_in(e, e->ids.p, ids, BL * 8));
   RET(copy_in(e, e->lens64.p, lens, (size_t)B * 8));
   RET(copy_in(e, e->spk.p, speaker, (size_t)n_spk_ids * 8));
@@ -1294,14 +1378,21 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
     KCHK(e, launch_add_speaker(x, xs, e->spk_emb, ptr<int64_t>(e->spk), n_spk_ids, c.n_speakers, B, L, H, e->stream));
   }
   RET(predictor(e, e->dur, xs, ptr<float>(e->logd), tl, B, L, act_enc, act_enc_h, frac_enc));
-  {
+  if (fp) {   // teacher-forced: given durations, targets (the predictors still run: their outputs are returned)
+    ProfScope ps(e, "misc", 0, 0);
+    RET(forced_durations_and_targets(e, *fp, B, L, d_control, cref[0]));
+  } else {
     ProfScope ps(e, "misc", 0, 0);
     KCHK(e, launch_duration(ptr<float>(e->logd), d_control, ptr<float>(e->durf), ptr<int32_t>(e->cum),
                             ptr<int64_t>(e->mel64), ptr<int32_t>(e->mel32), B, L, e->stream, cref[0]));
   }
-  HIPCHK(e, hipMemcpyAsync(e->h_mel, e->mel64.p, (size_t)B * 8, hipMemcpyDeviceToHost, e->stream));
-  hipEvent_t mel_ready = get_event(e);
-  HIPCHK(e, hipEventRecord(mel_ready, e->stream));
+  const bool soft = fp && fp->soft;   // T and the mel lengths are the caller's: nothing to wait for
+  hipEvent_t mel_ready = nullptr;
+  if (!soft) {
+    HIPCHK(e, hipMemcpyAsync(e->h_mel, e->mel64.p, (size_t)B * 8, hipMemcpyDeviceToHost, e->stream));
+    mel_ready = get_event(e);
+    HIPCHK(e, hipEventRecord(mel_ready, e->stream));
+  }
   // pitch / energy predictors run while the mel lengths travel to the host
   float* xp = ptr<float>(e->xp);
   const bool p_frame = c.pitch_frame != 0, e_frame = c.energy_frame != 0;   // frame_level features wait for the length regulator (below)
@@ -1327,19 +1418,34 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
     vc.p = p_frame ? CtlRef() : cref[1];
     vc.e = e_frame ? CtlRef() : cref[2];
     vc.N = L;
-    KCHK(e, launch_variance_embed(xs, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
-                                  e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
-                                  ptr<int32_t>(e->eidx), B, L, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 0 : 1) | (e_frame ? 0 : 2), vc));
+    if (fp) {
+      RET(forced_embed(e, *fp, xs, B, L, L, L, (p_frame ? 0 : 1) | (e_frame ? 0 : 2), p_control, e_control, pitch_mode, vc));
+    } else {
+      KCHK(e, launch_variance_embed(xs, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
+                                    e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
+                                    ptr<int32_t>(e->eidx), B, L, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 0 : 1) | (e_frame ? 0 : 2), vc));
+    }
   }
-  // the one host synchronisation of the acoustic model: T = max(mel_lens) sizes everything downstream
-  HIPCHK(e, hipEventSynchronize(mel_ready));
-  e->ev_pool.push_back(mel_ready);
   long long T = 0;
-  for (int b = 0; b < B; ++b) T = std::max<long long>(T, e->h_mel[b]);
-  if (T <= 0) return e->fail(E2ETTS_EINVAL, "every predicted duration is zero: nothing to synthesise");
+  if (soft) {
+    // the mel lengths as the scan kernel clamps them; given in device memory, every utterance counts as T frames long on the host (the
+    // launch grids stay padded; the kernels mask by the device copy)
+    T = fp->T;
+    for (int b = 0; b < B; ++b) e->h_mel[b] = fp->mel_lens_host ? std::min<long long>(std::max<long long>(fp->mel_lens_host[b], 0), T) : T;
+  } else {
+    // the one host synchronisation of the acoustic model: T = max(mel_lens) sizes everything downstream
+    HIPCHK(e, hipEventSynchronize(mel_ready));
+    e->ev_pool.push_back(mel_ready);
+    for (int b = 0; b < B; ++b) T = std::max<long long>(T, e->h_mel[b]);
+  }
+  if (T <= 0)
+    return e->fail(E2ETTS_EINVAL, fp && fp->f->durations ? "every given duration is zero (or was clamped to zero): nothing to synthesise"
+                                                         : "every predicted duration is zero: nothing to synthesise");
   if (T > c.max_seq_len && T > c.pos_table_rows)
     return e->fail(E2ETTS_EINVAL, "T=%lld exceeds the shipped position table (%d rows)", T, c.pos_table_rows);
   if (T > (1 << 20)) return e->fail(E2ETTS_EINVAL, "T=%lld is unreasonably large", T);
+  if (fp && !soft && ((fp->has_p && c.pitch_frame) || (fp->has_e && c.energy_frame)) && T > fp->T)
+    return e->fail(E2ETTS_EINVAL, "the durations give T=%lld frames, the frame_level targets have %d columns", T, fp->T);
   const size_t BT = (size_t)B * T;
   RET(ensure(e, e->dx, BT * H * 4));
   RET(ensure(e, e->dxb, BT * H * 4));
@@ -1356,7 +1462,28 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   const float* dpos = T > c.max_seq_len ? e->pos_regen : e->dec_pos;
   float* dx = ptr<float>(e->dx);
   const int32_t* ml = ptr<int32_t>(e->mel32);
-  {
+  if (soft) {
+    // soft expansion (U/layers.py:244-245) fused with the position add, exact fp32; ragged: rows < mel_len only (a frame_level feature's
+    // predictors read every row: padded then)
+    SoftExpandParams sx;
+    sx.attn = fp->f->attn_soft;
+    if (!is_device_pointer(sx.attn)) {
+      RET(ensure(e, e->fattn, BT * L * 4));
+      RET(copy_in(e, e->fattn.p, sx.attn, BT * L * 4));
+      sx.attn = ptr<float>(e->fattn);
+    }
+    sx.x = xs; sx.txt_lens = tl; sx.pos = (p_frame || e_frame) ? nullptr : dpos; sx.out = dx;
+    sx.B = B; sx.T = (int)T; sx.L = L; sx.H = H;
+    bool any_short = false;
+    for (int b = 0; b < B; ++b) any_short = any_short || e->h_mel[b] < T;
+    if (ragged && any_short && !p_frame && !e_frame) {
+      e->h_act.resize((size_t)(5 + c.voc_stages) * B, 0);
+      for (int b = 0; b < B; ++b) e->h_act[b] = (int32_t)e->h_mel[b];
+      sx.act_rows = ml; sx.act_rows_host = e->h_act.data();
+    }
+    ProfScope ps(e, "soft_expand", soft_expand_flops(sx), 4.0 * ((double)BT * L + (double)BL * H + (double)BT * H));
+    KCHK(e, launch_soft_expand(sx, e->stream));
+  } else {
     ProfScope ps(e, "misc", 0, 0);
     KCHK(e, launch_length_regulate(xs, ptr<int32_t>(e->cum), ml, (p_frame || e_frame) ? nullptr : dpos, dx, B, L, (int)T, H, e->stream));
   }
@@ -1394,10 +1521,18 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
     vc.N = (int)T;
     vc.cum = ptr<int32_t>(e->cum);
     vc.Lp = L;
-    KCHK(e, launch_variance_embed(dx, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
-                                  e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
-                                  ptr<int32_t>(e->eidx), B, (int)T, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 1 : 0) | (e_frame ? 2 : 0), vc));
+    if (fp) {
+      RET(forced_embed(e, *fp, dx, B, L, (int)T, fp->T, (p_frame ? 1 : 0) | (e_frame ? 2 : 0), p_control, e_control, pitch_mode, vc));
+    } else {
+      KCHK(e, launch_variance_embed(dx, ptr<float>(e->ppred), ptr<float>(e->epred), p_control, e_control, c.f0_mean, c.f0_std,
+                                    e->energy_bins, c.n_bins, e->pitch_emb, e->energy_emb, ptr<int32_t>(e->pidx),
+                                    ptr<int32_t>(e->eidx), B, (int)T, H, e->stream, pitch_mode, e->pitch_bins, (p_frame ? 1 : 0) | (e_frame ? 2 : 0), vc));
+    }
     KCHK(e, launch_add_positions(dx, dpos, B, (int)T, H, e->stream));
+  }
+  if (fp) {   // tap "dec_in": the decoder works in place on dx
+    RET(ensure(e, e->decin, BT * H * 4));
+    HIPCHK(e, hipMemcpyAsync(e->decin.p, dx, BT * H * 4, hipMemcpyDeviceToDevice, e->stream));
   }
   // Ragged mode (synthesize only).  Decoder: every consumer of a row >= mel_len masks it (keys are masked, the LayerNorm
   // kernels write zeros there), so its convolutions compute rows < mel_len only and valid rows stay bit-identical.
@@ -1464,6 +1599,7 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
   }
   e->last_B = B; e->last_L = L; e->last_T = (int)T;
   e->have_acoustic = true;
+  if (fp) { e->forced_last = true; e->forced_pitch = fp->has_p; e->forced_energy = fp->has_e; e->forced_T = fp->T; }
   return E2ETTS_OK;
 }
 
@@ -2663,13 +2799,41 @@ int e2etts_order_after(e2etts_engine* e, void* caller_stream) {
 static int acoustic_entry(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker,
                           int n_spk_ids, float d_control, float p_control, float e_control, const CtlArgs* ctl, float* dur_out,
                           int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out, int32_t* energy_idx_out, float* log_dur_out,
-                          float* pitch_pred_out, float* energy_pred_out) {
+                          float* pitch_pred_out, float* energy_pred_out, const e2etts_forced* forced = nullptr) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
   HIPCHK(e, hipSetDevice(e->device));
   if (B > 4096) return e->fail(E2ETTS_EINVAL, "B > 4096");
   if (ctl) RET(check_controls(e, *ctl, B, L));
-  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, false, ctl));
+  ForcedPlan fp;
+  if (forced) {
+    // the struct is validated before anything is enqueued (host_logic.h: forced_check); its size field first, nothing else before it
+    uint32_t fsize = 0;
+    memcpy(&fsize, forced, sizeof fsize);
+    e2etts_forced f;
+    memset(&f, 0, sizeof f);
+    if (fsize == sizeof f) f = *forced;
+    ForcedShape sh;
+    sh.B = B; sh.L = L; sh.pitch_no_uv = e->cfg.pitch_no_uv; sh.pitch_frame = e->cfg.pitch_frame; sh.energy_frame = e->cfg.energy_frame;
+    sh.max_seq_len = e->cfg.max_seq_len; sh.pos_table_rows = e->cfg.pos_table_rows; sh.var_pos_rows = e->var_pos_rows;
+    const float* dur_h = f.durations && !is_device_pointer(f.durations) ? f.durations : nullptr;
+    const int64_t* ml_h = f.mel_lens && !is_device_pointer(f.mel_lens) ? f.mel_lens : nullptr;
+    const int64_t* len_h = lens && !is_device_pointer(lens) ? lens : nullptr;
+    const std::string bad = forced_check(fsize, f, sh, dur_h, ml_h, len_h);
+    if (!bad.empty()) return e->fail(E2ETTS_EINVAL, "%s", bad.c_str());
+    if (!forced_is_null(f)) {   // (every member NULL: the predicted pass, e2etts_acoustic_ctl bit for bit)
+      fp.f = forced;
+      fp.soft = f.attn_soft != nullptr;
+      fp.has_p = f.f0 || f.pitch;
+      fp.has_e = f.energy != nullptr;
+      fp.p_avg = fp.has_p && f.pitch_frames && !e->cfg.pitch_frame;
+      fp.e_avg = fp.has_e && f.energy_frames && !e->cfg.energy_frame;
+      fp.T = f.T;
+      fp.mel_lens_host = ml_h;
+    }
+  }
+  // the forced pass serves generate_mel, which keeps valid frames only: it follows e2etts_set_ragged like e2etts_synthesize
+  RET(acoustic_impl(e, ids, lens, B, L, speaker, n_spk_ids, d_control, p_control, e_control, fp.f ? e->ragged != 0 : false, ctl, fp.f ? &fp : nullptr));
   const size_t BL = (size_t)B * L;
   if (dur_out) RET(copy_out(e, dur_out, e->durf.p, BL * 4));
   if (mel_lens_out) RET(copy_out(e, mel_lens_out, e->mel64.p, (size_t)B * 8));
@@ -2704,6 +2868,25 @@ int e2etts_acoustic_ctl(e2etts_engine* e, const int64_t* ids, const int64_t* len
                         energy_idx_out, log_dur_out, pitch_pred_out, energy_pred_out);
 }
 
+}  // extern "C"
+// The teacher-forced pass (include/e2etts_forced.h).  NOT an entry point of this library -- its ABI is frozen --: a C++ symbol that stays
+// inside whatever library the engine object is linked into; csrc/forced/forced.hip exports it from libe2etts_forced.so, which links this
+// object and therefore works on the same e2etts_engine layout as the library that created the handle (forced_entry.h).
+namespace e2etts {
+const char* engine_version() { return e2etts_version(); }
+int acoustic_forced_entry(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int B, int L, const int64_t* speaker, int n_spk_ids,
+                          const float* d_control, int n_d, const float* p_control, int n_p, const float* e_control, int n_e,
+                          const e2etts_forced* forced, float* dur_out, int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out,
+                          int32_t* energy_idx_out, float* log_dur_out, float* pitch_pred_out, float* energy_pred_out) {
+  CtlArgs ctl;
+  ctl.v[0] = d_control; ctl.v[1] = p_control; ctl.v[2] = e_control;
+  ctl.n[0] = n_d; ctl.n[1] = n_p; ctl.n[2] = n_e;
+  return acoustic_entry(e, ids, lens, B, L, speaker, n_spk_ids, 1.0f, 1.0f, 1.0f, &ctl, dur_out, mel_lens_out, T_out, pitch_idx_out,
+                        energy_idx_out, log_dur_out, pitch_pred_out, energy_pred_out, forced);
+}
+}  // namespace e2etts
+extern "C" {
+
 int e2etts_fetch_mel(e2etts_engine* e, float* mel, float* mel_post) {
   if (!e) return E2ETTS_EINVAL;
   std::lock_guard<std::mutex> lk(e->mu);
@@ -2736,6 +2919,29 @@ int e2etts_fetch_tap(e2etts_engine* e, const char* which, float* out, size_t n_f
   else if (!strcmp(which, "energy_pred")) { src = e->epred.p; n = ne; }
   else if (!strcmp(which, "enc_out")) { src = e->xa.p;  /* the encoder's output stays in its own buffer: nothing later in the pass writes it */ n = (size_t)e->last_B * e->last_L * e->cfg.hidden; }
   else if (!strcmp(which, "dec_out")) { src = e->dx.p; n = (size_t)e->last_B * e->last_T * e->cfg.hidden; }
+  else if (!strcmp(which, "dec_in") || !strcmp(which, "pitch_target") || !strcmp(which, "energy_target")) {
+    // taps of e2etts_acoustic_forced: the targets at the model's level as embedded (kept as separate f0 | uv | energy planes of
+    // max(B L, B T_given) floats with rows of L or T_given columns), the decoder's input
+    const bool is_p = which[0] == 'p', is_e = which[0] == 'e';
+    if (!e->forced_last || (is_p && !e->forced_pitch) || (is_e && !e->forced_energy))
+      return e->fail(E2ETTS_ESTATE, "tap '%s': the last acoustic pass was not an e2etts_acoustic_forced call that had it", which);
+    if (!is_p && !is_e) { src = e->decin.p; n = (size_t)e->last_B * e->last_T * e->cfg.hidden; }
+    else {
+      const bool frame = is_p ? e->cfg.pitch_frame != 0 : e->cfg.energy_frame != 0;
+      const size_t N = frame ? e->last_T : e->last_L, ld = frame ? (size_t)e->forced_T : (size_t)e->last_L, rows = e->last_B;
+      const int planes = is_p && !e->cfg.pitch_no_uv ? 2 : 1;
+      n = rows * N * planes;
+      if (n_floats != n) return e->fail(E2ETTS_EINVAL, "tap '%s' holds %zu floats, caller asked for %zu", which, n, n_floats);
+      const size_t n_lvl = std::max((size_t)e->last_B * e->last_L, (size_t)e->last_B * std::max(e->forced_T, 1));
+      for (int k = 0; k < planes; ++k) {   // plane k -> column k of [B, N, planes]: one strided copy per row of N values
+        const float* pl = ptr<float>(e->ftg) + (is_e ? 2 : k) * n_lvl;
+        for (size_t b = 0; b < rows; ++b)
+          HIPCHK(e, hipMemcpy2DAsync(out + b * N * planes + k, (size_t)planes * 4, pl + b * ld, 4, 4, N, hipMemcpyDefault, e->stream));
+      }
+      HIPCHK(e, hipStreamSynchronize(e->stream));
+      return E2ETTS_OK;
+    }
+  }
   else return e->fail(E2ETTS_EKEY, "unknown tap '%s'", which);
   if (n_floats != n) return e->fail(E2ETTS_EINVAL, "tap '%s' holds %zu floats, caller asked for %zu", which, n, n_floats);
   RET(copy_out(e, out, src, n * 4));
@@ -3295,7 +3501,7 @@ int e2etts_debug_poison_workspace(e2etts_engine* e) {
     return E2ETTS_OK;
   };
   for (DevBuf* b : {&e->xa, &e->xb, &e->xs, &e->xp, &e->tmp, &e->qkv, &e->att, &e->hid, &e->p1, &e->p2, &e->attws, &e->ffpool, &e->dx, &e->dxb, &e->mel,
-                    &e->melpost, &e->pn1, &e->pn2, &e->melin})
+                    &e->melpost, &e->pn1, &e->pn2, &e->melin, &e->fattn, &e->ftgf, &e->ftg, &e->decin})
     RET(poison(*b));
   RET(poison_work(e->voc));
   RET(poison_out(e->voc));

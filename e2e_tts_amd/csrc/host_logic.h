@@ -4,6 +4,7 @@
 // conv_gemm.hip include the same header, so what the sanitizer run exercises is the code the library ships.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <cmath>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/e2etts.h"
+#include "../../include/e2etts_forced.h"
 
 namespace e2etts {
 
@@ -193,6 +195,78 @@ inline void ragged_counts(const int32_t* rows, int B, int T, int Cout, long long
   }
   *t128 = t * (((long long)Cout + 127) / 128);
   *nrows = r;
+}
+
+// ---- e2etts_acoustic_forced (include/e2etts_forced.h): what the struct asks for, checked before anything is enqueued.
+// Every member NULL: the call is e2etts_acoustic_ctl (the engine routes it there and reads nothing else of the struct).
+inline bool forced_is_null(const e2etts_forced& f) {
+  return !f.durations && !f.attn_soft && !f.mel_lens && !f.f0 && !f.uv && !f.pitch && !f.energy;
+}
+// What of the engine's state the checks depend on.
+struct ForcedShape {
+  int B = 0, L = 0;
+  int pitch_no_uv = 0, pitch_frame = 0, energy_frame = 0;   // e2etts_config
+  int max_seq_len = 0, pos_table_rows = 0;
+  unsigned long long var_pos_rows = 0;   // rows of the variance predictors' position table
+};
+// "" when the struct is served, else the message (it names the offending value).  `struct_size` is what the caller wrote into the
+// struct's first field (read before anything else; nothing of `f` is trusted when it is not this header's).  dur_host / mel_lens_host /
+// lens_host: the same arrays when they lie in HOST memory, else nullptr (device arrays are clamped by the kernels that read them).
+inline std::string forced_check(uint32_t struct_size, const e2etts_forced& f, const ForcedShape& s, const float* dur_host,
+                                const int64_t* mel_lens_host, const int64_t* lens_host) {
+  char m[256];
+  auto msg = [&](const char* fmt, auto... a) { snprintf(m, sizeof m, fmt, a...); return std::string(m); };
+  if (struct_size != sizeof(e2etts_forced))
+    return msg("e2etts_forced.struct_size = %u, this library knows %zu: the caller was built against another revision of e2etts_forced.h",
+               (unsigned)struct_size, sizeof(e2etts_forced));
+  if (s.B <= 0 || s.L <= 0) return msg("B and L must be positive (got B=%d L=%d)", s.B, s.L);
+  if (f.pitch_frames != 0 && f.pitch_frames != 1) return msg("pitch_frames = %d: expected 0 or 1", (int)f.pitch_frames);
+  if (f.energy_frames != 0 && f.energy_frames != 1) return msg("energy_frames = %d: expected 0 or 1", (int)f.energy_frames);
+  if (f.T < 0) return msg("T = %d is negative", (int)f.T);
+  if (f.T > (1 << 20)) return msg("T=%lld is unreasonably large", (long long)f.T);
+  // target kinds
+  if (s.pitch_no_uv && (f.f0 || f.uv)) return msg("an f0 / uv target was given, but the model has pitch_no_uv = %d: pass `pitch`", s.pitch_no_uv);
+  if (!s.pitch_no_uv && f.pitch) return msg("a `pitch` target was given, but the model has pitch_no_uv = %d (use_uv): pass f0 and uv", s.pitch_no_uv);
+  if ((f.f0 != nullptr) != (f.uv != nullptr)) return msg("f0 and uv come together: %s is NULL", f.f0 ? "uv" : "f0");
+  const bool has_p = f.f0 || f.pitch, has_e = f.energy != nullptr;
+  // a [B, T] target: frame-resolved, or at the level of a frame_level feature
+  const bool p_bt = has_p && (f.pitch_frames || s.pitch_frame), e_bt = has_e && (f.energy_frames || s.energy_frame);
+  const bool p_avg = has_p && f.pitch_frames && !s.pitch_frame, e_avg = has_e && f.energy_frames && !s.energy_frame;
+  if ((p_avg || e_avg) && !f.durations)
+    return msg("a frame-resolved %s target of a phoneme_level feature is averaged over `durations`, which is NULL", p_avg ? "pitch" : "energy");
+  if ((p_bt || e_bt) && f.T <= 0) return msg("a [B, T] %s target needs T, which is %d", p_bt ? "pitch" : "energy", (int)f.T);
+  // soft expansion
+  if (f.attn_soft) {
+    if (f.T <= 0) return msg("attn_soft needs T, which is %d", (int)f.T);
+    if (!f.mel_lens) return msg("attn_soft [B = %d, T = %d, L = %d] needs mel_lens, which is NULL", s.B, (int)f.T, s.L);
+    if (f.T > s.max_seq_len && f.T > s.pos_table_rows)
+      return msg("T=%lld exceeds the shipped position table (%d rows)", (long long)f.T, s.pos_table_rows);
+    if ((s.pitch_frame || s.energy_frame) && (unsigned long long)f.T + 1 > s.var_pos_rows)
+      return msg("T=%lld exceeds the variance predictors' position table (%lld rows)", (long long)f.T, (long long)s.var_pos_rows);
+    if (mel_lens_host)
+      for (int b = 0; b < s.B; ++b)
+        if (mel_lens_host[b] < 1 || mel_lens_host[b] > f.T)
+          return msg("mel_lens[%d]=%lld outside [1, %d]", b, (long long)mel_lens_host[b], (int)f.T);
+  } else if (f.mel_lens) {
+    return msg("mel_lens was given without attn_soft (T = %d): the length regulator takes its lengths from the durations", (int)f.T);
+  }
+  if (f.durations && dur_host) {
+    for (int b = 0; b < s.B; ++b) {
+      double sum = 0;
+      const long long len = lens_host ? (lens_host[b] < 0 ? 0 : (lens_host[b] > s.L ? s.L : lens_host[b])) : s.L;
+      for (int l = 0; l < s.L; ++l) {
+        const float d = dur_host[(size_t)b * s.L + l];
+        if (!(d == d) || std::isinf(d)) return msg("durations[%d, %d] = %g is not finite", b, l, (double)d);
+        if (d < 0.f) return msg("durations[%d, %d] = %g is negative", b, l, (double)d);
+        if (d != std::floor(d)) return msg("durations[%d, %d] = %g is not an integer", b, l, (double)d);
+        if (d > 1048576.f) return msg("durations[%d, %d] = %g exceeds 2^20 frames", b, l, (double)d);
+        if (l < len) sum += d;
+      }
+      if ((p_avg || e_avg) && sum > (double)f.T)
+        return msg("durations of utterance %d sum to %.0f frames, the frame-resolved targets have T = %d", b, sum, (int)f.T);
+    }
+  }
+  return std::string();
 }
 
 }  // namespace e2etts

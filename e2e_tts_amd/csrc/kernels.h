@@ -152,6 +152,61 @@ const char* launch_add_positions(float* y, const float* pos, int B, int T, int H
 // length regulator fused with the decoder position add: y[b, t, :] = (t < mel_len[b] ? x[b, ph(t), :] : 0) + pos[t, :] (pos == nullptr: without it)
 const char* launch_length_regulate(const float* x, const int32_t* cum, const int32_t* mel_lens, const float* pos,
                                    float* y, int B, int L, int T, int H, hipStream_t s);
+// ---- teacher.hip: the teacher-forced pass (include/e2etts_forced.h: e2etts_acoustic_forced; reference U/layers.py:175-272 with attn_prior)
+// Soft expansion (U/layers.py:244-245: torch.bmm(attn_soft, x)), exact fp32 on the fp32 MFMA in every precision mode:
+// out[b, t, :] = sum_{l < txt_lens[b]} attn[b, t, l] * x[b, l, :] (+ pos[t, :]).  Columns l >= txt_lens[b] of the map and rows
+// l >= txt_lens[b] of x are not read.  One chain of terms in l order per element: the same bits whatever B, T and L are.  H % 32 == 0.
+struct SoftExpandParams {
+  const float* attn = nullptr;           // [B, T, L]
+  const float* x = nullptr;              // [B, L, H]
+  const int32_t* txt_lens = nullptr;     // [B] device (clamped to [0, L])
+  const int32_t* act_rows = nullptr;     // optional [B] device: only rows < act_rows[b] are needed (ragged batches): whole 32-row tiles past
+                                         // them are skipped and keep their old contents
+  const int32_t* act_rows_host = nullptr;  // the same values in host memory (launcher only): compact grid, see RowMap
+  const float* pos = nullptr;            // optional [>= T, H]: the decoder's position rows, added in the epilogue
+  float* out = nullptr;                  // [B, T, H]
+  int B = 0, T = 0, L = 0, H = 0;
+};
+const char* launch_soft_expand(const SoftExpandParams& p, hipStream_t s);
+double soft_expand_flops(const SoftExpandParams& p);   // 2 B T L H
+// Given durations -> launch_duration's outputs, and the per-phoneme means of up to three frame-resolved targets in the same pass
+// (U/function.py:155-175 get_phoneme_level / frame2phoneme: numpy's float32 mean of frames [pos, pos + d), 0 for d == 0, the in-place
+// overwrite of the frame array reproduced; uv: 1 where the mean is exactly 1.0, U/layers.py:230-231).  One wavefront per utterance.
+struct TeacherTarget {
+  const float* src = nullptr;   // [B, T] frames
+  float* dst = nullptr;         // [B, L] means, 0 at and past the utterance's length
+  int uv = 0;                   // apply the uv rule
+};
+struct TeacherScanParams {
+  float* dur = nullptr;               // [B, L] in: durations as given; out: clamped (NaN / negative -> 0, truncated, <= 2^20, 0 at l >= txt_lens[b])
+  const int32_t* txt_lens = nullptr;  // [B]
+  int32_t* cum = nullptr;             // [B, L] inclusive scan
+  int64_t* mel64 = nullptr;           // [B] sums, or mel_given clamped to [0, T]
+  int32_t* mel32 = nullptr;
+  const int64_t* mel_given = nullptr; // optional [B] (soft expansion: the mel lengths are the caller's)
+  TeacherTarget tg[3];
+  int n_tg = 0;
+  int B = 0, L = 0, T = 0;            // T: columns of the frame rows (frames >= T are left out of a mean)
+};
+const char* launch_teacher_scan(const TeacherScanParams& p, hipStream_t s);
+// launch_variance_embed's epilogue with either feature taken from a target (no control) instead of prediction * control; a feature
+// without a target (nullptr) gives launch_variance_embed's bits.  Targets are read at [b * tld + t], t < N (tld >= N).
+struct TargetEmbedParams {
+  const float* pitch_t = nullptr;    // f0 (pitch_mode 0 / 1, with uv_t) or the pitch itself (pitch_mode 2)
+  const float* uv_t = nullptr;
+  const float* energy_t = nullptr;
+  int tld = 0, N = 0, H = 0;
+  float p_control = 1.0f, e_control = 1.0f, f0_mean = 0.f, f0_std = 1.f;
+  const float* energy_bins = nullptr;
+  const float* pitch_bins = nullptr;
+  int n_bins = 0, pitch_mode = 0, feat = 3;
+  const float* pitch_emb = nullptr;
+  const float* energy_emb = nullptr;
+  int32_t* pitch_idx = nullptr;
+  int32_t* energy_idx = nullptr;
+  VarCtl ctl;
+};
+const char* launch_target_embed(float* x, float* pitch_pred, const float* energy_pred, const TargetEmbedParams& q, int B, hipStream_t s);
 // out[b] = min(cap, (lens[b] + add) * mul + add_rows): rows a layer has to compute for utterance b in ragged mode
 const char* launch_act_rows(const int32_t* lens, int32_t* out, int B, int add, int mul, long long cap, hipStream_t s, long long add_rows = 0);
 // S = (S + Sj) [+ Sk] [/ div] over n floats (n % 4 == 0): joins the sums of ResBlocks run on side streams

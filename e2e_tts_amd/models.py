@@ -248,6 +248,11 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         or 48 kHz): the recordings are converted to the transform's rate on the device (e2e_tts_amd.resample, default filter), the mel
         library reads the result where it lies, and mel_lens follow from the converted lengths ceil(wav_lens * L / M).  None: the
         recordings are taken to be at the transform's rate, as before."""
+        out, energy, _ = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate)
+        return out + (energy,) if return_energy else out
+
+    def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate):
+        """``align_audio``'s work -> (its 4-tuple, the frame energies or None, the mel front-end's mel_lens [B] int64 on the host)."""
         from . import aligner as al
         torch = _torch()
         if stft is None:
@@ -294,13 +299,130 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         a = enc.encoder
         a._check(a.lib.e2ealign_order_after(a._h, fe.stream()), "e2ealign_order_after")   # the aligner's stream after the mel's
         a.align(mel_dev, keys, spk, tl, ml, prior, out_dur=dur, out_hard=hard, out_attn=soft, out_logprob=logprob, want=())
-        out = (soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1))
-        return out + (energy,) if return_energy else out
+        return (soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1)), energy, np.asarray(ml, dtype=np.int64).reshape(-1)
 
-    def forward(self, *a, **k):
-        raise NotImplementedError("training forward is out of scope; use .inference(), or .align() for the aligner's attn_out")
+    def _forced(self, speaker, texts, txt_lens, attn_out, mel_lens, T, p_targets, e_targets, step, after_stream):
+        """The engine's teacher-forced pass on an aligner result that lies on the device.  -> the reference's two tuples."""
+        import ctypes
+        torch = _torch()
+        eng = self._ensure_engine()
+        dev = torch.device("cuda", self._device)
+        soft4, hard4, dur, logprob4 = attn_out
+        ids = torch.as_tensor(texts, dtype=torch.int64).contiguous()
+        B, L = ids.shape
+        lens = torch.as_tensor(txt_lens, dtype=torch.int64).reshape(-1).contiguous()
+        spk = torch.as_tensor(speaker, dtype=torch.int64).reshape(-1).contiguous()
+        ml = torch.as_tensor(np.asarray(mel_lens, dtype=np.int64))
+        ve = self.config["variance"]["variance_embedding"]
+        use_uv = bool(ve["use_uv"])
+        dm = self.config["variance"]["duration_modelling"]
+        soft = int(step) < int(dm["binarization_start_steps"])
+        kw = {}
+        f32 = lambda v: torch.as_tensor(v, dtype=torch.float32).contiguous()   # noqa: E731
+        if p_targets is not None:
+            if use_uv != isinstance(p_targets, Mapping):
+                raise ValueError("p_targets must be {'f0', 'uv'} for a use_uv model and one tensor otherwise")
+            if use_uv:
+                kw.update(f0=f32(p_targets["f0"]), uv=f32(p_targets["uv"]))
+            else:
+                kw.update(pitch=f32(p_targets))
+        if e_targets is not None:
+            kw.update(energy=f32(e_targets))
+        with eng.lock:
+            if after_stream:   # the engine's stream after the aligner's, as align_audio orders the aligner after the mel
+                eng._check(eng.lib.e2etts_order_after(eng._h, ctypes.c_void_p(after_stream)), "e2etts_order_after")
+            r = eng.acoustic_forced(ids, lens, spk, durations=dur.contiguous(), attn_soft=soft4[:, 0].contiguous() if soft else None,
+                                    mel_lens=ml if soft else None, pitch_frames=True, energy_frames=True, T=T,
+                                    want=("mel_lens", "log_d"), **kw)
+            To = r["T"]
+            mel = torch.empty((B, To, self.n_channels), dtype=torch.float32, device=dev)
+            mel_post = torch.empty_like(mel)
+            eng.fetch_mel(B, To, out_mel=mel, out_mel_post=mel_post)
+            pf, ef = ve["pitch_feature"] == "frame_level", ve["energy_feature"] == "frame_level"
+
+            def tap(name, shape):   # a tap copied into a tensor on the device: no visit to the host
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+                eng.fetch_tap_into(name, t)
+                return t
+
+            p_shape = (B, To if pf else L, 2) if use_uv else (B, To if pf else L)
+            p_pred, e_pred = tap("pitch_pred", p_shape), tap("energy_pred", (B, To if ef else L))
+            p_ret = e_ret = None
+            if p_targets is not None:
+                pt = tap("pitch_target", p_shape)
+                p_ret = {"f0": pt[..., 0].contiguous(), "uv": pt[..., 1].contiguous()} if use_uv else pt
+            if e_targets is not None:
+                e_ret = tap("energy_target", (B, To if ef else L))
+        out_lens = torch.from_numpy(r["mel_lens"]).to(dev)
+        lens_d = lens.to(dev)
+        txt_masks = torch.arange(L, device=dev)[None, :] >= lens_d[:, None]           # get_mask_from_lengths
+        mel_masks = torch.arange(To, device=dev)[None, :] >= out_lens[:, None]
+        return ((mel, mel_post, torch.from_numpy(r["log_d"]).to(dev), p_pred, e_pred, lens_d, txt_masks, out_lens, mel_masks,
+                 (soft4, hard4, dur, logprob4)), (p_ret, e_ret))
+
+    @staticmethod
+    def _check_lengths(txt_lens, mel_lens):
+        tl = np.asarray(_torch().as_tensor(txt_lens).cpu(), dtype=np.int64).reshape(-1)
+        ml = np.asarray(_torch().as_tensor(mel_lens).cpu(), dtype=np.int64).reshape(-1)
+        bad = np.nonzero(ml < tl)[0]
+        if bad.size:
+            b = int(bad[0])
+            raise ValueError(f"row {b}: mel_len {int(ml[b])} < txt_len {int(tl[b])}: the monotonic alignment needs a frame per phoneme")
+        return tl, ml
+
+    def forward(self, inputs=None, step=0):
+        """The reference's teacher-forced forward in eval() (U/model.py:95-153; what generate_mel calls): ``inputs`` is its 10-tuple
+        (speakers, texts, mels [B, T, n_mel], attn_priors, p_targets, e_targets, txt_lens, max_txt_len, mel_lens, max_mel_len) with the
+        targets at FRAME level ({"f0", "uv"} of [B, T], or one [B, T] tensor for a model without use_uv; None = embed the prediction).
+        -> the reference's two tuples, (mel, mel_post, log_d, pitch_pred, energy_pred, txt_lens, txt_masks, mel_lens, mel_masks, attn_out),
+        (p_targets, e_targets) as embedded; attn_out comes from the aligner library, and its soft map and durations are handed to the
+        engine where they lie.  step < binarization_start_steps (generate_mel: 0) expands the phonemes with the soft map, else with the
+        length regulator on the MAS durations.  Training (no inputs, or train mode) stays out of scope."""
+        if inputs is None or self.training:
+            raise NotImplementedError("training forward is out of scope; use .inference(), or .align() for the aligner's attn_out")
+        speakers, texts, mels, attn_priors, p_targets, e_targets, txt_lens, max_txt_len, mel_lens, max_mel_len = inputs
+        torch = _torch()
+        ids = torch.as_tensor(texts)
+        if max_txt_len is not None and int(max_txt_len) != ids.shape[1]:
+            raise ValueError(f"max_txt_len={int(max_txt_len)} != texts.shape[1]={ids.shape[1]}")
+        T = int(torch.as_tensor(mels).shape[1])
+        if max_mel_len is not None and int(max_mel_len) != T:
+            raise ValueError(f"max_mel_len={int(max_mel_len)} != mels.shape[1]={T}")
+        _, ml = self._check_lengths(txt_lens, mel_lens)   # before any launch
+        attn_out = self.align(speakers, texts, txt_lens, mels, mel_lens, attn_prior=attn_priors)
+        return self._forced(speakers, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, self._ensure_aligner()[0].encoder.stream())
 
     __call__ = forward
+
+    def forward_audio(self, speaker, texts, txt_lens, wavs, wav_lens, p_targets=None, e_targets=None, step=0, wav_rate=None):
+        """``align_audio`` followed by the teacher-forced pass: recordings -> ground-truth-aligned mels, with the mel, the soft map and the
+        durations never leaving the device.  p_targets / e_targets: frame-level targets [B, T] as for ``forward`` (T = the mel frames of
+        the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``: as for ``align_audio``.
+        -> ``forward``'s two tuples."""
+        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate)
+        self._check_lengths(txt_lens, ml)
+        T = int(attn_out[0].shape[2])
+        return self._forced(speaker, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, self._ensure_aligner()[0].encoder.stream())
+
+
+def f0_targets(f0_hz, stats: Mapping[str, object], pitch_quantization: str = "linear", pitch_eps: float = 0.000000001):
+    """A recording's f0 track in Hz (0 = unvoiced) -> (f0 target, uv target) as the reference's data loader makes them (get_f0,
+    src/tools/dataloader.py:185-196): uv = f0 == 0; f0 normalised with stats["f0"] -- or log2(f0 + pitch_eps) for pitch_quantization
+    "log" --; unvoiced stretches filled by linear interpolation between their voiced neighbours (np.interp: constant beyond the first and
+    the last voiced frame), an all-unvoiced track set to 0.  The f0 extractor itself (parselmouth in the reference) is not part of this
+    package: callers bring the Hz track.  -> (f0 in the input's float dtype, uv float32), numpy arrays of one utterance [T]."""
+    f0 = np.array(f0_hz, copy=True)
+    if f0.ndim != 1:
+        raise ValueError(f"f0_targets takes one utterance's track [T], got shape {f0.shape}")
+    if f0.dtype.kind != "f":
+        f0 = f0.astype(np.float64)
+    uv = f0 == 0
+    f0 = np.log2(f0 + pitch_eps) if pitch_quantization == "log" else (f0 - stats["f0"]["mean"]) / stats["f0"]["std"]
+    if sum(uv) == len(f0):
+        f0[uv] = 0
+    elif sum(uv) > 0:
+        f0[uv] = np.interp(np.where(uv)[0], np.where(~uv)[0], f0[~uv])
+    return f0, uv.astype(np.float32)
 
 
 class AlignmentEncoder:

@@ -190,6 +190,10 @@ E2ETTS_API int e2etts_acoustic_ctl(e2etts_engine* engine, const int64_t* ids, co
                         const float* e_control, int n_e, float* dur_out, int64_t* mel_lens_out, int* T_out, int32_t* pitch_idx_out,
                         int32_t* energy_idx_out, float* log_dur_out, float* pitch_pred_out, float* energy_pred_out);
 
+/* The TEACHER-FORCED pass (UnsupervisedFastSpeech2.forward in eval(), U/model.py:95-153: durations, pitch and energy given instead of
+ * predicted) is e2etts_acoustic_forced of include/e2etts_forced.h, served by the companion library libe2etts_forced.so on an engine of
+ * this library: this header and the symbols libe2etts_hip.so exports are unchanged by it. */
+
 /* Copies of the resident results of the last e2etts_acoustic: mel, mel_post [B, T, n_mel] (either may be NULL). */
 E2ETTS_API int e2etts_fetch_mel(e2etts_engine* engine, float* mel, float* mel_post);
 
@@ -197,6 +201,8 @@ E2ETTS_API int e2etts_fetch_mel(e2etts_engine* engine, float* mel, float* mel_po
 /* taps: "enc_out" [B, L, hidden], "dec_out" [B, T, hidden] (after e2etts_acoustic); "istft_spec_phase" [B, T * prod(voc_up_rate) + 1,
  * n_fft + 2] = exp / sin heads of the iSTFTNet generator (reference iSTFT.forward's return values), after a vocoder call. */
 E2ETTS_API int e2etts_fetch_tap(e2etts_engine* engine, const char* which, float* out, size_t n_floats);
+/* after e2etts_acoustic_forced (include/e2etts_forced.h) also "pitch_target", "energy_target", "dec_in" (see there; E2ETTS_ESTATE after any other
+ * acoustic pass). */
 /* more taps of the last e2etts_acoustic, at the level the feature lives at (N = L for phoneme_level, T for frame_level):
  * e2etts_fetch_tap: "pitch_pred" [B, N, 2] ([B, N] when pitch_no_uv), "energy_pred" [B, N]; e2etts_fetch_tap_i32: "pitch_idx", "energy_idx" [B, N]. */
 E2ETTS_API int e2etts_fetch_tap_i32(e2etts_engine* engine, const char* which, int32_t* out, size_t n_values);
