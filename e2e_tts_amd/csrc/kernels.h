@@ -108,10 +108,18 @@ long long attention_par_max_grid();
 const char* launch_layernorm(const float* x, float* y, const float* gamma, const float* beta, const int32_t* lens,
                              int B, int N, int C, float eps, hipStream_t s);
 
+// a * b rounded to float32 on its own, for the kernels whose contract is one rounding per operation.  __fmul_rn is a plain product in
+// this toolchain, and the default contraction mode fuses it into an add or subtract that consumes it; a product formed under
+// contract(off) carries no such licence, whatever consumes it.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // x[b, l, :] = emb[ids[b, l], :] + pos[l, :]
 const char* launch_embed(const int64_t* ids, const float* emb, const float* pos, float* x, int B, int L, int H,
                          int n_rows, hipStream_t s);
-// x[b, l, :] = xin[b, l, :] + spk[speaker[b or 0], :]   (xin may be x)
+// x[b, l, :] = xin[b, l, :] + spk[speaker[b or 0], :]   (xin may be x; H % 4 == 0; ids outside [0, n_speakers) are clamped into it)
 const char* launch_add_speaker(const float* xin, float* x, const float* spk, const int64_t* speaker, int n_spk_ids, int n_speakers,
                                int B, int L, int H, hipStream_t s);
 // y = x + alpha[0] * table[pos(b, l)], pos = running count of x[b, l, 0] != 0 (0 where it is 0)
@@ -119,6 +127,7 @@ const char* launch_add_speaker(const float* xin, float* x, const float* spk, con
 const char* launch_var_positions(const float* x, int32_t* posbuf, const float* table, int table_rows, const float* alpha,
                                  float* y, int B, int L, int H, hipStream_t s, bool compute_positions = true);
 // out[row, o] = dot(x[row, :], w[o, :]) + b[o], o < O <= 2; rows >= lens[b] -> 0 when lens != null
+// (C % 4 == 0, B * L > 0, x and w 16-byte aligned: anything else is refused)
 const char* launch_rowdot(const float* x, const float* w, const float* b, float* out, const int32_t* lens, int B, int L,
                           int C, int O, hipStream_t s);
 // Per-utterance / per-phoneme controls of the _ctl entry points (include/e2etts.h): element (b, l) is p[b * sb + l * sl] -- one value
@@ -136,11 +145,16 @@ struct VarCtl {
   int Lp = 0;
 };
 // duration_rounded, integer durations, inclusive scan -> mel_lens; one block per utterance
+// dur = max(rint(exp(log_d) - 1) * control, 0) in float32, repeat count = trunc(dur) capped at 2^20, cum = inclusive scan of the counts
+// saturated at 2^31 - 1, mel_lens64 = the unsaturated sum.  NaN (a NaN log_d or control, or inf * 0): the repeat count is 0 and dur holds
+// 0, not NaN -- the maximum drops the NaN operand, where torch.clamp(min = 0) of the reference (U/layers.py:218-221) would hand NaN on.
 const char* launch_duration(const float* log_d, float d_control, float* dur, int32_t* cum, int64_t* mel_lens64,
                             int32_t* mel_lens32, int B, int L, hipStream_t s, CtlRef d_ctl = CtlRef());
 // pitch / energy bucket indices + x += pitch_emb[pidx] + energy_emb[eidx]
 // pitch_mode 0: f0 = pred[0] * std + mean, zeroed where pred[1] > 0 (uv), tensor_f0_to_coarse; 1: the same with f0 = 2 ** pred[0]
 // (pitch_quantization "log"); 2: use_uv False -- ONE prediction per row, bucketize(pred * p_control, pitch_bins) (U/layers.py:136-160)
+// The bucket of a value is the first index whose boundary is >= it (torch.bucketize, right = False); NaN goes past the last boundary
+// (n_bins - 1), as torch.bucketize puts it.  Modes 0 / 1 on a NaN f0: an index inside [0, n_bins - 1], otherwise unspecified.
 const char* launch_variance_embed(float* x, float* pitch_pred /*[B,L,2], scaled in place by p_control; mode 2: [B,L], left as it is*/,
                                   const float* energy_pred, float p_control, float e_control, float f0_mean,
                                   float f0_std, const float* energy_bins, int n_bins, const float* pitch_emb,
@@ -362,6 +376,8 @@ size_t x3_frag_bytes(int Cout, int KW, int Cin);
 const char* launch_f32_to_frag(const float* w, float* frag, int Cout, int KW, int Cin, hipStream_t s);
 
 // iSTFTNet tail: leaky ReLU + ReflectionPad1d((1, 0)) on channels-last frames; exp / sin heads, inverse STFT with overlap-add
+// (n_fft a power of two in [4, 256], hop a proper divisor of it -- hop == n_fft leaves the periodic Hann window's squared sum 0 at the
+// frame joins and is refused, as torch.istft refuses it --, F >= 2, ldq >= n_fft + 2)
 const char* launch_reflect_lrelu(const float* in, float* out, int B, long long n, int C, float slope, hipStream_t s);
 const char* launch_istft(const float* q, int ldq, float* specphase, float* ri, float* wav, int16_t* pcm, int B, long long F, int nfft,
                          int hop, hipStream_t s);

@@ -134,7 +134,7 @@ __global__ void var_pos_add_kernel(const float* __restrict__ x, const int32_t* _
   for (int i = threadIdx.x; i < H / 4; i += blockDim.x) {
     const float4 v = xr[i], t = tr[i];
     // x + (alpha * table): two roundings, as the reference computes it
-    yr[i] = make_float4(v.x + __fmul_rn(a, t.x), v.y + __fmul_rn(a, t.y), v.z + __fmul_rn(a, t.z), v.w + __fmul_rn(a, t.w));
+    yr[i] = make_float4(v.x + mul_rn(a, t.x), v.y + mul_rn(a, t.y), v.z + mul_rn(a, t.z), v.w + mul_rn(a, t.w));
   }
 }
 
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(64) void duration_kernel(const float* __restrict__ 
     float d = 0.f;
     if (l < L) {
       const float e = __fsub_rn(expf(log_d[b * L + l]), 1.0f);
-      d = fmaxf(__fmul_rn(rintf(e), ctl.p ? ctl.p[(long long)b * ctl.sb + (long long)l * ctl.sl] : d_control), 0.f);
+      d = fmaxf(mul_rn(rintf(e), ctl.p ? ctl.p[(long long)b * ctl.sb + (long long)l * ctl.sl] : d_control), 0.f);
       dur[b * L + l] = d;
     }
     int v = d == d ? (int)fminf(d, 1048576.f) : 0;  // <= 2^20 each, 64 lanes: the wave's scan stays below 2^26
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(64) void duration_kernel(const float* __restrict__ 
 // ---------------------------------------------------------------- pitch / energy buckets + embedding add
 // f0 bucket: reference U/layers.py:145-154 + U/function.py:178-187 (constants :9-13); energy: torch.bucketize
 // (right = False) on linspace bins (U/layers.py:169).  Every fp32 operation is kept a separate rounding
-// (__f*_rn: no FMA contraction) so that the integer results track the reference's elementwise torch ops.
+// (mul_rn, kernels.h: no FMA contraction) so that the integer results track the reference's elementwise torch ops.
 __global__ __launch_bounds__(128) void variance_embed_kernel(float* __restrict__ x, float* __restrict__ pitch_pred,
                                                              const float* __restrict__ energy_pred, float p_control,
                                                              float e_control, float f0_mean, float f0_std,
@@ -231,20 +231,20 @@ __global__ __launch_bounds__(128) void variance_embed_kernel(float* __restrict__
   // feat: bit 0 = pitch, bit 1 = energy take part in this pass (the other one lives at the other level: phoneme / frame, U/layers.py:226-257)
   if (!(feat & 1)) {
   } else if (pitch_mode == 2) {  // use_uv False (U/layers.py:155-157): bucketize(prediction * control, pitch_bins), right = False
-    f0 = __fmul_rn(pitch_pred[row], p_control);
+    f0 = mul_rn(pitch_pred[row], p_control);
     int lo = 0, hi = n_bins - 1;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (pitch_bins[mid] < f0) lo = mid + 1; else hi = mid;
+      if (!(pitch_bins[mid] >= f0)) lo = mid + 1; else hi = mid;   // (NaN: past the last boundary, as torch.bucketize)
     }
     pidx = lo;
   } else {
-    f0 = __fmul_rn(pitch_pred[2 * row], p_control);
-    uvl = __fmul_rn(pitch_pred[2 * row + 1], p_control);
-    float f0d = pitch_mode == 1 ? powf(2.0f, f0) : __fadd_rn(__fmul_rn(f0, f0_std), f0_mean);  // U/layers.py:148-151
+    f0 = mul_rn(pitch_pred[2 * row], p_control);
+    uvl = mul_rn(pitch_pred[2 * row + 1], p_control);
+    float f0d = pitch_mode == 1 ? powf(2.0f, f0) : __fadd_rn(mul_rn(f0, f0_std), f0_mean);  // U/layers.py:148-151
     if (uvl > 0.f) f0d = 0.f;
-    float mel = __fmul_rn(1127.0f, logf(__fadd_rn(1.0f, __fdiv_rn(f0d, 700.0f))));
-    if (mel > 0.f) mel = __fadd_rn(__fdiv_rn(__fmul_rn(__fsub_rn(mel, mel_min), 254.0f), mel_range), 1.0f);
+    float mel = mul_rn(1127.0f, logf(__fadd_rn(1.0f, __fdiv_rn(f0d, 700.0f))));
+    if (mel > 0.f) mel = __fadd_rn(__fdiv_rn(mul_rn(__fsub_rn(mel, mel_min), 254.0f), mel_range), 1.0f);
     if (mel <= 1.f) mel = 1.f;
     if (mel > 255.f) mel = 255.f;
     pidx = (int)__fadd_rn(mel, 0.5f);
@@ -252,14 +252,15 @@ __global__ __launch_bounds__(128) void variance_embed_kernel(float* __restrict__
   }
   int eidx = 0;
   if (feat & 2) {
-    const float e = __fmul_rn(energy_pred[row], e_control);
-    int lo = 0, hi = n_bins - 1;  // first index with bins[idx] >= e; n_bins - 1 boundaries
+    const float e = mul_rn(energy_pred[row], e_control);
+    int lo = 0, hi = n_bins - 1;  // first index with bins[idx] >= e; n_bins - 1 boundaries (NaN: n_bins - 1, as torch.bucketize)
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (energy_bins[mid] < e) lo = mid + 1; else hi = mid;
+      if (!(energy_bins[mid] >= e)) lo = mid + 1; else hi = mid;
     }
     eidx = lo;
   }
+  __syncthreads();  // every wave has read the prediction before thread 0 scales it in place
   if (threadIdx.x == 0) {
     if ((feat & 1) && pitch_mode != 2) {  // (mode 2 hands back the prediction before the control, as the reference does: U/layers.py:156,162)
       pitch_pred[2 * row] = f0;
@@ -725,7 +726,7 @@ __global__ __launch_bounds__(TPB) void conv_post_kernel(const float* __restrict_
   }
   const float v = tanhf(acc + bias[0]);
   if (wav) wav[(long long)b * N + t] = v;
-  if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)__fmul_rn(v, 32768.0f);
+  if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)mul_rn(v, 32768.0f);
 }
 
 // The same tail in precision "bf16_act" (include/e2etts.h): x bf16 [B, N, C]; x = bf16(lrelu_0.01(x)); y = bf16(conv + b) with the bf16-rounded
@@ -787,7 +788,7 @@ __global__ __launch_bounds__(TPB) void conv_post_bf16_kernel(const __bf16* __res
   }
   const float v = cp_rnd<FP16>(tanhf(cp_rnd<FP16>(acc + bias[0])));
   if (wav) wav[(long long)b * N + t] = v;
-  if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)__fmul_rn(v, 32768.0f);
+  if (pcm) pcm[(long long)b * N + t] = (int16_t)(int32_t)mul_rn(v, 32768.0f);
 }
 
 }  // namespace
@@ -824,6 +825,7 @@ const char* launch_add_speaker(const float* xin, float* x, const float* spk, con
                                int B, int L, int H, hipStream_t s) {
   if (!xin || !x || !spk || !speaker) return "add_speaker: null pointer";
   if (n_spk_ids != 1 && n_spk_ids != B) return "add_speaker: speaker must have 1 or B entries";
+  if (H % 4 || H <= 0 || B <= 0 || L <= 0 || n_speakers <= 0) return "add_speaker: bad dims";
   hipLaunchKernelGGL(add_speaker_kernel, dim3(B * L), dim3(128), 0, s, xin, x, spk, speaker, n_spk_ids, n_speakers, L, H);
   return CHECK_LAUNCH("add_speaker");
 }
@@ -831,7 +833,8 @@ const char* launch_add_speaker(const float* xin, float* x, const float* spk, con
 const char* launch_rowdot(const float* x, const float* w, const float* b, float* out, const int32_t* lens, int B, int L,
                           int C, int O, hipStream_t s) {
   if (!x || !w || !b || !out) return "rowdot: null pointer";
-  if (C % 4 || O <= 0 || O > 4) return "rowdot: bad dims";
+  if (C % 4 || C <= 0 || O <= 0 || O > 2 || B <= 0 || L <= 0) return "rowdot: bad dims";
+  if (((uintptr_t)x | (uintptr_t)w) & 15) return "rowdot: x and w must be 16-byte aligned";
   const int rows = B * L;
   hipLaunchKernelGGL(rowdot_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, w, b, out, lens, rows, L, C, O);
   return CHECK_LAUNCH("rowdot");
@@ -840,6 +843,7 @@ const char* launch_rowdot(const float* x, const float* w, const float* b, float*
 const char* launch_duration(const float* log_d, float d_control, float* dur, int32_t* cum, int64_t* mel_lens64,
                             int32_t* mel_lens32, int B, int L, hipStream_t s, CtlRef d_ctl) {
   if (!log_d || !dur || !cum || !mel_lens64 || !mel_lens32) return "duration: null pointer";
+  if (B <= 0 || L <= 0) return "duration: bad dims";
   hipLaunchKernelGGL(duration_kernel, dim3(B), dim3(64), 0, s, log_d, d_control, d_ctl, dur, cum, mel_lens64, mel_lens32, L);
   return CHECK_LAUNCH("duration");
 }
@@ -1003,6 +1007,9 @@ const char* launch_istft(const float* q, int ldq, float* specphase, float* ri, f
                          int hop, hipStream_t s) {
   if (!q || !specphase || !ri) return "istft: null pointer";
   if (nfft < 4 || nfft > 256 || (nfft & (nfft - 1)) || hop <= 0 || nfft % hop || F < 2) return "istft: n_fft must be a power of two in [4, 256], hop must divide it";
+  // hop == n_fft: the periodic Hann window is 0 at m = 0, so the squared-window sum is 0 at every frame join (0 / 0); torch.istft refuses it too
+  if (hop >= nfft) return "istft: hop must be below n_fft (the window sum is zero at the frame joins)";
+  if (B <= 0 || ldq < nfft + 2) return "istft: bad dims";
   const int bins = nfft / 2 + 1;
   const long long total = (long long)B * F * bins;
   hipLaunchKernelGGL(istft_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, q, ldq, specphase,
@@ -1082,6 +1089,7 @@ const char* launch_var_positions(const float* x, int32_t* posbuf, const float* t
                                   float* y, int B, int L, int H, hipStream_t s, bool compute_positions) {
   if (!x || !posbuf || !table || !alpha || !y) return "var_positions: null pointer";
   if (L + 1 > table_rows) return "var_positions: sequence longer than the shipped position table";
+  if (H % 4 || H <= 0 || B <= 0 || L <= 0) return "var_positions: bad dims";
   if (compute_positions) hipLaunchKernelGGL(var_positions_kernel, dim3(B), dim3(64), 0, s, x, posbuf, L, H);
   hipLaunchKernelGGL(var_pos_add_kernel, dim3(B * L), dim3(128), 0, s, x, posbuf, table, table_rows, alpha, y, H);
   return CHECK_LAUNCH("var_positions");

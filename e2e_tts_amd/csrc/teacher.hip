@@ -245,11 +245,11 @@ __global__ __launch_bounds__(128) void target_embed_kernel(float* __restrict__ x
   int pidx = 0;
   if (!(feat & 1)) {
   } else if (q.pitch_mode == 2) {
-    f0 = p_tgt ? q.pitch_t[ti] : __fmul_rn(pitch_pred[row], p_control);
+    f0 = p_tgt ? q.pitch_t[ti] : mul_rn(pitch_pred[row], p_control);
     int lo = 0, hi = n_bins - 1;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (q.pitch_bins[mid] < f0) lo = mid + 1; else hi = mid;
+      if (!(q.pitch_bins[mid] >= f0)) lo = mid + 1; else hi = mid;   // (NaN: past the last boundary, as torch.bucketize)
     }
     pidx = lo;
   } else {
@@ -257,13 +257,13 @@ __global__ __launch_bounds__(128) void target_embed_kernel(float* __restrict__ x
       f0 = q.pitch_t[ti];
       uvl = q.uv_t[ti];
     } else {
-      f0 = __fmul_rn(pitch_pred[2 * row], p_control);
-      uvl = __fmul_rn(pitch_pred[2 * row + 1], p_control);
+      f0 = mul_rn(pitch_pred[2 * row], p_control);
+      uvl = mul_rn(pitch_pred[2 * row + 1], p_control);
     }
-    float f0d = q.pitch_mode == 1 ? powf(2.0f, f0) : __fadd_rn(__fmul_rn(f0, q.f0_std), q.f0_mean);
+    float f0d = q.pitch_mode == 1 ? powf(2.0f, f0) : __fadd_rn(mul_rn(f0, q.f0_std), q.f0_mean);
     if (uvl > 0.f) f0d = 0.f;
-    float mel = __fmul_rn(1127.0f, logf(__fadd_rn(1.0f, __fdiv_rn(f0d, 700.0f))));
-    if (mel > 0.f) mel = __fadd_rn(__fdiv_rn(__fmul_rn(__fsub_rn(mel, mel_min), 254.0f), mel_range), 1.0f);
+    float mel = mul_rn(1127.0f, logf(__fadd_rn(1.0f, __fdiv_rn(f0d, 700.0f))));
+    if (mel > 0.f) mel = __fadd_rn(__fdiv_rn(mul_rn(__fsub_rn(mel, mel_min), 254.0f), mel_range), 1.0f);
     if (mel <= 1.f) mel = 1.f;
     if (mel > 255.f) mel = 255.f;
     pidx = (int)__fadd_rn(mel, 0.5f);
@@ -271,14 +271,15 @@ __global__ __launch_bounds__(128) void target_embed_kernel(float* __restrict__ x
   }
   int eidx = 0;
   if (feat & 2) {
-    const float e = e_tgt ? q.energy_t[ti] : __fmul_rn(energy_pred[row], e_control);
+    const float e = e_tgt ? q.energy_t[ti] : mul_rn(energy_pred[row], e_control);
     int lo = 0, hi = n_bins - 1;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
-      if (q.energy_bins[mid] < e) lo = mid + 1; else hi = mid;
+      if (!(q.energy_bins[mid] >= e)) lo = mid + 1; else hi = mid;
     }
     eidx = lo;
   }
+  __syncthreads();  // every wave has read the prediction before thread 0 scales it in place
   if (threadIdx.x == 0) {
     if ((feat & 1) && q.pitch_mode != 2 && !p_tgt) {
       pitch_pred[2 * row] = f0;
