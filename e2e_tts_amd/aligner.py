@@ -17,7 +17,7 @@ from ._lib import _addr, _expect, _is_cuda
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align.so")
-# the TEST build of the same source (-DE2EALIGN_TEST_HOOKS: one more export, e2ealign_debug_poison_workspace), loaded instead of the product
+# the TEST build of the same source (-DE2EALIGN_TEST_HOOKS: two more exports, e2ealign_debug_poison_workspace and e2ealign_debug_attention), loaded instead of the product
 # library only when E2ETTS_TEST_HOOKS=1 is in the environment (_companion.load)
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align_test.so")
 ABI_VERSION = 1   # E2EALIGN_ABI_VERSION of the include/e2etts_align.h this binding mirrors
@@ -44,7 +44,8 @@ SIGNATURES = {
     "e2ealign_profile_enable": (_I, [_P, _I]),
     "e2ealign_profile_read": (_I, [_P, C.POINTER(C.c_double)]),
 }
-HOOK_SIGNATURES = {"e2ealign_debug_poison_workspace": (_I, [_P])}
+HOOK_SIGNATURES = {"e2ealign_debug_poison_workspace": (_I, [_P]),
+                   "e2ealign_debug_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P])}
 EXPORTED_SYMBOLS = list(SIGNATURES)
 TEST_HOOK_SYMBOLS = list(HOOK_SIGNATURES)
 
@@ -131,6 +132,19 @@ class Aligner(_companion.CompanionHandle):
         self._order(mel, keys, speaker, txt_lens, prior, out_attn, out_logprob)
         self._check(self.lib.e2ealign_forward(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(prior), B, T, L,
                                               _addr(out_attn), _addr(out_logprob)), "e2ealign_forward")
+        return r
+
+    def debug_attention(self, q, k, prior=None, txt_lens=None, want=("attn", "attn_logprob")):
+        """Test build only (E2ETTS_TEST_HOOKS=1), next to poison_workspace: the attention pass of forward() alone on projections given by the
+        caller, q [B, T, n_att] and k [B, L, n_att] float32 (no weights needed) -> dict with "attn" and "attn_logprob" [B, T, L]."""
+        B, T, L = int(q.shape[0]), int(q.shape[1]), int(k.shape[1])
+        _expect(q, "q", "float32", B * T * self.n_att)
+        _expect(k, "k", "float32", B * L * self.n_att)
+        _expect(prior, "prior", "float32", B * T * L)
+        txt_lens = self._lens(txt_lens, B, "txt_lens")
+        r = {name: np.empty((B, T, L), np.float32) for name in want}
+        self._order(q, k, prior, txt_lens)
+        self._hook("attention", _addr(q), _addr(k), _addr(prior), _addr(txt_lens), B, T, L, _addr(r.get("attn")), _addr(r.get("attn_logprob")))
         return r
 
     def mas(self, attn, in_lens, out_lens, B: Optional[int] = None, T: Optional[int] = None, L: Optional[int] = None, log_map: bool = False,

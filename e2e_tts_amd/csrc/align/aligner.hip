@@ -387,6 +387,11 @@ struct FwdArgs {
   int B, T, L;
 };
 
+int check_attention_tile(e2ealign_handle* h, int L) {
+  if (attn_lds_bytes(4, L, h->n_att) > ATTN_LDS_MAX) return h->fail(E2EALIGN_EINVAL, "L * n_att too large for the attention pass's LDS tile");
+  return E2EALIGN_OK;
+}
+
 int check_forward(e2ealign_handle* h, const FwdArgs& a) {
   RET(check_dims(h, a.B, a.T, a.L));
   if (!a.mel || !a.keys) return h->fail(E2EALIGN_EINVAL, "mel and keys must not be NULL");
@@ -395,7 +400,23 @@ int check_forward(e2ealign_handle* h, const FwdArgs& a) {
   // 256-byte aligned buffers): refused here, so that no launcher can object once copies are enqueued
   if ((long long)a.T * 2 * h->n_mel * 4 >= (1LL << 31) || (long long)a.L * 2 * h->n_text * 4 >= (1LL << 31))
     return h->fail(E2EALIGN_EINVAL, "one utterance's widest projection (T * 2 n_mel or L * 2 n_text floats) must stay below 2 GiB");
-  if (attn_lds_bytes(4, a.L, h->n_att) > ATTN_LDS_MAX) return h->fail(E2EALIGN_EINVAL, "L * n_att too large for the attention pass's LDS tile");
+  return check_attention_tile(h, a.L);
+}
+
+// The attention pass on device q [B, T, n_att] and k [B, L, n_att] into the handle's attn / attn_logprob: the ONE place that chooses the frame
+// tile (16 frames per workgroup while the tile fits the LDS limit, 4 otherwise; check_attention_tile has refused what 4 cannot hold).
+// run_forward and the test build's e2ealign_debug_attention both launch through it.
+int launch_attention(e2ealign_handle* h, const float* q, const float* k, const float* prior, const int32_t* lens, int B, int T, int L) {
+  const int A = h->n_att;
+  hipStream_t s = h->stream;
+  if (attn_lds_bytes(16, L, A) <= ATTN_LDS_MAX) {
+    hipLaunchKernelGGL(aln_attn_kernel<4>, dim3((T + 15) / 16, B), dim3(256), attn_lds_bytes(16, L, A), s, q, k, prior, lens, (float*)h->attn.p,
+                       (float*)h->logp.p, T, L, A, h->temperature);
+  } else {
+    hipLaunchKernelGGL(aln_attn_kernel<1>, dim3((T + 3) / 4, B), dim3(256), attn_lds_bytes(4, L, A), s, q, k, prior, lens, (float*)h->attn.p,
+                       (float*)h->logp.p, T, L, A, h->temperature);
+  }
+  HIPCHK(h, hipGetLastError());
   return E2EALIGN_OK;
 }
 
@@ -446,14 +467,7 @@ int run_forward(e2ealign_handle* h, const FwdArgs& a) {
   KCHK(h, launch_conv_gemm(conv(qx, h->q4w, h->q4b, qy, B, T, M, A, 1, ACT_NONE), s));
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[1], s));
   const int32_t* lens = a.txt_lens ? (const int32_t*)h->lens_txt.p : nullptr;
-  if (attn_lds_bytes(16, L, A) <= ATTN_LDS_MAX) {
-    hipLaunchKernelGGL(aln_attn_kernel<4>, dim3((T + 15) / 16, B), dim3(256), attn_lds_bytes(16, L, A), s, (const float*)qy, (const float*)kenc, prior, lens,
-                       (float*)h->attn.p, (float*)h->logp.p, T, L, A, h->temperature);
-  } else {
-    hipLaunchKernelGGL(aln_attn_kernel<1>, dim3((T + 3) / 4, B), dim3(256), attn_lds_bytes(4, L, A), s, (const float*)qy, (const float*)kenc, prior, lens,
-                       (float*)h->attn.p, (float*)h->logp.p, T, L, A, h->temperature);
-  }
-  HIPCHK(h, hipGetLastError());
+  RET(launch_attention(h, qy, kenc, prior, lens, B, T, L));
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[2], s));
   h->rB = B; h->rT = T; h->rL = L;
   return E2EALIGN_OK;
@@ -688,6 +702,41 @@ int e2ealign_debug_poison_workspace(e2ealign_handle* h) {
   RET(poison_workspaces(h));
   h->rB = h->rT = h->rL = 0;
   return E2EALIGN_OK;
+}
+
+int e2ealign_debug_attention(e2ealign_handle* h, const float* q, const float* k, const float* prior, const int64_t* txt_lens, int B, int T, int L,
+                             float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  RET(check_dims(h, B, T, L));
+  if (!q || !k) return h->fail(E2EALIGN_EINVAL, "q and k must not be NULL");
+  RET(check_attention_tile(h, L));
+  std::vector<int64_t> tl;
+  if (txt_lens) {
+    RET(fetch_host(h, txt_lens, B, tl));
+    RET(check_lens(h, tl, L, "txt_lens", "L"));
+  }
+  RET(begin_call(h));
+  const size_t A = h->n_att, n = (size_t)B * T * L * 4;
+  h->rB = h->rT = h->rL = 0;
+  RET(reserve(h, h->qy, (size_t)B * T * A * 4));
+  RET(reserve(h, h->kenc, (size_t)B * L * A * 4));
+  RET(reserve(h, h->attn, n));
+  RET(reserve(h, h->logp, n));
+  if (txt_lens) RET(upload_lens(h, h->lens_txt, h->host_txt, tl));
+  const float* dprior = nullptr;
+  if (prior) {
+    RET(reserve(h, h->prior, n));
+    HIPCHK(h, hipMemcpyAsync(h->prior.p, prior, n, hipMemcpyDefault, h->stream));
+    dprior = (const float*)h->prior.p;
+  }
+  HIPCHK(h, hipMemcpyAsync(h->qy.p, q, (size_t)B * T * A * 4, hipMemcpyDefault, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->kenc.p, k, (size_t)B * L * A * 4, hipMemcpyDefault, h->stream));
+  RET(launch_attention(h, (const float*)h->qy.p, (const float*)h->kenc.p, dprior, txt_lens ? (const int32_t*)h->lens_txt.p : nullptr, B, T, L));
+  h->rB = B; h->rT = T; h->rL = L;
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, false, false);
 }
 #endif
 

@@ -15,11 +15,18 @@
 #include "kernels.h"
 
 #include <cfloat>
+#include <climits>
 
 namespace e2etts {
 namespace {
 
 #define CHECK_LAUNCH(name) (hipGetLastError() == hipSuccess ? nullptr : name ": launch failed")
+
+// Every arithmetic step of these passes is ONE correctly rounded float32 operation (kernels.h states the contract; the per-kernel tests
+// compare bit for bit).  Products go through mul_rn: __fmul_rn is a plain product here, which the compiler contracts into the add or subtract
+// that consumes it.  The root is sqrtf, which compiles to the hardware estimate plus the correction against its neighbours; __fsqrt_rn
+// compiles to the bare estimate.
+__device__ __forceinline__ float magnitude(float re, float im) { return sqrtf(__fadd_rn(mul_rn(re, re), mul_rn(im, im))); }
 
 // One thread per 4 consecutive positions of the padded signal of utterance blockIdx.y (hop % 32 == 0: rows and float4s line up).
 __global__ void __launch_bounds__(256) stft_pad_kernel(const float* __restrict__ wav, long long wav_bs, const int32_t* __restrict__ n_valid,
@@ -72,11 +79,11 @@ __global__ void __launch_bounds__(256) spectral_subtract_kernel(float* __restric
   __syncthreads();
   for (int k = threadIdx.x; k < bins; k += blockDim.x) {
     const float re = row[k], im = row[bins + k];
-    const float mag = __fsqrt_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));
-    const float md = fmaxf(__fsub_rn(mag, __fmul_rn(bias[k], strength)), 0.f);
+    const float mag = magnitude(re, im);
+    const float md = fmaxf(__fsub_rn(mag, mul_rn(bias[k], strength)), 0.f);
     const float sc = mag > 0.f ? __fdiv_rn(md, mag) : 0.f;   // mag_d * cos / sin(atan2(im, re)) = (re, im) * mag_d / mag
-    row[k] = __fmul_rn(re, sc);
-    row[bins + k] = __fmul_rn(im, sc);
+    row[k] = mul_rn(re, sc);
+    row[bins + k] = mul_rn(im, sc);
   }
   for (int k = 2 * bins + threadIdx.x; k < Cpad; k += blockDim.x) row[k] = 0.f;
   __syncthreads();
@@ -88,7 +95,7 @@ __global__ void bias_frame_kernel(const float* __restrict__ spec, float* __restr
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= bins) return;
   const float re = spec[k], im = spec[bins + k];
-  bias[k] = __fsqrt_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)));
+  bias[k] = magnitude(re, im);
 }
 
 __device__ __forceinline__ int16_t pcm_sat(float v) {
@@ -123,7 +130,7 @@ __global__ void __launch_bounds__(256) ola_norm_kernel(const float* __restrict__
         float env = 0.f;
         for (long long f = f_lo; f <= f_hi; ++f) env = (float)((double)env + win_sq[p - f * hop]);
         if (env > FLT_MIN) v = __fdiv_rn(v, env);
-        v = __fmul_rn(v, scale);
+        v = mul_rn(v, scale);
       }
     }
     t[k] = v;
@@ -212,7 +219,7 @@ __global__ void __launch_bounds__(256) ola_norm_stream_kernel(const float* __res
         float env = 0.f;
         for (long long f = f_lo; f <= f_hi; ++f) env = (float)((double)env + win_sq[p - f * hop]);
         if (env > FLT_MIN) v = __fdiv_rn(v, env);
-        v = __fmul_rn(v, scale);
+        v = mul_rn(v, scale);
       }
     }
     t[k] = v;
@@ -267,6 +274,8 @@ const char* launch_spectral_subtract(float* spec, const float* bias, const int32
   const int bins = filter_length / 2 + 1;
   if (B <= 0 || B > 65535 || R <= 0 || filter_length <= 0 || filter_length % 2 || Cpad % 4 || Cpad < 2 * bins || Cpad > 16384)
     return "spectral_subtract: bad dims";
+  // (rows frames[b] .. frames[b] + n_overlap - 2 are zeroed: a stray n_overlap would wipe rows the caller owns or leave the inverse's unzeroed)
+  if (n_overlap != 2 && n_overlap != 4 && n_overlap != 8) return "spectral_subtract: n_overlap must be 2, 4 or 8";
   if ((uintptr_t)spec & 15) return "spectral_subtract: spec must be 16-byte aligned";
   hipLaunchKernelGGL(spectral_subtract_kernel, dim3(R, B), dim3(256), (size_t)Cpad * sizeof(float), s, spec, bias, frames, R, Cpad, bins, n_overlap,
                      strength);
@@ -323,6 +332,7 @@ const char* launch_ola_norm_stream(const float* y, long long y_bs, long long y_o
   if (const char* m = denoiser_geometry_check(filter_length, hop, nullptr)) return m;
   if (B <= 0 || B > 65535 || n <= 0 || in_bs < n || p_abs0 < 0 || F_abs <= 0) return "ola_norm_stream: bad dims";
   if (!pass && (y_off < 0 || y_off + n > y_bs)) return "ola_norm_stream: emitted range outside the overlap-add";
+  if (p_abs0 > LLONG_MAX - n) return "ola_norm_stream: absolute position overflows";
   const bool vec_out = (n % 4 == 0) && (!wav || ((uintptr_t)wav & 15) == 0) && (!pcm || ((uintptr_t)pcm & 7) == 0);
   const long long total4 = (n + 3) / 4;
   if ((total4 + 255) / 256 >= (1LL << 31)) return "ola_norm_stream: grid too large";

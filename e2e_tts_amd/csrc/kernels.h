@@ -418,6 +418,11 @@ const char* launch_wsola(const int16_t* x, long long n_in, int16_t* out, long lo
 
 // ---- denoiser.hip: the passes around the two exact-fp32 convolutions of the vocoder-bias denoiser (reference V/denoiser.py:55-186).
 // Geometry served: filter_length = hop * n_overlap, n_overlap in {2, 4, 8}, hop % 32 == 0, hop <= 1024; nullptr when it is.
+// Arithmetic contract of every pass below: each written step is ONE correctly rounded float32 operation (products through mul_rn, the root
+// correctly rounded), so a numpy float32 restatement with one rounding per operation reproduces every output bit:
+//   mag = sqrt(fl(fl(re * re) + fl(im * im)));  md = max(fl(mag - fl(bias * strength)), 0);  sc = mag > 0 ? fl(md / mag) : 0;
+//   out = fl(re * sc), fl(im * sc);  v = env > FLT_MIN ? fl(v / env) : v, then fl(v * fl(filter_length / hop));
+//   pcm = (int16) min(max(trunc(fl(v * 32768)), -32768), 32767) -- fmaxf returns its other operand for a NaN, so a NaN sample becomes -32768.
 const char* denoiser_geometry_check(int filter_length, int hop, int* n_overlap_out);
 // out [B, R, hop]: per utterance filter_length / 2 reflected samples, its n_valid[b] samples, filter_length / 2 samples reflected at ITS OWN
 // end (F.pad(mode = 'reflect'): the edge sample is not repeated), then zeros.  wav [B] rows of stride wav_bs; needs
@@ -427,6 +432,7 @@ const char* launch_stft_pad(const float* wav, long long wav_bs, const int32_t* n
 // In place on spec [B, R, Cpad] (re[0 .. bins) | im[0 .. bins) | padding, bins = filter_length / 2 + 1), rows f < frames[b]:
 // mag = sqrt(re^2 + im^2), md = max(mag - strength * bias[k], 0), (re, im) *= md / mag (0 where mag == 0); padding channels -> 0.
 // Rows frames[b] <= f < frames[b] + n_overlap - 1 -> 0 (what the inverse convolution reads past the last frame); later rows untouched.
+// n_overlap must be 2, 4 or 8 (the geometry served); Cpad % 4 == 0, 2 * bins <= Cpad <= 16384 (the row is held in Cpad * 4 bytes of dynamic LDS).
 const char* launch_spectral_subtract(float* spec, const float* bias, const int32_t* frames, int B, int R, int Cpad, int filter_length, int n_overlap,
                                      float strength, hipStream_t s);
 // bias[k] = sqrt(re^2 + im^2) of one spectrum row, k < filter_length / 2 + 1
@@ -435,7 +441,8 @@ const char* launch_bias_frame(const float* spec_row, float* bias, int filter_len
 // divided by the window sum-square envelope of frames[b] frames where that exceeds FLT_MIN (win_sq: the squared, centre-padded window
 // [filter_length] in float64, summed into a float32 accumulator frame by frame as librosa's window_sumsquare does), times filter_length / hop.
 // Rows with n_valid[b] <= filter_length / 2 copy in[b, i] (row stride in_bs).  Samples i >= n_valid[b] are 0.  wav [B, n] fp32 and / or
-// pcm [B, n] int16 = trunc(v * 32768) SATURATED to [-32768, 32767].
+// pcm [B, n] int16 = trunc(v * 32768) SATURATED to [-32768, 32767] (NaN -> -32768).  `in` is always required: which rows pass through is
+// decided on the device, from n_valid.
 const char* launch_ola_norm(const float* y, const float* in, long long in_bs, const int32_t* n_valid, const int32_t* frames, const double* win_sq,
                             float* wav, int16_t* pcm, int B, long long n, int R, int filter_length, int hop, hipStream_t s);
 
@@ -448,6 +455,7 @@ const char* launch_fill_i32(int32_t* p, int n, int32_t v, hipStream_t s);
 // n emitted samples per row into wav / pcm [B, n]: sample k is y[b, y_off + k] (rows of stride y_bs), at absolute padded position p_abs0 + k,
 // normalised as launch_ola_norm does with the envelope of the absolute frames 0 .. F_abs - 1 (F_abs = LLONG_MAX: end not known yet).
 // pass: copies in[b, k] (row stride in_bs) instead -- a whole signal of at most filter_length / 2 samples.
+// p_abs0 + n must not overflow a long long; positions are 64-bit throughout (a stream may run past 2^31 samples).
 const char* launch_ola_norm_stream(const float* y, long long y_bs, long long y_off, const float* in, long long in_bs, const double* win_sq, float* wav,
                                    int16_t* pcm, int B, long long n, long long p_abs0, long long F_abs, int filter_length, int hop, bool pass,
                                    hipStream_t s);

@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(TAIL_THREADS) mel_tail_kernel(const float* __r
     for (int k = lane; k < bins; k += 64) {
       const float re = row[k], im = row[bins + k];
       // sqrt((re^2 + im^2) + 1e-9), every product and sum rounded on its own as torch's pow(2).sum(-1) + 1e-9 rounds them
-      const float mg = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(re, re), __fmul_rn(im, im)), 1e-9f));
+      const float mg = sqrtf(__fadd_rn(__fadd_rn(mul_rn(re, re), mul_rn(im, im)), 1e-9f));
       mel_smag[f * bins + k] = mg;
       e = fmaf(mg, mg, e);
     }

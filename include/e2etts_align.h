@@ -117,6 +117,11 @@ E2EALIGN_API int e2ealign_profile_read(e2ealign_handle* handle, double ms_out[3]
 /* Test build only (libe2etts_align_test.so; the product library does not export it): fills every workspace of the handle (the resident
  * maps included, the weights not) with NaN bit patterns. */
 E2EALIGN_API int e2ealign_debug_poison_workspace(e2ealign_handle* handle);
+/* Test build only: the attention pass of e2ealign_forward ALONE, on projections given by the caller instead of computed from weights (none
+ * need be loaded): q [B, T, n_att], k [B, L, n_att] fp32, prior [B, T, L] | NULL, txt_lens [B] int64 | NULL, host or device memory.  Same
+ * validation of B, T, L and txt_lens as e2ealign_forward, same choice of the frame tile (one function launches both), same outputs. */
+E2EALIGN_API int e2ealign_debug_attention(e2ealign_handle* handle, const float* q, const float* k, const float* prior, const int64_t* txt_lens,
+                                          int B, int T, int L, float* attn_out, float* attn_logprob_out);
 #endif
 
 #ifdef __cplusplus

@@ -161,3 +161,143 @@ def valid_stats(x, ref, txt_lens, mel_lens, full_columns=False):
         d.append(np.abs(x[b, :int(mel_lens[b]), :n].astype(np.float64) - ref[b, :int(mel_lens[b]), :n].astype(np.float64)).ravel())
     d = np.concatenate(d)
     return float(d.mean()), float(d.max())
+
+
+# ---------------------------------------------------------------- the attention pass alone (aln_attn_kernel through e2ealign_debug_attention)
+U = 2.0 ** -24               # unit roundoff of float32
+K_ULP = 4                    # assumed maximum ulp error of expf / logf on the device (tests/small_ref.py's K; assumed, not measured)
+EPS_PRIOR = np.float32(1e-8)
+SECOND_ORDER = 1.001         # the bars below are first-order in U; every relative error involved is below 1e-4, so 1 + 1e-3 covers the rest
+ATTN_LDS_MAX = 64 * 1024
+
+
+def attn_lds_bytes(TI, L, C):
+    """aligner.hip: the LDS tile of the attention pass with TI frames per workgroup."""
+    return (TI * C + 64 * (C | 1) + TI * L) * 4
+
+
+def attn_frames_per_workgroup(L, C):
+    """16 (four frames per wave) while that tile fits the LDS limit, else 4; None where not even 4 fit (refused)."""
+    return 16 if attn_lds_bytes(16, L, C) <= ATTN_LDS_MAX else 4 if attn_lds_bytes(4, L, C) <= ATTN_LDS_MAX else None
+
+
+def _lens_or_full(txt_lens, B, L):
+    return np.full(B, L, np.int64) if txt_lens is None else np.asarray(txt_lens, np.int64)
+
+
+def attention64(q, k, temperature, txt_lens=None, prior=None):
+    """The attention pass in float64 on float32 inputs: q [B, T, C], k [B, L, C] -> (attn, attn_logprob, bar_attn, bar_logprob), all [B, T, L].
+
+    The bars bound |float32 kernel - this| per element to first order in U = 2^-24, from the operations on the element's path:
+      score    s = -temperature * sum_c (q - k)^2: one subtraction (relative U on the difference, 2 U on its square), a chain of ceil(C / 4)
+               fused accumulations, two additions joining the four chains, one product; every term is >= 0, so the relative errors add:
+               |ds| <= (ceil(C / 4) + 5) U |s|.  Without a prior attn_logprob = s.
+      prior    x = s - m (U |x|; m is ANY common shift: log-softmax does not depend on it), ls = logf(sum expf(x)): the terms carry
+               ds + U |x| + 2 K U (K ulp = K 2^-23 relative), weighted in the sum by their softmax weights w; the sum itself ceil(L / 64) + 6
+               additions of positive terms (per-lane strided partial sums, then a 6-stage butterfly); logf adds 2 K U |ls|.  Then
+               (x - ls) [U |x - ls|], logf(prior + 1e-8f) [the addition: U relative on the argument = U absolute on the logarithm; logf:
+               2 K U |log|], and the last addition [U |attn_logprob|].
+      softmax  over the valid keys, on the attn_logprob values v (error bl): y = v - m2 (U |y|), expf (2 K U), the sum (ceil(len / 64) + 6) U
+               + the weighted errors of its terms, one division (U): relative to attn.  Masked keys are exactly 0 (bar 0).
+    K = 4 is small_ref.py's allowance: assumed, not measured.  The whole bar is multiplied by SECOND_ORDER; 2^-149 is added to attn's for
+    a result in the subnormals."""
+    q64, k64 = np.asarray(q, np.float32).astype(np.float64), np.asarray(k, np.float32).astype(np.float64)
+    B, T, C = q64.shape
+    L = k64.shape[1]
+    t = np.float64(np.float32(temperature))
+    d = ((q64[:, :, None, :] - k64[:, None, :, :]) ** 2).sum(-1)
+    s = -t * d
+    bs = (-(-C // 4) + 5) * U * np.abs(s)
+    if prior is None:
+        logp, bl = s, bs
+    else:
+        m = s.max(-1, keepdims=True)
+        x = s - m
+        e = np.exp(x)
+        w = e / e.sum(-1, keepdims=True)
+        ls = np.log(e.sum(-1, keepdims=True))
+        lp = np.log(np.asarray(prior, np.float32).astype(np.float64) + np.float64(EPS_PRIOR))
+        logp = (x - ls) + lp
+        e_ls = (w * (bs + U * np.abs(x) + 2 * K_ULP * U)).sum(-1, keepdims=True) + (-(-L // 64) + 6) * U + 2 * K_ULP * U * np.abs(ls)
+        bl = bs + U * np.abs(x) + e_ls + U * np.abs(x - ls) + U + 2 * K_ULP * U * np.abs(lp) + U * np.abs(logp)
+    lens = _lens_or_full(txt_lens, B, L)
+    attn, ba = np.zeros_like(logp), np.zeros_like(logp)
+    for b in range(B):
+        n = int(lens[b])
+        v = logp[b, :, :n]
+        y = v - v.max(-1, keepdims=True)
+        e = np.exp(y)
+        a = e / e.sum(-1, keepdims=True)
+        term = bl[b, :, :n] + U * np.abs(y) + 2 * K_ULP * U
+        rel = term + (a * term).sum(-1, keepdims=True) + (-(-n // 64) + 6) * U + U
+        attn[b, :, :n] = a
+        ba[b, :, :n] = rel * a * SECOND_ORDER + 2.0 ** -149
+    return attn, logp, ba, bl * SECOND_ORDER
+
+
+def _wave_reduce(per_lane, op):
+    """The 6-stage xor butterfly over 64 lanes ([..., 64] float32): every lane ends with the same value."""
+    v = per_lane
+    idx = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = op(v, v[..., idx ^ o])
+    return v[..., 0]
+
+
+def _lane_partials(x, fill, op):
+    """[..., n] float32 -> [..., 64]: lane l folds columns l, l + 64, ... in ascending order, starting from `fill`."""
+    n = x.shape[-1]
+    acc = np.full(x.shape[:-1] + (64,), fill, np.float32)
+    for j0 in range(0, n, 64):
+        blk = x[..., j0:j0 + 64]
+        acc[..., :blk.shape[-1]] = op(acc[..., :blk.shape[-1]], blk)
+    return acc
+
+
+def attention32_kernel_order(q, k, temperature, txt_lens=None, prior=None, mut=None):
+    """The attention pass in float32 in aln_attn_kernel's order: channel c goes to chain c mod 4 by one fused multiply-add (the product
+    exact in float64, the sum rounded to float64 and then to float32: a double rounding, which can differ from the device's single one in
+    rare last bits), chains joined (0 + 1) + (2 + 3), times -temperature; per row 64-lane strided partial maxima and sums, then the xor
+    butterfly; numpy's float32 exp and log for expf and logf.  -> (attn, attn_logprob) float32.
+
+    mut: one of the mutations the tests must catch -- "tail" (the last of the C mod 4 channels dropped), "stale" (a partial key tile keeps
+    the previous tile's keys), "prior_len" (the prior's log-softmax over len instead of L), "softmax_L" (the masked softmax over L),
+    "mask+1" (one masked key let in), "no_eps" (log(prior) without + 1e-8), "skip_last" (frame T - 1 of a partial frame tile not written)."""
+    f32 = np.float32
+    q, k = np.asarray(q, f32), np.asarray(k, f32)
+    B, T, C = q.shape
+    L = k.shape[1]
+    if mut == "stale" and L % 64:
+        k = k.copy()
+        j0 = L // 64 * 64
+        if j0:
+            k[:, j0:] = k[:, j0 - 64:L - 64]
+    acc = np.zeros((4, B, T, L), f32)
+    for c in range(C - 1 if (mut == "tail" and C % 4) else C):
+        dd = (q[:, :, None, c] - k[:, None, :, c]).astype(np.float64)
+        acc[c & 3] = (dd * dd + acc[c & 3].astype(np.float64)).astype(f32)
+    row = f32(-f32(temperature)) * ((acc[0] + acc[1]) + (acc[2] + acc[3]))
+    lens = _lens_or_full(txt_lens, B, L)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if prior is not None:
+            pr = np.asarray(prior, f32)
+            out = np.empty_like(row)
+            for b in range(B):
+                n = int(lens[b]) if mut == "prior_len" else L
+                r = row[b]
+                m = _wave_reduce(_lane_partials(r[:, :n], -np.inf, np.maximum), np.maximum)[:, None]
+                ssum = _wave_reduce(_lane_partials(np.exp(r[:, :n] - m), 0.0, np.add), np.add)[:, None]
+                out[b] = ((r - m) - np.log(ssum)) + np.log(pr[b] if mut == "no_eps" else pr[b] + EPS_PRIOR)
+            row = out
+        attn = np.zeros_like(row)
+        for b in range(B):
+            n = L if mut == "softmax_L" else min(L, int(lens[b]) + 1) if mut == "mask+1" else int(lens[b])
+            v = row[b, :, :n]
+            m2 = _wave_reduce(_lane_partials(v, -np.inf, np.maximum), np.maximum)[:, None]
+            e = np.exp(v - m2)
+            s2 = _wave_reduce(_lane_partials(e, 0.0, np.add), np.add)[:, None]
+            attn[b, :, :n] = e / s2
+    logp = row.copy()
+    if mut == "skip_last" and T % 16:
+        attn[:, T - 1], logp[:, T - 1] = np.nan, np.nan        # whatever the buffer held: the tests pre-fill with NaN
+    return attn, logp
