@@ -405,6 +405,9 @@ const char* launch_rel_attention(const float* qkv, const float* pos, int pos_row
 // v [B, N, >= H] with row stride v_ld (batch stride N * v_ld); wl the logit weights TRANSPOSED, [H][H / hs]; bl [H / hs]; out [B, H].
 // hs in {1, 2, 4, 8}, H <= 1024, H / hs <= 512.  ws: ff_pool_workspace_bytes() of scratch for the partial (max, sum, weighted sum) triples
 // of the ff_pool_splits() row runs per utterance, merged in run order (no atomics: bit-identical from run to run).
+// Workspace layout after a launch (the per-kernel tests read it): float [B][splits][H / hs][hs + 2], per (b, run, head) the run's largest
+// logit, the sum of exp(s - max) over the run's rows, then the hs sums of exp(s - max) * v'.  Runs are consecutive rows, all of one length
+// (a multiple of 16) but the last.
 const char* launch_ff_pool(const float* v, int v_ld, const float* scale, const float* wl, const float* bl, const int32_t* lens, float* out, float* ws,
                            size_t ws_bytes, int B, int N, int H, int head_size, hipStream_t s);
 size_t ff_pool_workspace_bytes(int B, int N, int H, int head_size);

@@ -209,6 +209,17 @@ int tile_frames(int bins) {
   return ft;
 }
 
+// the tail over the spectrum in h->spec ([B, T + n_overlap - 1, cpad]) into h->mel / h->energy, frames [B] on the device: the one place
+// mel_tail_kernel is launched from (e2emel_forward, and e2emel_debug_tail of the test build)
+int launch_tail(e2emel_handle* h, const int32_t* d_frames, int B, int T) {
+  const int FT = h->tile, R = T + h->nov - 1;
+  hipLaunchKernelGGL(mel_tail_kernel, dim3((T + FT - 1) / FT, B), dim3(TAIL_THREADS), (size_t)FT * h->bins * 4, h->stream, (const float*)h->spec.p,
+                     (const float*)h->basis.p, (const int2*)h->band.p, d_frames, (float*)h->mel.p, (float*)h->energy.p, T, R, h->cpad, h->bins,
+                     h->n_mel, FT, h->clip, h->log_clip);
+  HIPCHK(h, hipGetLastError());
+  return E2EMEL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,13 +389,7 @@ int e2emel_forward(e2emel_handle* h, const void* audio, int dtype, long long aud
     KCHK(h, launch_conv_gemm(p, s));
   }
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[2], s));
-  {
-    const int FT = h->tile;
-    hipLaunchKernelGGL(mel_tail_kernel, dim3((T + FT - 1) / FT, B), dim3(TAIL_THREADS), (size_t)FT * h->bins * 4, s, (const float*)h->spec.p,
-                       (const float*)h->basis.p, (const int2*)h->band.p, d_frames, (float*)h->mel.p, (float*)h->energy.p, T, R, h->cpad, h->bins, M, FT,
-                       h->clip, h->log_clip);
-    HIPCHK(h, hipGetLastError());
-  }
+  RET(launch_tail(h, d_frames, B, T));
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[3], s));
   RET(copy_out(h, mel_out, h->mel.p, (size_t)B * T * M * 4));
   RET(copy_out(h, energy_out, h->energy.p, (size_t)B * T * 4));
@@ -438,6 +443,35 @@ int e2emel_debug_force_dense(e2emel_handle* h, int on) {
     }
   HIPCHK(h, hipStreamSynchronize(h->stream));
   HIPCHK(h, hipMemcpy(h->band.p, band.data(), band.size() * 4, hipMemcpyHostToDevice));
+  return E2EMEL_OK;
+}
+
+int e2emel_debug_tail(e2emel_handle* h, const float* spec, const int32_t* frames, int B, int T, float* mel_out, float* energy_out) {
+  if (!h) return E2EMEL_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (!spec || !frames) return h->fail(E2EMEL_EINVAL, "spec and frames must not be NULL");
+  if (B < 1 || B > E2EMEL_MAX_B || T < 1 || T > (1 << 20)) return h->fail(E2EMEL_EINVAL, "e2emel_debug_tail: B or T out of range");
+  std::vector<int32_t> fr;
+  RET(fetch_host(h, frames, (size_t)B, fr));
+  for (int b = 0; b < B; ++b)
+    if (fr[b] < 0 || fr[b] > T) return h->fail(E2EMEL_EINVAL, "e2emel_debug_tail: frames[b] must lie in [0, T]");
+  if (!h->loaded) return h->fail(E2EMEL_ESTATE, "e2emel_debug_tail before e2emel_load");
+  RET(begin_call(h));
+  h->rB = 0;
+  const size_t R = (size_t)T + h->nov - 1, M = h->n_mel;
+  h->host_lens = fr;   // outlives the asynchronous copy
+  RET(reserve(h, h->lens, (size_t)B * 4));
+  RET(reserve(h, h->spec, (size_t)B * R * h->cpad * 4));
+  RET(reserve(h, h->mel, (size_t)B * T * M * 4));
+  RET(reserve(h, h->energy, (size_t)B * T * 4));
+  HIPCHK(h, hipMemcpyAsync(h->lens.p, h->host_lens.data(), (size_t)B * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->spec.p, spec, (size_t)B * R * h->cpad * 4, hipMemcpyDefault, h->stream));
+  RET(launch_tail(h, (const int32_t*)h->lens.p, B, T));
+  RET(copy_out(h, mel_out, h->mel.p, (size_t)B * T * M * 4));
+  RET(copy_out(h, energy_out, h->energy.p, (size_t)B * T * 4));
+  HIPCHK(h, hipStreamSynchronize(h->stream));
+  h->unfinished = false;
+  h->rB = B;
   return E2EMEL_OK;
 }
 #endif

@@ -17,7 +17,7 @@ from ._lib import _addr, _expect
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_mel.so")
-# the TEST build of the same source (-DE2EMEL_TEST_HOOKS: two more exports, e2emel_debug_poison_workspace and e2emel_debug_force_dense), loaded instead of the product
+# the TEST build of the same source (-DE2EMEL_TEST_HOOKS: three more exports, e2emel_debug_poison_workspace, e2emel_debug_force_dense and e2emel_debug_tail), loaded instead of the product
 # library only when E2ETTS_TEST_HOOKS=1 is in the environment (_companion.load)
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_mel_test.so")
 ABI_VERSION = 1   # E2EMEL_ABI_VERSION of the include/e2etts_mel.h this binding mirrors
@@ -45,7 +45,8 @@ SIGNATURES = {
     "e2emel_profile_enable": (_I, [_P, _I]),
     "e2emel_profile_read": (_I, [_P, C.POINTER(C.c_double)]),
 }
-HOOK_SIGNATURES = {"e2emel_debug_poison_workspace": (_I, [_P]), "e2emel_debug_force_dense": (_I, [_P, _I])}
+HOOK_SIGNATURES = {"e2emel_debug_poison_workspace": (_I, [_P]), "e2emel_debug_force_dense": (_I, [_P, _I]),
+                   "e2emel_debug_tail": (_I, [_P, _P, _P, _I, _I, _P, _P])}
 EXPORTED_SYMBOLS = list(SIGNATURES)
 TEST_HOOK_SYMBOLS = list(HOOK_SIGNATURES)
 
@@ -244,3 +245,17 @@ class MelFrontend(_companion.CompanionHandle):
     def force_dense(self, on: bool = True):
         """Test build only (E2ETTS_TEST_HOOKS=1): walk all bins of every mel row instead of the recorded bands."""
         self._hook("force_dense", 1 if on else 0)
+
+    def debug_tail(self, spec, frames):
+        """Test build only (E2ETTS_TEST_HOOKS=1): the tail kernel alone on the caller's spectrum.  spec [B, T + n_overlap - 1, Cpad] float32
+        (numpy; re | im | padding per row, Cpad = 2 * bins rounded up to a multiple of 32), frames [B] -> (mel [B, T, n_mel], energy [B, T])."""
+        spec = np.ascontiguousarray(spec, dtype=np.float32)
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        nov, cpad = self.n_fft // self.hop, (2 * self.bins + 31) // 32 * 32
+        B, T = spec.shape[0], spec.shape[1] - nov + 1
+        if spec.ndim != 3 or spec.shape[2] != cpad or T < 1 or fr.shape != (B,):
+            raise ValueError(f"spec of shape {spec.shape} / {fr.size} frame counts: expected [B, T + {nov - 1}, {cpad}] and [B]")
+        mel, energy = np.empty((B, T, self.n_mel), np.float32), np.empty((B, T), np.float32)
+        self._hook("tail", spec.ctypes.data, fr.ctypes.data, B, T, mel.ctypes.data, energy.ctypes.data)
+        self._resident = (B, T)
+        return mel, energy

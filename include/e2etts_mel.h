@@ -128,6 +128,12 @@ E2EMEL_API int e2emel_debug_poison_workspace(e2emel_handle* handle);
 /* Test build only: on != 0 replaces the band table recorded by the last e2emel_load with the degenerate band [0, bins - 1] of every row
  * (the tail kernel then walks all bins, explicit zeros included, as it does for a dense matrix); 0 puts the recorded bands back. */
 E2EMEL_API int e2emel_debug_force_dense(e2emel_handle* handle, int on);
+/* Test build only: the tail kernel alone.  The caller's spectrum spec [B, T + n_overlap - 1, Cpad] fp32 (host or device; row f of an
+ * utterance holds re[0 .. bins) | im[0 .. bins) of frame f, Cpad = 2 * bins rounded up to a multiple of 32; the last n_overlap - 1 rows
+ * are never read) goes straight into mel_tail_kernel, through the function e2emel_forward launches it through, with frames [B] int32
+ * (host or device, 0 <= frames[b] <= T) as the rows' frame counts.  mel_out [B, T, n_mel] and energy_out [B, T] as e2emel_forward writes
+ * them.  The transform's basis is not used: the handle may have been loaded with any dft_basis. */
+E2EMEL_API int e2emel_debug_tail(e2emel_handle* handle, const float* spec, const int32_t* frames, int B, int T, float* mel_out, float* energy_out);
 #endif
 
 #ifdef __cplusplus
