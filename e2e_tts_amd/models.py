@@ -236,7 +236,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
                                           au["signal"]["sampling_rate"], au["mel"]["mel_fmin"], au["mel"]["mel_fmax"], device=self._device)
         return stft
 
-    def align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior=None, return_energy=False, stft=None, wav_rate=None):
+    def align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior=None, return_energy=False, stft=None, wav_rate=None, condition=None):
         """Forced alignment of RECORDINGS: wavs [B, n] (float32 in [-1, 1] or int16 PCM; numpy or torch, host or GPU), wav_lens [B] samples
         -> ``align``'s tuple (attn_soft, attn_hard, attn_hard_dur, attn_logprob), plus the frame energies [B, T] when ``return_energy``.
         The mel is computed on the device by the mel library, every row over its own length (mel_lens = wav_lens // hop, as
@@ -247,11 +247,64 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         guessing a transform.  ``wav_rate``: the sampling rate of ``wavs`` when it is not the transform's (studio recordings are usually 44.1
         or 48 kHz): the recordings are converted to the transform's rate on the device (e2e_tts_amd.resample, default filter), the mel
         library reads the result where it lies, and mel_lens follow from the converted lengths ceil(wav_lens * L / M).  None: the
-        recordings are taken to be at the transform's rate, as before."""
-        out, energy, _ = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate)
+        recordings are taken to be at the transform's rate, as before.  ``condition``: ``dict(trim=None | "reference" | "both",
+        loudness_dBFS=None | dB, channels=1 | 2)`` prepares the recordings first as the reference's normalize_signal does
+        (e2e_tts_amd.condition; unpinned against pydub, see there), on the device and in its order: downmix ([B, n, 2] or [B, 2 n]
+        interleaved frames, wav_lens in frames), rate, silence trim, loudness; wav_lens and mel_lens then follow from the kept samples.
+        Conditioning works on int16 PCM: with ``wav_rate`` it takes the resampler's int16 output, float32 ``wavs`` at the transform's own
+        rate raise ValueError.  None: today's path, bit for bit."""
+        out, energy, _ = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition)
         return out + (energy,) if return_energy else out
 
-    def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate):
+    def _conditioned(self, wavs, wl, stft, wav_rate, condition):
+        """``align_audio``'s recordings through downmix, rate, trim and loudness -> (int16 rows in the conditioner's HBM, their lengths,
+        the stream the mel library has to wait for)."""
+        from .condition import Conditioner, loudness_gain
+        cond = dict(condition)
+        trim, loud, channels = cond.pop("trim", None), cond.pop("loudness_dBFS", None), int(cond.pop("channels", 1))
+        if cond:
+            raise ValueError(f"condition: unknown keys {sorted(cond)} (trim, loudness_dBFS, channels)")
+        if channels not in (1, 2):
+            raise ValueError(f"condition: channels must be 1 or 2 (got {channels})")
+        rate = int(stft.sampling_rate)
+        resampling = wav_rate is not None and int(wav_rate) != rate
+        cache = self.__dict__.setdefault("_conditioners", {})
+        if (rate, self._device) not in cache:
+            cache[(rate, self._device)] = Conditioner(rate, device=self._device)
+        c = cache[(rate, self._device)]
+        after = None
+        if channels == 2:
+            if not isinstance(wavs, np.ndarray) and not hasattr(wavs, "data_ptr"):
+                wavs = np.asarray(wavs)
+            if "int16" not in str(wavs.dtype):
+                raise ValueError("condition: the downmix works on int16 PCM")
+            c.downmix(wavs, fetch=False)
+            x, after = c.resident_mono(), c.hip_stream()
+        else:
+            x = stft._audio(wavs)
+        if resampling:
+            from .resample import Resampler
+            rcache = self.__dict__.setdefault("_resamplers", {})
+            key = (int(wav_rate), rate, self._device)
+            if key not in rcache:
+                rcache[key] = Resampler(key[0], key[1], device=self._device)
+            rsm = rcache[key]
+            if after:
+                rsm.order_after_stream(after)
+            wl = rsm.forward(x, n_valid=wl, want=())["n_out"]
+            x, after = rsm.resident()[1], rsm.hip_stream()          # the int16 output
+        elif "int16" not in str(x.dtype):
+            raise ValueError("condition: conditioning works on int16 PCM; float32 recordings are taken only with wav_rate (the resampler's int16 output)")
+        if after:
+            c.order_after_stream(after)
+        a = c.analyze(x, wl, trim)
+        gain = np.ones(len(wl), np.float64)
+        if loud is not None:
+            gain = np.array([loudness_gain(int(s), int(n), loud) for s, n in zip(a["sumsq"], a["n_out"])], np.float64)
+        c.apply(gain, want=("pcm",), fetch=False)
+        return c.resident()[0], a["n_out"].astype(np.int64), c.hip_stream()
+
+    def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition=None):
         """``align_audio``'s work -> (its 4-tuple, the frame energies or None, the mel front-end's mel_lens [B] int64 on the host)."""
         from . import aligner as al
         torch = _torch()
@@ -270,8 +323,13 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         keys = emb[ids].contiguous()
         spk = spk_table[sp].contiguous()
         fe = stft.frontend
-        x = stft._audio(wavs)
         wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
+        if condition is not None:
+            x, wl, after = self._conditioned(wavs, wl, stft, wav_rate, condition)
+            fe._call("order_after", after)                          # the mel's stream after the conditioner's
+            wav_rate = None
+        else:
+            x = stft._audio(wavs)
         if wav_rate is not None and int(wav_rate) != int(stft.sampling_rate):
             from .resample import Resampler
             cache = self.__dict__.setdefault("_resamplers", {})
@@ -394,12 +452,13 @@ class UnsupervisedFastSpeech2(_EngineBacked):
 
     __call__ = forward
 
-    def forward_audio(self, speaker, texts, txt_lens, wavs, wav_lens, p_targets=None, e_targets=None, step=0, wav_rate=None):
+    def forward_audio(self, speaker, texts, txt_lens, wavs, wav_lens, p_targets=None, e_targets=None, step=0, wav_rate=None, condition=None):
         """``align_audio`` followed by the teacher-forced pass: recordings -> ground-truth-aligned mels, with the mel, the soft map and the
         durations never leaving the device.  p_targets / e_targets: frame-level targets [B, T] as for ``forward`` (T = the mel frames of
-        the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``: as for ``align_audio``.
+        the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``, ``condition``: as for ``align_audio`` (with
+        ``condition`` T follows from the kept samples).
         -> ``forward``'s two tuples."""
-        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate)
+        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate, condition)
         self._check_lengths(txt_lens, ml)
         T = int(attn_out[0].shape[2])
         return self._forced(speaker, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, self._ensure_aligner()[0].encoder.stream())
