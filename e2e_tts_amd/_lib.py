@@ -15,7 +15,8 @@ from .config import CEngineConfig, EngineDims
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_hip.so")
-# The TEST build of the same sources (-DE2ETTS_TEST_HOOKS: one more export, e2etts_debug_poison_workspace).  Loaded instead of the product
+# The TEST build of the same sources (-DE2ETTS_TEST_HOOKS: one more export, e2etts_debug_poison_workspace, and the tuning switches of
+# csrc/tuning.hip read from the environment; the product library ignores those variables).  Loaded instead of the product
 # library only when E2ETTS_TEST_HOOKS=1 is in the environment (tests/conftest.py sets it); nothing in the product path asks for it.
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_hip_test.so")
 ABI_VERSION = 4   # E2ETTS_ABI_VERSION of the include/e2etts.h this binding mirrors

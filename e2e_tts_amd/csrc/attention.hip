@@ -13,9 +13,9 @@
 #include <math.h>
 
 #include <algorithm>
-#include <stdlib.h>
 
 #include "kernels.h"
+#include "tuning.h"
 
 namespace e2etts {
 
@@ -1431,12 +1431,11 @@ const char* launch_rel_attention(const float* qkv, const float* pos, int pos_row
   return err == hipSuccess ? nullptr : hipGetErrorString(err);
 }
 
-// largest padded grid (64-query workgroups, before the segment split) that computes its key segments in parallel; E2ETTS_ATT_PAR_MAX (tuning aid)
+// largest padded grid (64-query workgroups, before the segment split) that computes its key segments in parallel
 long long attention_par_max_grid() {
   // default: up to one round of the serial form's workgroups (2 per CU).  Same box, T = 768: B = 8 (192 workgroups) 1.12 -> 1.04 ms/step,
   // B = 32 (768) 2.41 -> 2.47: above one round the serial form already fills the chip and the workspace round trip costs more than it buys
-  static const long long v = getenv("E2ETTS_ATT_PAR_MAX") ? atoll(getenv("E2ETTS_ATT_PAR_MAX")) : 512;
-  return v;
+  return 512;
 }
 
 size_t attention_workspace_bytes(int B, int N, int H, int n_head) {
@@ -1456,8 +1455,8 @@ const char* launch_attention(const float* qkv, float* out, const int32_t* lens, 
   // The split form on 64-query workgroups (same bits, see attention_split_kernel).  fp32: at every grid size -- B = 1: 225 -> 135 us per
   // decoder layer, B = 32: 2.50 -> 2.22 ms/step.  bf16x3: up to 512 workgroups (B = 16: 0.82 -> 0.75 ms/step); beyond, the 256-query
   // workgroups of attention_x3_kernel win (B = 32: 0.95 against 1.33 ms), their K / V conversion shared by four times the queries.
-  // E2ETTS_ATT_SPLIT_MAX overrides both limits (0: never split -- what the bit-identity test runs its child process with).
-  static const long long split_env = getenv("E2ETTS_ATT_SPLIT_MAX") ? atoll(getenv("E2ETTS_ATT_SPLIT_MAX")) : -1;
+  // tuning().att_split_max overrides both limits.
+  const long long split_env = tuning().att_split_max;
   const long long split_max = split_env >= 0 ? split_env : (x3 ? 512 : (1LL << 62));
   dim3 gs((N + 63) / 64, n_head, B);
   // ragged batch, lengths known on the host: the compact 1-D grid of the query blocks that exist (kernels.h: RowMap)
@@ -1483,27 +1482,14 @@ const char* launch_attention(const float* qkv, float* out, const int32_t* lens, 
     return hipGetLastError() == hipSuccess ? nullptr : "attention: launch failed";
   }
   if (x3) {
-    static const int nw = getenv("E2ETTS_ATT_NW") ? atoi(getenv("E2ETTS_ATT_NW")) : 8;  // tuning aid
-    if (nw == 8) {
-      dim3 g8((N + 255) / 256, n_head, B);
-      const dim3 gc = shape(g8, 256);
-      switch (dk) {
-        case 32: hipLaunchKernelGGL((attention_x3_kernel<32, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-        case 64: hipLaunchKernelGGL((attention_x3_kernel<64, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-        case 96: hipLaunchKernelGGL((attention_x3_kernel<96, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-        case 128: hipLaunchKernelGGL((attention_x3_kernel<128, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-        case 192: hipLaunchKernelGGL((attention_x3_kernel<192, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-        default: return "attention: head dim must be one of 32, 64, 96, 128, 192";
-      }
-      return hipGetLastError() == hipSuccess ? nullptr : "attention: launch failed";
-    }
-    const dim3 gc = shape(grid, 128);
+    dim3 g8((N + 255) / 256, n_head, B);
+    const dim3 gc = shape(g8, 256);
     switch (dk) {
-      case 32: hipLaunchKernelGGL((attention_x3_kernel<32, 4>), gc, dim3(256), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-      case 64: hipLaunchKernelGGL((attention_x3_kernel<64, 4>), gc, dim3(256), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-      case 96: hipLaunchKernelGGL((attention_x3_kernel<96, 4>), gc, dim3(256), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-      case 128: hipLaunchKernelGGL((attention_x3_kernel<128, 4>), gc, dim3(256), 0, s, qkv, out, lens, N, H, temperature, rm); break;
-      case 192: hipLaunchKernelGGL((attention_x3_kernel<192, 4>), gc, dim3(256), 0, s, qkv, out, lens, N, H, temperature, rm); break;
+      case 32: hipLaunchKernelGGL((attention_x3_kernel<32, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
+      case 64: hipLaunchKernelGGL((attention_x3_kernel<64, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
+      case 96: hipLaunchKernelGGL((attention_x3_kernel<96, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
+      case 128: hipLaunchKernelGGL((attention_x3_kernel<128, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
+      case 192: hipLaunchKernelGGL((attention_x3_kernel<192, 8>), gc, dim3(512), 0, s, qkv, out, lens, N, H, temperature, rm); break;
       default: return "attention: head dim must be one of 32, 64, 96, 128, 192";
     }
     return hipGetLastError() == hipSuccess ? nullptr : "attention: launch failed";
@@ -1512,12 +1498,11 @@ const char* launch_attention(const float* qkv, float* out, const int32_t* lens, 
     dim3 gc = shape(gs, 64);
     // Small padded grids (the B = 1 latency path): every key segment of a query block in a workgroup of its own, merged by
     // attention_combine_kernel -- the same operations as the in-register merge, so the same bits (ATT_SEG_CHUNKS).  B = 1, T = 768: 24
-    // workgroups walking 24 chunks -> 72 walking 8, 133 -> ~55 us per decoder layer.  E2ETTS_ATT_PAR=0: never (tuning aid).
-    static const bool par_on = !(getenv("E2ETTS_ATT_PAR") && atoi(getenv("E2ETTS_ATT_PAR")) == 0);
+    // workgroups walking 24 chunks -> 72 walking 8, 133 -> ~55 us per decoder layer.  (tuning().att_par: never)
     const int nseg = ((N + 31) / 32 + ATT_SEG_CHUNKS - 1) / ATT_SEG_CHUNKS;
     int par_nseg = 0;
     float *ws_o = nullptr, *ws_ml = nullptr;
-    if (par_on && rm.n == 0 && nseg >= 2 && ws && ws_bytes >= attention_workspace_bytes(B, N, H, n_head) && (((uintptr_t)ws) & 15) == 0 &&
+    if (tuning().att_par && rm.n == 0 && nseg >= 2 && ws && ws_bytes >= attention_workspace_bytes(B, N, H, n_head) && (((uintptr_t)ws) & 15) == 0 &&
         (long long)gs.x * gs.y * gs.z <= attention_par_max_grid() && (long long)gs.x * nseg < (1LL << 31)) {
       par_nseg = nseg;
       ws_o = ws;

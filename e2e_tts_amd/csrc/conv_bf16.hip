@@ -27,12 +27,10 @@
 // (ConvTranspose1d as a 3-tap convolution whose columns < tap_split never use tap 2 and the others never tap 0: packer.polyphase_upsampler)
 // keeps only the two live taps of each tile.
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "kernels.h"
+#include "tuning.h"
 
 namespace e2etts {
 
@@ -1130,7 +1128,7 @@ __global__ void f16_image_kernel(const float* __restrict__ w, uint4* __restrict_
 }
 
 struct BcCfg {
-  int MT, NT, WGM, WGN;
+  int MT, WGM, WGN;
 };
 
 // Tile shape.  What bounds a plain-bf16 convolution on this chip is the path weight fragments take into the registers: 64 B / clk per CU
@@ -1141,11 +1139,9 @@ struct BcCfg {
 // ds_read_b128 per unit use half of) leaves headroom, MT = 2 sits on the limit, MT = 1 runs at half rate.  So: 32 columns per wavefront,
 // and as many position blocks as still leave the launch a useful number of workgroups.
 BcCfg bc_choose(const BConvParams& p) {
-  BcCfg c{1, 1, 4, 1};                                  // wavefronts stacked on the rows (Cout % 32 == 0)
-  if (p.Cout % 128 == 0) c = {1, 1, 1, 4};              // ... side by side on the columns
-  else if (p.Cout % 64 == 0) c = {1, 1, 2, 2};
-  static const int mt_env = getenv("E2ETTS_BCONV_MT") ? atoi(getenv("E2ETTS_BCONV_MT")) : 0;   // tuning aids
-  static const int nt_env = getenv("E2ETTS_BCONV_NT") ? atoi(getenv("E2ETTS_BCONV_NT")) : 0;
+  BcCfg c{1, 4, 1};                                     // wavefronts stacked on the rows (Cout % 32 == 0)
+  if (p.Cout % 128 == 0) c = {1, 1, 4};                 // ... side by side on the columns
+  else if (p.Cout % 64 == 0) c = {1, 2, 2};
   const long long rows = p.rows_hint > 0 ? p.rows_hint : (long long)p.B * p.T;
   auto wgs = [&](int mt) { return ((rows + 32 * mt * c.WGM - 1) / (32 * mt * c.WGM)) * (p.Cout / (32 * c.WGN)); };
   const int halo = p.dil * (p.KW - 1);
@@ -1153,9 +1149,6 @@ BcCfg bc_choose(const BConvParams& p) {
   c.MT = 1;
   for (int mt : {4, 2})   // the largest wavefront tile that leaves >= 48 workgroups, and two of them per CU once there is more than one per CU
     if (wgs(mt) >= 48 && lds(mt) <= (wgs(mt) <= 256 ? 160 : 80) * 1024) { c.MT = mt; break; }
-  if (mt_env > 0 && lds(mt_env) <= 160 * 1024) c.MT = mt_env;
-  // two column blocks per wavefront (MT <= 2, Cout % 256 == 0): half the workgroups stage the same slab; only on request
-  if (nt_env == 2 && c.MT <= 2 && c.WGN == 4 && p.Cout % 256 == 0 && (p.tap_split % 64) == 0) c.NT = 2;
   return c;
 }
 
@@ -1179,8 +1172,6 @@ const char* bc_launch(const BConvParams* ps, int n, hipStream_t s) {
   for (int k = n; k < BC_GROUP_MAX; ++k) g.wg_end[k] = (int)nwg;
   if (lds > 160 * 1024) return "conv_bf16: slab exceeds the CU's LDS";
   if (nwg >= (1LL << 31)) return "conv_bf16: grid too large";
-  static const long lds_min = getenv("E2ETTS_BCONV_LDS_MIN") ? atol(getenv("E2ETTS_BCONV_LDS_MIN")) : 0;   // tuning aid: occupancy experiments
-  lds = std::max(lds, (size_t)std::min(lds_min, 160L * 1024));
   static bool attr_done = false;   // > 64 KiB of dynamic LDS needs the opt-in, once per instantiation
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_bf16_kernel<MT, NT, WGM, WGN, D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1216,16 +1207,19 @@ bool conv_bf16_supported(const BConvParams& p) {
 }
 
 const char* conv_bf16_class(const BConvParams& p) {
-  const BcCfg c = bc_choose(p);
-  static char names[16][24];
-  static int next = 0;
-  char nm[24];
-  snprintf(nm, sizeof nm, "conv_bf16_%dx%d", 32 * c.MT * c.WGM, 32 * c.NT * c.WGN);
-  for (int i = 0; i < next; ++i)
-    if (!strcmp(names[i], nm)) return names[i];
-  if (next == 16) return "conv_bf16";
-  strcpy(names[next], nm);
-  return names[next++];
+  const BcCfg c = bc_choose(p);   // "conv_bf16_<rows>x<columns>" of the workgroup tile: 32 * MT * WGM x 32 * WGN
+  switch (c.WGN * 8 + c.MT) {
+    case 1 * 8 + 1: return "conv_bf16_128x32";
+    case 1 * 8 + 2: return "conv_bf16_256x32";
+    case 1 * 8 + 4: return "conv_bf16_512x32";
+    case 2 * 8 + 1: return "conv_bf16_64x64";
+    case 2 * 8 + 2: return "conv_bf16_128x64";
+    case 2 * 8 + 4: return "conv_bf16_256x64";
+    case 4 * 8 + 1: return "conv_bf16_32x128";
+    case 4 * 8 + 2: return "conv_bf16_64x128";
+    case 4 * 8 + 4: return "conv_bf16_128x128";
+  }
+  return "conv_bf16";
 }
 
 static const char* bc_check(const BConvParams& p) {
@@ -1258,19 +1252,17 @@ const char* launch_conv_bf16_group(const BConvParams* ps, int n, hipStream_t s) 
     if (ps[k].dil * (ps[k].KW - 1) > ref.dil * (ref.KW - 1)) { ref.KW = ps[k].KW; ref.dil = ps[k].dil; }
   }
   const BcCfg c = bc_choose(ref);
-#define E2ETTS_BC_CASE(mt, nt, wgm, wgn, d) \
-  if (c.MT == mt && c.NT == nt && c.WGM == wgm && c.WGN == wgn) return bc_launch<mt, nt, wgm, wgn, d>(ps, n, s);
-  E2ETTS_BC_CASE(1, 2, 1, 4, 8)
-  E2ETTS_BC_CASE(2, 2, 1, 4, 6)
-  E2ETTS_BC_CASE(1, 1, 1, 4, 8)
-  E2ETTS_BC_CASE(2, 1, 1, 4, 8)
-  E2ETTS_BC_CASE(4, 1, 1, 4, 6)
-  E2ETTS_BC_CASE(4, 1, 2, 2, 6)
-  E2ETTS_BC_CASE(4, 1, 4, 1, 6)
-  E2ETTS_BC_CASE(1, 1, 2, 2, 8)
-  E2ETTS_BC_CASE(2, 1, 2, 2, 8)
-  E2ETTS_BC_CASE(1, 1, 4, 1, 8)
-  E2ETTS_BC_CASE(2, 1, 4, 1, 8)
+#define E2ETTS_BC_CASE(mt, wgm, wgn, d) \
+  if (c.MT == mt && c.WGM == wgm && c.WGN == wgn) return bc_launch<mt, 1, wgm, wgn, d>(ps, n, s);   // (one column block per wavefront)
+  E2ETTS_BC_CASE(1, 1, 4, 8)
+  E2ETTS_BC_CASE(2, 1, 4, 8)
+  E2ETTS_BC_CASE(4, 1, 4, 6)
+  E2ETTS_BC_CASE(4, 2, 2, 6)
+  E2ETTS_BC_CASE(4, 4, 1, 6)
+  E2ETTS_BC_CASE(1, 2, 2, 8)
+  E2ETTS_BC_CASE(2, 2, 2, 8)
+  E2ETTS_BC_CASE(1, 4, 1, 8)
+  E2ETTS_BC_CASE(2, 4, 1, 8)
 #undef E2ETTS_BC_CASE
   return "conv_bf16: no instantiation for the chosen tile";
 }
@@ -1323,20 +1315,12 @@ long long pb_tiles4(const PairParams& p) {
   const int wgm = p.C >= 128 ? 1 : 4 / (p.C / 32);
   return (long long)p.B * ((p.T + 128 * wgm - p.KW) / (128 * wgm - (p.KW - 1)));
 }
-int pb_mt(long long tiles4) {
-  static const int mt_env = getenv("E2ETTS_BPAIR_MT") ? atoi(getenv("E2ETTS_BPAIR_MT")) : 0;   // tuning aid
-  if (mt_env == 2 || mt_env == 4) return mt_env;
-  return tiles4 >= 128 ? 4 : 2;
-}
 
 }  // namespace
 
 bool pair_bf16_supported(const PairParams& p) {
-  static const bool on = !(getenv("E2ETTS_BPAIR") && atoi(getenv("E2ETTS_BPAIR")) == 0);   // tuning aid: 0 keeps resblock_pair.hip
-  if (!on || (p.mode != 2 && p.mode != 3 && p.mode != 4) || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
+  if (!tuning().bpair || (p.mode != 2 && p.mode != 3 && p.mode != 4) || !p.bimg1 || !p.bimg2 || p.act_rows) return false;
   if (!(p.C == 32 || p.C == 64 || p.C == 128 || p.C == 256) || !(p.KW & 1) || p.KW < 3 || p.KW > 15 || p.dil < 1 || p.dil * (p.KW - 1) > BC_MAX_HALO) return false;
-  static const bool on256 = !(getenv("E2ETTS_BPAIR256") && atoi(getenv("E2ETTS_BPAIR256")) == 0);   // tuning aid
-  if (p.C == 256 && !on256) return false;
   if (p.x_bs != (long long)p.T * p.C || p.out_bs != (long long)p.T * p.C) return false;
   return (long long)p.T * p.C * 4 < (1LL << 31);
 }
@@ -1355,13 +1339,12 @@ const char* launch_pair_bf16_group(const PairParams* ps, int n, hipStream_t s) {
     if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C || p.mode != ps[0].mode) return "pair_bf16: the members of a group share B, T, C and the activation type";
     tiles4 += pb_tiles4(p);
   }
-  const int mt = pb_mt(tiles4);
+  const int mt = tiles4 >= 128 ? 4 : 2;
   const int C = ps[0].C;
   // 256 channels: eight wavefronts side by side on the channels, one workgroup per CU (the slab alone is 60-94 KB); 64-position blocks
   // per wavefront while the launch has fewer tiles than CUs (a 542-frame window: 226 tiles of 64 rows for the three kernel sizes together)
   // (same-box A/B at a 542-frame window, whole pass: 64-position blocks 10.64 ms, 128-position blocks 10.95, two convolution launches 10.76)
-  static const int mt256 = getenv("E2ETTS_BPAIR256_MT") ? atoi(getenv("E2ETTS_BPAIR256_MT")) : 0;   // tuning aid (0: by grid size)
-  if (C == 256) return (mt256 == 4 || (mt256 == 0 && tiles4 >= 512)) ? pb_launch<4, 1, 8, 6>(ps, n, s) : pb_launch<2, 1, 8, 8>(ps, n, s);
+  if (C == 256) return tiles4 >= 512 ? pb_launch<4, 1, 8, 6>(ps, n, s) : pb_launch<2, 1, 8, 8>(ps, n, s);
   if (C == 128) return mt == 4 ? pb_launch<4, 1, 4, 6>(ps, n, s) : pb_launch<2, 1, 4, 8>(ps, n, s);
   if (C == 64) return mt == 4 ? pb_launch<4, 2, 2, 6>(ps, n, s) : pb_launch<2, 2, 2, 8>(ps, n, s);
   return mt == 4 ? pb_launch<4, 4, 1, 6>(ps, n, s) : pb_launch<2, 4, 1, 8>(ps, n, s);
@@ -1458,8 +1441,7 @@ const char* rb_launch_stage(const RbParams* ps, int n, hipStream_t s) {
 }  // namespace
 
 bool rb_bf16_supported(const RbParams& p) {
-  static const bool on = !(getenv("E2ETTS_BRB") && atoi(getenv("E2ETTS_BRB")) == 0);   // tuning aid: 0 keeps the pair launches
-  if (!on || !(p.C == 32 || p.C == 64) || !(p.KW & 1) || p.KW < 3 || p.KW > 15 || p.n_pairs < 1 || p.n_pairs > RB_MAX_PAIRS) return false;
+  if (!tuning().brb || !(p.C == 32 || p.C == 64) || !(p.KW & 1) || p.KW < 3 || p.KW > 15 || p.n_pairs < 1 || p.n_pairs > RB_MAX_PAIRS) return false;
   int H, gx;
   rb_geometry(p, H, gx);
   for (int m = 0; m < p.n_pairs; ++m)
@@ -1490,23 +1472,13 @@ const char* launch_rb_bf16_group(const RbParams* ps, int n, hipStream_t s) {
     if (p.x == p.out) return "rb_bf16: in-place is not possible (tiles read their neighbours' rows)";
     if (p.B != ps[0].B || p.T != ps[0].T || p.C != ps[0].C || p.act16 != ps[0].act16) return "rb_bf16: the members of a group share B, T, C and the activation type";
   }
-  // 32 channels: 8 wavefronts of 64 positions each (two per SIMD: one covers the other's image writes and barriers) or 4 of 128
-  static const int w32 = getenv("E2ETTS_BRB_W32") ? atoi(getenv("E2ETTS_BRB_W32")) : 8;   // tuning aid (3: tiles of 384 positions, two workgroups per CU)
-  if (ps[0].C == 32 && w32 == 3) {
-    for (int k = 0; k < n; ++k) {
-      int H, gx;
-      rb_geometry(ps[k], H, gx);
-      if (384 - 2 * H < 192) return "rb_bf16: receptive field too wide for the 384-position tile";
-    }
-    return rb_launch<3, 4, 1, 6>(ps, n, s);
-  }
-  if (ps[0].C == 32) return w32 == 4 ? rb_launch<4, 4, 1, 4>(ps, n, s) : rb_launch<2, 8, 1, 8>(ps, n, s);
+  // 32 channels: 8 wavefronts of 64 positions each (two per SIMD: one covers the other's image writes and barriers)
+  if (ps[0].C == 32) return rb_launch<2, 8, 1, 8>(ps, n, s);
   return rb_launch<4, 4, 2, 4>(ps, n, s);
 }
 
 bool rb_bf16_stage_supported(const RbParams* ps, int n) {
-  static const bool on = !(getenv("E2ETTS_BRB_STAGE") && atoi(getenv("E2ETTS_BRB_STAGE")) == 0);   // tuning aid: 0 keeps one workgroup per ResBlock
-  if (!on || !ps || n < 1 || n > BC_GROUP_MAX || ps[0].C != 32) return false;
+  if (!ps || n < 1 || n > BC_GROUP_MAX || ps[0].C != 32) return false;
   int Hm = 0, gxm = 0, hkm = 0;
   for (int k = 0; k < n; ++k) {
     if (!rb_bf16_supported(ps[k]) || ps[k].accumulate || ps[k].x != ps[0].x || ps[k].act16 != ps[0].act16 || ps[k].B != ps[0].B || ps[k].T != ps[0].T || ps[k].C != ps[0].C ||

@@ -28,10 +28,10 @@
 // (launch_x3_to_frag / launch_f32_to_frag): no LDS weight tile, no barrier per tap.  The grid is one-dimensional and XCD-aware: the
 // column tiles of a row group run next to each other on one XCD's L2 (see the kernel's prologue).
 #include <algorithm>
-#include <cstdlib>
 
 #include "host_logic.h"
 #include "kernels.h"
+#include "tuning.h"
 
 namespace e2etts {
 
@@ -626,8 +626,7 @@ __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p,
 template <int BM, int BN, int WM, int WN, int MODE, bool ACCUM, bool VEC, bool BFRAG, int CPI = 0, int OCC = 2, bool GELU = false>
 const char* launch_cfg_impl(const ConvParams& p, hipStream_t s) {
   const int halo = p.dil * (p.KW - 1);
-  static const int lds_pad = getenv("E2ETTS_LDS_PAD") ? atoi(getenv("E2ETTS_LDS_PAD")) : 0;  // tuning aid: occupancy experiments
-  const size_t lds = (size_t)((BM + halo) * LDK * (CPI > 0 ? CPI : 1) + (BFRAG ? 0 : 2 * BN * LDK)) * sizeof(float) + (BFRAG ? lds_pad : 0);
+  const size_t lds = (size_t)((BM + halo) * LDK * (CPI > 0 ? CPI : 1) + (BFRAG ? 0 : 2 * BN * LDK)) * sizeof(float);
   if (lds > 80 * 1024) return "conv_gemm: LDS tile exceeds 80 KiB";
   if (lds > 64 * 1024) {  // the multi-chunk Linear form: opt in once per instantiation (two workgroups per CU still fit)
     static const hipError_t attr = hipFuncSetAttribute(
@@ -647,8 +646,7 @@ const char* launch_cfg_impl(const ConvParams& p, hipStream_t s) {
     for (int b = 0; b < p.B; ++b) real_tiles += (std::min(std::max(p.act_rows_host[b], 0), p.T) + BM - 1) / BM;
   const long long total = compact ? real_tiles * ntiles
                                   : (long long)((double)mtiles * ntiles * p.B * (p.act_frac > 0.0 && p.act_frac <= 1.0 ? p.act_frac : 1.0));
-  static const int wg_per_cu = getenv("E2ETTS_WG_PER_CU") ? atoi(getenv("E2ETTS_WG_PER_CU")) : 24;  // tuning aid
-  int tpb = (int)(total / (256 * wg_per_cu));
+  int tpb = (int)(total / (256 * tuning().wg_per_cu));
   tpb = tpb < 1 ? 1 : (tpb > 64 ? 64 : tpb);
   if (tpb > mtiles) tpb = mtiles;
   const int gx = (mtiles + tpb - 1) / tpb;                        // row groups per utterance (padded length)
@@ -678,24 +676,21 @@ template <int BM, int BN, int WM, int WN, int MODE>
 const char* launch_cfg(const ConvParams& p, hipStream_t s) {
   // (fp32 fragments for the 256 x 64 / 256 x 32 tiles were measured too: 0 .. -6 %, the LDS tile stays there.)  The 64 x 64 few-rows tile
   // -- small batches, the B = 1 latency path, the encoder -- is a chain of short iterations per wave, where the barrier per tap of the
-  // LDS weight tile is a large part of each link: fragments there too (E2ETTS_FRAG64=0: off, tuning aid).
-  static const bool frag64 = !(getenv("E2ETTS_FRAG64") && atoi(getenv("E2ETTS_FRAG64")) == 0);
+  // LDS weight tile is a large part of each link: fragments there too (tuning().frag64).
   if constexpr (BN == 128 || (BM == 64 && BN == 64)) {
-    if (BN == 64 && !frag64) {
+    if (BN == 64 && !tuning().frag64) {
       return p.accumulate ? launch_cfg_impl<BM, BN, WM, WN, MODE, true, true, false>(p, s)
                           : launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, false>(p, s);
     }
     // plain Linear layers (q | k | v, fc, the k = 1 FFN conv, every Conformer GEMM): several chunks per work item
-    static const int cpi_env = getenv("E2ETTS_K1_CPI") ? atoi(getenv("E2ETTS_K1_CPI")) : 4;  // tuning aid: 0 = off, 2, 4
     if constexpr (BM == 128 || BM == 64) {
-      if (p.wfrag && p.KW == 1 && !p.accumulate && cpi_env > 0) {
-        if (cpi_env >= 4 && p.Cin % (4 * BK) == 0) return launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, true, 4>(p, s);
+      if (p.wfrag && p.KW == 1 && !p.accumulate) {
+        if (p.Cin % (4 * BK) == 0) return launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, true, 4>(p, s);
         if (p.Cin % (2 * BK) == 0) return launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, true, 2>(p, s);
       }
     }
-    if constexpr (MODE == 0 && BM == 128 && BN == 128) {  // three waves per SIMD (see OCC above); E2ETTS_F32_OCC=2: off (tuning aid)
-      static const bool occ3 = !(getenv("E2ETTS_F32_OCC") && atoi(getenv("E2ETTS_F32_OCC")) == 2);
-      if (p.wfrag && occ3 && p.zero_tap_split == 0)
+    if constexpr (MODE == 0 && BM == 128 && BN == 128) {  // three waves per SIMD (see OCC above)
+      if (p.wfrag && p.zero_tap_split == 0)
         return p.accumulate ? launch_cfg_impl<BM, BN, WM, WN, MODE, true, true, true, 0, 3>(p, s)
                             : launch_cfg_impl<BM, BN, WM, WN, MODE, false, true, true, 0, 3>(p, s);
     }
@@ -744,10 +739,9 @@ bool few_rows(const ConvParams& p) {  // host_logic.h
   return tile_few_rows_n(t128, rows, p.Cout) || (!p.wfrag && under_round_many_rows(p));
 }
 bool half_rows(const ConvParams& p) {
-  static const bool on = !(getenv("E2ETTS_HALF_ROWS") && atoi(getenv("E2ETTS_HALF_ROWS")) == 0);  // tuning aid
   if (!p.wfrag) return false;
   if (under_round_many_rows(p)) return true;
-  if (!on || p.accumulate) return false;
+  if (p.accumulate) return false;
   long long t128, rows;
   launch_counts(p, &t128, &rows);
   return tile_half_rows_n(t128, rows, p.Cout);

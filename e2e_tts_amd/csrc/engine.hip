@@ -24,6 +24,7 @@
 #define E2ETTS_ST_DEPTH 2   // chunks the streaming vocoder keeps in flight (tuning builds: 3)
 #endif
 #include "kernels.h"
+#include "tuning.h"
 
 using namespace e2etts;
 
@@ -370,10 +371,9 @@ int prof_collect(e2etts_engine* e) {
   } while (0)
 
 // The plain-bf16 mode's convolutions on conv_bf16.hip (bit-identical to conv_gemm's mode 2, so the choice is per launch): a padded
-// batch, dense rows, an activation that is a slope.  E2ETTS_BCONV=0 (tuning aid) keeps them on conv_gemm.
+// batch, dense rows, an activation that is a slope.  (tuning().bconv: off keeps them on conv_gemm.)
 bool bconv_params(const ConvParams& p, BConvParams& q) {
-  static const bool on = !(getenv("E2ETTS_BCONV") && atoi(getenv("E2ETTS_BCONV")) == 0);
-  if (!on || p.x3 != 2 || !p.bimg || p.act_rows || p.lens) return false;
+  if (!tuning().bconv || p.x3 != 2 || !p.bimg || p.act_rows || p.lens) return false;
   if (p.act != ACT_NONE && p.act != ACT_RELU && p.act != ACT_LRELU) return false;
   if (p.in_ld != p.Cin || p.out_ld != p.Cout || (p.res && p.res_ld != p.Cout)) return false;
   if (p.in_bs != (long long)p.T * p.Cin || p.out_bs != (long long)p.T * p.Cout || (p.res && p.res_bs != p.out_bs)) return false;
@@ -389,10 +389,17 @@ bool bconv_params(const ConvParams& p, BConvParams& q) {
   return conv_bf16_supported(q);
 }
 
+// E2ETTS_PROFILE_FINE (set at all, in the product library too): one profile class per layer shape instead of per kernel configuration.
+// It names profile classes and selects nothing.
+bool profile_fine() {
+  static const bool fine = getenv("E2ETTS_PROFILE_FINE") != nullptr;
+  return fine;
+}
+
 // One conv / linear launch.  alg_scale < 1 when part of the packed weight is structural zeros
 // (the polyphase upsampler) so that the recorded FLOPs stay the algorithmic ones.
 // ksplit: a phoneme-level layer (encoder FFT blocks, predictors): served by conv_ksplit.hip at every batch size when its fp32 fragment
-// image exists (E2ETTS_KSPLIT=0 routes them through conv_gemm again: tuning aid, changes the summation order of those layers)
+// image exists
 int conv(e2etts_engine* e, ConvParams p, double alg_scale = 1.0, bool ksplit = false) {
   if (p.in_ld == 0) p.in_ld = p.Cin;
   if (p.out_ld == 0) p.out_ld = p.Cout;
@@ -404,8 +411,7 @@ int conv(e2etts_engine* e, ConvParams p, double alg_scale = 1.0, bool ksplit = f
     auto it = e->frag_of.find(p.w);
     if (it != e->frag_of.end()) p.wfrag = it->second;
   }
-  // E2ETTS_PROFILE_FINE=1: one profile class per layer shape instead of per kernel configuration (a tuning aid)
-  static const bool fine = getenv("E2ETTS_PROFILE_FINE") != nullptr;
+  const bool fine = profile_fine();
   char fname[48];
   if (fine && e->prof_on)
     snprintf(fname, sizeof fname, "%s %d>%d k%d d%d r%lld%s%s", p.x3 ? "x3" : "f32", p.Cin, p.Cout, p.KW, p.dil,
@@ -419,23 +425,21 @@ int conv(e2etts_engine* e, ConvParams p, double alg_scale = 1.0, bool ksplit = f
     }
     if (p.in_bf16 || p.out_b || p.in_add[0]) return e->fail(E2ETTS_EINVAL, "bf16 hand-over / joined input asked of a launch conv_bf16 does not serve");
   }
-  static const bool ksplit_on = !(getenv("E2ETTS_KSPLIT") && atoi(getenv("E2ETTS_KSPLIT")) == 0);
   // ... and only where the chain is long (K = KW x Cin >= 768: the FFN convolutions, the predictors): a q | k | v or fc projection
   // (K = 384) is a chain of 12 short links, and at B = 32 the split costs those more (three idle waves per epilogue) than it saves.
   // The choice is by layer shape, never by batch size, so every batch size sums every layer in the same order.
-  if (ksplit && ksplit_on && (long long)((p.Cin + 31) / 32) * p.KW >= 24 && conv_ksplit_supported(p)) {
+  if (ksplit && (long long)((p.Cin + 31) / 32) * p.KW >= 24 && conv_ksplit_supported(p)) {
     ProfScope ps(e, fine && e->prof_on ? fname : "conv_ksplit", conv_gemm_flops(p) * alg_scale, conv_gemm_bytes(p));
     KCHK(e, launch_conv_ksplit(p, e->stream));
     return E2ETTS_OK;
   }
   // few rows (small batches, the B = 1 latency path) on fragment-order weights: conv_rows -- conv_gemm's arithmetic, MFMA for MFMA, with
-  // one wavefront per 32-row tile and no workgroup barrier (conv_ksplit.hip).  Same bits: E2ETTS_ROWS=0 (tuning aid) changes speed only.
+  // one wavefront per 32-row tile and no workgroup barrier (conv_ksplit.hip).  Same bits: tuning().rows changes speed only.
   // Taken where it measured ahead: convolutions (KW >= 3: a k = 1 Linear stages a slab per 6 MFMAs here, conv_gemm's multi-chunk items do
   // better) on grids of at most one 64 x 64 workgroup per CU -- B = 1: the decoder's k = 9 convolution 63 -> 40 us, the postnet's 52 -> 36;
   // at B = 4 conv_gemm's several workgroups per CU already hide what this kernel avoids.
-  static const bool rows_on = !(getenv("E2ETTS_ROWS") && atoi(getenv("E2ETTS_ROWS")) == 0);
   const long long wg64 = (long long)((p.T + 63) / 64) * p.B * ((p.Cout + 63) / 64);
-  if (rows_on && p.KW >= 3 && wg64 <= 256 && tile_few_rows(p.B, p.T, p.Cout) && conv_rows_supported(p)) {
+  if (tuning().rows && p.KW >= 3 && wg64 <= 256 && tile_few_rows(p.B, p.T, p.Cout) && conv_rows_supported(p)) {
     ProfScope ps(e, fine && e->prof_on ? fname : (p.x3 ? "conv_x3_rows" : "conv_rows"), conv_gemm_flops(p) * alg_scale, conv_gemm_bytes(p));
     KCHK(e, launch_conv_rows(p, e->stream));
     return E2ETTS_OK;
@@ -483,10 +487,9 @@ int make_frag(e2etts_engine* e, const float* wx3, uint64_t cout, uint64_t kw, ui
 }
 
 // fp32 weights of a layer the 128-column kernels serve (Cout > 64) -> fp32 fragment order, for the exact-fp32 mode.
-// phoneme_level: a layer conv_ksplit.hip serves -- that kernel has no other weight format, so its image is made whatever the tuning aid says.
+// phoneme_level: a layer conv_ksplit.hip serves -- that kernel has no other weight format, so its image is made whatever tuning().frag32 says.
 int make_frag32(e2etts_engine* e, const float* w, uint64_t cout, uint64_t kw, uint64_t cin, bool narrow = false, bool phoneme_level = false) {
-  static const bool off = getenv("E2ETTS_NO_FRAG32") != nullptr;  // tuning aid: A/B against the LDS weight tile
-  if ((off && !phoneme_level) || !w || (cout <= 64 && !narrow && !phoneme_level) || e->frag_of.count(w)) return E2ETTS_OK;
+  if ((!tuning().frag32 && !phoneme_level) || !w || (cout <= 64 && !narrow && !phoneme_level) || e->frag_of.count(w)) return E2ETTS_OK;
   float* f = nullptr;
   const size_t bytes = x3_frag_bytes((int)cout, (int)kw, (int)cin);
   HIPCHK(e, hipMalloc(&f, bytes));
@@ -899,10 +902,8 @@ int bind_vocoder(e2etts_engine* e) {
         KCHK(e, launch_x3_to_frag(e->rb_c2[idx][m].wx3, f + one / 4, (int)ch, k, (int)ch, e->stream));
       }
       // at 128 / 256 channels the fp32 kernels are bound by the matrix pipe and the fused form recomputes (KW - 1) / 128 of its rows:
-      // it pays up to a kernel size that the environment can move (tuning aid; same bits either way)
-      static const int f32_k128 = getenv("E2ETTS_F32_FUSE_K128") ? atoi(getenv("E2ETTS_F32_FUSE_K128")) : 7;
-      static const int f32_k256 = getenv("E2ETTS_F32_FUSE_K256") ? atoi(getenv("E2ETTS_F32_FUSE_K256")) : 0;
-      if (ch <= 64 || (ch == 128 && k <= f32_k128) || (ch == 256 && k <= f32_k256)) {  // fp32 images of the same pairs
+      // it pays up to kernel size 7 at 128 channels and not at 256 (same bits either way)
+      if (ch <= 64 || (ch == 128 && k <= 7)) {  // fp32 images of the same pairs
         float* b32 = nullptr;
         HIPCHK(e, hipMalloc(&b32, 2 * one * c.voc_n_dil));
         e->dev_bytes += 2 * one * c.voc_n_dil;
@@ -1605,34 +1606,6 @@ int acoustic_impl(e2etts_engine* e, const int64_t* ids, const int64_t* lens, int
 
 // ---- the ResBlock launches of the two vocoder walks (vocoder_impl, vocoder_act16): one set of builders
 
-// The tuning aids of vocoder_impl ("tuning aids"), read once.  All of them change speed only, never a result bit.
-struct VocTuning {
-  long long conc_frames;  // E2ETTS_VOC_CONC_FRAMES=n: most frames per call whose ResBlocks run side by side (unset, < 0: 2 048; 4 096 in exact fp32)
-  bool group;             // E2ETTS_VOC_GROUP=0 keeps the side streams where plain bf16 groups the ResBlocks into one launch
-  bool stream_side;       // E2ETTS_STREAM_SIDE=1: side streams in a stream slot's pass too
-  int brb_stage_big;      // E2ETTS_BRB_STAGE_BIG=0: no whole-stage rb_bf16 launch at large grids
-  bool brb_always;        // E2ETTS_BRB_ALWAYS=1: rb_bf16 (one ResBlock per launch) at large grids too
-  bool profile_fine;      // E2ETTS_PROFILE_FINE (set at all): one profile class per layer shape
-  bool bpair_big;         // E2ETTS_BPAIR_BIG=0 keeps resblock_pair.hip at large grids
-  bool defer_join;        // E2ETTS_VOC_DEFER_JOIN=0: a grouped stage's join as a launch of its own
-};
-const VocTuning& voc_tuning() {
-  static const VocTuning t = [] {
-    auto num = [](const char* name, long long unset) { const char* v = getenv(name); return v ? atoll(v) : unset; };
-    VocTuning v;
-    v.conc_frames = num("E2ETTS_VOC_CONC_FRAMES", -1);
-    v.group = num("E2ETTS_VOC_GROUP", 1) != 0;
-    v.stream_side = num("E2ETTS_STREAM_SIDE", 0) != 0;
-    v.brb_stage_big = (int)num("E2ETTS_BRB_STAGE_BIG", 1);
-    v.brb_always = num("E2ETTS_BRB_ALWAYS", 0) != 0;
-    v.profile_fine = getenv("E2ETTS_PROFILE_FINE") != nullptr;
-    v.bpair_big = num("E2ETTS_BPAIR_BIG", 1) != 0;
-    v.defer_join = num("E2ETTS_VOC_DEFER_JOIN", 1) != 0;
-    return v;
-  }();
-  return t;
-}
-
 // How a walk reads a convolution's weights.  kind 0, vocoder_impl: fp32 biases, the fragment-order pair images and -- in plain bf16 --
 // the conv_bf16.hip images of bimg_of; kind 1 / 2, vocoder_act16: bf16 / fp16 elements, i.e. the images of bimg_of | bimg_act / himg_of and
 // the parameters rounded to that type (r16_of / r16h_of).
@@ -2042,7 +2015,7 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
   float* const XU = ptr<float>(P.v1);
   const RbBufs mb = rb_bufs(P, 0);
   float *const S = mb.S, *const T1 = mb.T1, *const CUR = mb.CUR;
-  const VocTuning& tune = voc_tuning();
+  const Tuning& tune = tuning();
   const VocWeights W{e, 0};
 
   // weight selection: split-precision image when requested and present, else fp32
@@ -2088,10 +2061,10 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
   // ResBlock's launches -- 384 tiles on 256 CUs at B = 1, chains of 40-70 us kernels -- leave CUs idle at every tail.  They run side by
   // side: ResBlock 0 on the pass's stream into S, ResBlock j > 0 on a side stream into a sum buffer of its own, joined by
   // S = (S + S_j) [/ num_kernels] in the accumulating epilogue's order -- same operations, same bits.  Off while the full class profile is taken
-  // and above E2ETTS_VOC_CONC_FRAMES frames (default 2 048; 4 096 in exact fp32), where every launch fills the chip.
+  // and above tuning().voc_conc_frames frames (default 2 048; 4 096 in exact fp32), where every launch fills the chip.
   // (measured per batch size and mode: bf16x3 gains up to B = 2 at T = 768 and loses 1-2 % from B = 4, exact fp32 still gains 2 % at
   // B = 4 and loses from B = 8; a per-stage limit on the tile count instead showed nothing beyond noise)
-  const long long conc_frames = tune.conc_frames >= 0 ? tune.conc_frames : (e->voc_precision == E2ETTS_PRECISION_FP32 ? 4096 : 2048);
+  const long long conc_frames = tune.voc_conc_frames >= 0 ? tune.voc_conc_frames : (e->voc_precision == E2ETTS_PRECISION_FP32 ? 4096 : 2048);
   const int nk = c.voc_n_kernels, nd = c.voc_n_dil;
   // (a profile of ALL classes wants one kernel at a time; a profile filtered to one class -- bench.py's timed region -- records its
   // events on whichever stream the launch goes to and is fine)
@@ -2100,13 +2073,13 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
   // the pass's stream -- a third of the launches, no fork / join events, and a grid the three kernel sizes fill together (one ResBlock's
   // pair is 1.15 rounds of workgroups at a 542-frame window, the k = 11 stream the critical path of every stage, and the host needed
   // longer to enqueue three streams' launches than the GPU to run them).  Each ResBlock keeps its own buffers as on the side streams,
-  // and the join below is the same: same bits.  E2ETTS_VOC_GROUP=0 (tuning aid) keeps the streams.
+  // and the join below is the same: same bits.  (tuning().voc_group: off keeps the streams.)
   const bool small_window = nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && nk <= BC_GROUP_MAX && (long long)B * T <= conc_frames;
-  const bool group_mode = tune.group && small_window && e->voc_precision == E2ETTS_PRECISION_BF16 && !ragged_lens && c.voc_resblock == 1 && e->fuse_pairs;
+  const bool group_mode = tune.voc_group && small_window && e->voc_precision == E2ETTS_PRECISION_BF16 && !ragged_lens && c.voc_resblock == 1 && e->fuse_pairs;
   // A pass in a stream slot (e2etts_vocoder_stream_push) overlaps with the other slot's pass instead: side streams of its own would only
-  // crowd the process's four hardware queues (E2ETTS_STREAM_SIDE=1, tuning aid, keeps them); the calibration pass has none either.
+  // crowd the process's four hardware queues; the calibration pass has none either.
   const bool conc = (!full_profile || group_mode) && nk > 1 && nk <= E2ETTS_MAX_RB_KERNELS && (long long)B * T <= conc_frames &&
-                    (P.resident || tune.stream_side || group_mode);
+                    (P.resident || group_mode);
   if (conc)
     for (int j = 0; j + 1 < nk; ++j)
       for (int k = 0; k < 3; ++k) RET(ensure(e, P.vside[j][k], vb));
@@ -2241,7 +2214,7 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
     // Large grids, plain bf16, padded batch: the stage form of rb_bf16 (every ResBlock of the stage and their sum per workgroup: x read once,
     // the sum written once) where it exists (32 channels) -- there these stages run on the HBM roofline as pair launches.
     bool whole_stage_done = false;
-    if (tune.brb_stage_big && !grouped_stage && !conc && e->fuse_pairs >= 2 && !act_stage[i + 1] && nk <= BC_GROUP_MAX)
+    if (!grouped_stage && !conc && e->fuse_pairs >= 2 && !act_stage[i + 1] && nk <= BC_GROUP_MAX)
       RET(whole_stage(e, W, g, XU, S, whole_stage_done));
     for (int jj = 0; jj < nk && !grouped_stage && !whole_stage_done; ++jj) {
       const int j = conc ? nk - 1 - jj : jj;
@@ -2259,18 +2232,8 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
       // batches: 52 tiles at B = 1, T = 768) the two-launch form on 64 x 64 tiles fills the chip better (B = 1: 5.99 vs 6.45 ms per
       // utterance).  Both forms give the same bits, so the choice is invisible in the output.
       if (fused && co == 256 && (long long)B * (n / 128) < 256) fused = false;
-      // plain bf16, padded batch: the whole ResBlock in one launch on conv_bf16.hip's machinery, any kernel size at 32 / 64 channels
-      bool whole_rb = false;
-      // (at large grids the pair / chain kernels, two or three workgroups per CU, are ahead of this one-workgroup-per-CU kernel:
-      // measured 7.9 against 8.4 ms for the 60 s utterance in one call; E2ETTS_BRB_ALWAYS=1 takes it there too -- same bits)
-      if (tune.brb_always && fused && e->fuse_pairs >= 2 && !act_stage[i + 1]) {
-        RbParams rq;
-        if (rb_params(W, g, j, XU, S, rq)) {
-          RET(rb_single(e, W, g, rq, closing(j, true, nk, conc)));
-          whole_rb = true;
-          fused = false;   // nothing left for the pair / chain / two-launch forms below
-        }
-      }
+      // (no whole ResBlock per launch, rb_bf16, here: at large grids the pair / chain kernels, two or three workgroups per CU, are ahead
+      // of that one-workgroup-per-CU kernel: measured 7.9 against 8.4 ms for the 60 s utterance in one call)
       // the whole ResBlock in one launch (resblock_chain.hip) where it exists: kernel size 3 at 32 / 64 channels
       const bool chained = fused && !f32 && e->fuse_pairs >= 2 && resblock_chain_supported(co, k, c.voc_rb_dil[j], nd);
       if (chained) {
@@ -2296,10 +2259,10 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
         q.act_rows = act_stage[i + 1]; q.act_rows_host = act_stage_h[i + 1]; q.act_frac = vfs[i + 1];
         q.accumulate = cl.accumulate; q.out_div = cl.out_div;
         // (at large grids the two kernel families are level pair by pair; the whole 60 s utterance in one call: 7.69 ms with pair_bf16
-        // everywhere against 7.91 with resblock_pair.hip there, same box; E2ETTS_BPAIR_BIG=0 keeps the latter -- same bits)
-        const bool bpair = (tune.bpair_big || small_window) && pair_bf16_supported(q);
+        // everywhere against 7.91 with resblock_pair.hip there, same box -- same bits)
+        const bool bpair = pair_bf16_supported(q);
         char nm[48];
-        if (tune.profile_fine) snprintf(nm, sizeof nm, "pair %d k%d d%d r%lld%s", co, k, q.dil, (long long)B * n, q.accumulate ? "+a" : "");
+        if (profile_fine()) snprintf(nm, sizeof nm, "pair %d k%d d%d r%lld%s", co, k, q.dil, (long long)B * n, q.accumulate ? "+a" : "");
         else if (bpair) snprintf(nm, sizeof nm, "pair_bf16_%d", co);
         else snprintf(nm, sizeof nm, f32 ? "resblock_pair_f32_%d" : "resblock_pair_%d", co);
         ProfScope ps(e, nm, resblock_pair_flops(q), resblock_pair_bytes(q));
@@ -2318,7 +2281,7 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
         RET(conv(e, p));
         cur = p.out;
       }
-      for (int m = 0; m < nd && !fused && !whole_rb && c.voc_resblock == 1; ++m) {
+      for (int m = 0; m < nd && !fused && c.voc_resblock == 1; ++m) {
         const int d = c.voc_rb_dil[j][m];
         // xt = c1(lrelu(x)); the lrelu that feeds c2 is applied here, in c1's epilogue (V/layers.py:35-38)
         p = ConvParams();
@@ -2357,7 +2320,7 @@ int vocoder_impl(e2etts_engine* e, VocPass& P, const float* mel_btc, int B, int 
     // its launch and its pass over four tensors (142 MB at the 32- and 64-channel stages of a 542-frame window at 48 kHz).
     bool deferred = false;
     if (joined_in_kernel) deferred = true;   // nothing left to join
-    if (conc && grouped_stage && !joined_in_kernel && tune.defer_join && nk <= 4) {
+    if (conc && grouped_stage && !joined_in_kernel && tune.voc_defer_join && nk <= 4) {
       bool can = false;
       if (i + 1 < c.voc_stages) {
         ConvParams q;

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "kernels.h"
+#include "tuning.h"
 
 namespace e2etts {
 namespace {
@@ -991,9 +992,8 @@ const char* launch_dwconv_glu_swish(const float* in, const float* w, const float
   if (B <= 0 || N <= 0 || C <= 0 || C % 4 || k <= 0 || k % 2 == 0) return "dwconv_glu: channels must be a multiple of 4, kernel odd";
   if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)out | (uintptr_t)scratch) & 15) return "dwconv_glu: buffers must be 16-byte aligned";
   if (B > 65535) return "dwconv_glu: batch exceeds the grid limit";
-  static const bool off = getenv("E2ETTS_DWGLU") && atoi(getenv("E2ETTS_DWGLU")) == 0;   // tuning aid: the two-kernel form
   if (fused_out) *fused_out = true;
-  if (!off) {
+  if (tuning().dwglu) {   // (off: the two-kernel form)
     if (k == 31 && C % 128 == 0) return launch_dwglu_cfg<31, 128>(in, w, bias, out, B, N, C, s);
     if (k == 15 && C % 128 == 0) return launch_dwglu_cfg<15, 128>(in, w, bias, out, B, N, C, s);
     if (k == 7 && C % 64 == 0) return launch_dwglu_cfg<7, 64>(in, w, bias, out, B, N, C, s);

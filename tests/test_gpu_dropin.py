@@ -391,3 +391,58 @@ def test_product_library_gives_the_test_builds_bits(tmp_path):
         assert line[3] == want, line
         outs.append(line[1:3])
     assert outs[0] == outs[1]
+
+
+_TUNING_CHILD = r"""
+import hashlib, json, os, sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np
+from e2e_tts_amd import _lib, config as cfgmod, synth_weights as sw
+from e2e_tts_amd.runtime import engine_from_states
+lib = _lib.load_library()
+assert os.path.basename(lib._name) == sys.argv[3], lib._name
+cfg = cfgmod.tiny_config(); stats = cfgmod.DEFAULT_STATS
+ac = sw.make_acoustic_state(cfg, stats, 4, seed=1234, mode="varied"); voc = sw.make_vocoder_state(cfg, seed=4321)
+eng = engine_from_states(cfg, stats, ac, voc, device=0)
+eng.set_precision("bf16")
+eng.profile_enable(True)
+g = np.load(sys.argv[2])
+r = eng.acoustic(g["ids"], g["lens"], np.array([int(g["speaker"])], np.int64))
+wav, pcm = eng.vocoder(None, r["B"], r["T"], wav=False, pcm=True)
+classes = [[s["name"], s["launches"]] for s in eng.profile_read()]
+print("TUNING_CHILD", json.dumps({"sha": hashlib.sha256(np.ascontiguousarray(pcm).tobytes()).hexdigest(), "classes": classes}))
+"""
+
+# what sends the plain-bf16 vocoder and the few-rows / split-attention launches back to the older kernels -- in the test build only
+_TUNING_OFF = dict(E2ETTS_BCONV="0", E2ETTS_BPAIR="0", E2ETTS_BRB="0", E2ETTS_VOC_GROUP="0", E2ETTS_ROWS="0", E2ETTS_ATT_SPLIT_MAX="0")
+
+
+@pytest.mark.gpu
+def test_product_library_ignores_the_tuning_switches(tmp_path):
+    """The tuning switches (csrc/tuning.hip) are read by the test build alone.  Three child processes run the tiny model (B = 3, vocoder
+    precision bf16) once with the profile on: (a) the product library in a clean environment, (b) the product library with six switches
+    at 0, (c) the test build with the same six.  (b) must be (a) -- same PCM bits, same (class, launches) list: the product library runs its
+    default paths whatever the environment holds.  (c) must give the same bits on other kernels: no conv_bf16 / pair_bf16 / rb_ class,
+    which (a) -- conv_pre 80 -> 64 and the 32-channel stage of the tiny vocoder -- must have."""
+    import json
+    import subprocess
+    import sys
+    from conftest import GOLD, ROOT
+    script = tmp_path / "tuning_child.py"
+    script.write_text(_TUNING_CHILD)
+    clean = {k: v for k, v in os.environ.items() if k not in _TUNING_OFF}
+    outs = []
+    for hooks, name, extra in (("0", "libe2etts_hip.so", {}), ("0", "libe2etts_hip.so", _TUNING_OFF), ("1", "libe2etts_hip_test.so", _TUNING_OFF)):
+        env = dict(clean, E2ETTS_TEST_HOOKS=hooks, **extra)
+        r = subprocess.run([sys.executable, str(script), ROOT, os.path.join(GOLD, "tiny_b3.npz"), name], capture_output=True, text=True, timeout=300, env=env)
+        assert r.returncode == 0 and "TUNING_CHILD" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+        outs.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("TUNING_CHILD")][0].split(" ", 1)[1]))
+    a, b, c = outs
+    print("classes (a):", a["classes"])
+    print("classes (c):", c["classes"])
+    new = ("conv_bf16", "pair_bf16", "rb_")
+    assert b["sha"] == a["sha"] and b["classes"] == a["classes"]
+    assert c["sha"] == a["sha"]
+    assert c["classes"] != a["classes"]
+    assert not [n for n, _ in c["classes"] if n.startswith(new)], c["classes"]
+    assert [n for n, _ in a["classes"] if n.startswith(new)], a["classes"]

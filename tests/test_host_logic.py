@@ -339,3 +339,47 @@ def test_binding_refuses_wrong_dtypes_and_short_buffers():
         e.vocoder(np.zeros((1, e.dims.n_mel, 4)), 1, 4)
     with pytest.raises(ValueError, match="out_wav"):
         e.vocoder(np.zeros((1, e.dims.n_mel, 4), np.float32), 1, 4, out_wav=np.zeros(7, np.float32))
+
+
+TUNING_SWITCHES = ("E2ETTS_WG_PER_CU", "E2ETTS_FRAG64", "E2ETTS_NO_FRAG32", "E2ETTS_ROWS", "E2ETTS_ATT_SPLIT_MAX", "E2ETTS_ATT_PAR", "E2ETTS_DWGLU",
+                   "E2ETTS_VOC_CONC_FRAMES", "E2ETTS_BCONV", "E2ETTS_BPAIR", "E2ETTS_BRB", "E2ETTS_VOC_GROUP", "E2ETTS_VOC_DEFER_JOIN")
+RETIRED_SWITCHES = ("E2ETTS_LDS_PAD", "E2ETTS_K1_CPI", "E2ETTS_F32_OCC", "E2ETTS_HALF_ROWS", "E2ETTS_KSPLIT", "E2ETTS_F32_FUSE_K128", "E2ETTS_F32_FUSE_K256",
+                    "E2ETTS_STREAM_SIDE", "E2ETTS_BRB_STAGE_BIG", "E2ETTS_BRB_ALWAYS", "E2ETTS_BPAIR_BIG", "E2ETTS_ATT_PAR_MAX", "E2ETTS_ATT_NW",
+                    "E2ETTS_BCONV_MT", "E2ETTS_BCONV_NT", "E2ETTS_BCONV_LDS_MIN", "E2ETTS_BPAIR_MT", "E2ETTS_BPAIR256", "E2ETTS_BPAIR256_MT", "E2ETTS_BRB_W32",
+                    "E2ETTS_BRB_STAGE")
+
+
+def test_tuning_switches_are_one_table_that_only_the_test_build_reads():
+    """csrc/tuning.hip is the one table of the tuning switches and their one reader; only its -DE2ETTS_TEST_HOOKS object names them.  So the
+    product libraries hold none of the names (they cannot read what they do not name), the test build and the kernel harness hold all
+    thirteen, and the twenty-one retired switches are in no library.  Elsewhere in csrc/ the environment is read for E2ETTS_PROFILE_FINE
+    and E2ETTS_RCCL_LIB alone, in engine.hip."""
+    import glob
+    import __graft_entry__ as g
+    assert len(TUNING_SWITCHES) == 13 and len(RETIRED_SWITCHES) == 21
+    table = open(os.path.join(g.CSRC, "tuning.hip")).read()
+    assert set(re.findall(r'"(E2ETTS_[A-Z0-9_]+)"', table)) == set(TUNING_SWITCHES)
+    for path in glob.glob(os.path.join(g.CSRC, "**", "*"), recursive=True):
+        if not os.path.isfile(path) or os.path.basename(path) == "tuning.hip":
+            continue
+        text = open(path, errors="replace").read()
+        if os.path.relpath(path, g.CSRC) == "engine.hip":
+            assert sorted(re.findall(r'getenv\(\s*("[^"]*"|[^)]*)\)', text)) == ['"E2ETTS_PROFILE_FINE"', '"E2ETTS_RCCL_LIB"']
+            assert text.count("getenv(") == 2
+        else:
+            assert "getenv(" not in text, path
+    if g.built_hash() != g.source_hash() or g.built_hash(g.TEST_LIB) != g.source_hash():
+        g.build()
+    product = [g.LIB] + [c["lib"] for c in g.COMPANIONS]
+    test = [g.TEST_LIB, g.KT_LIB] + [c["test_lib"] for c in g.COMPANIONS]
+    for path in product:
+        blob = open(path, "rb").read()
+        for name in TUNING_SWITCHES + RETIRED_SWITCHES:
+            assert name.encode() not in blob, (path, name)
+    for path in test:
+        blob = open(path, "rb").read()
+        for name in RETIRED_SWITCHES:   # (as whole strings: E2ETTS_BPAIR and E2ETTS_BRB, which stay, begin some of these names)
+            assert name.encode() + b"\0" not in blob, (path, name)
+        if path in (g.TEST_LIB, g.KT_LIB):
+            for name in TUNING_SWITCHES:
+                assert name.encode() + b"\0" in blob, (path, name)

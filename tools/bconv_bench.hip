@@ -1,8 +1,10 @@
 // Self-check + micro-benchmark of conv_bf16.hip on the shapes of BASELINE config 5 (48 kHz HiFi-GAN, 8 x 8 x 4 x 2, width 512, B = 1):
 // every shape is run through conv_gemm in mode 2 (plain bf16: the path the engine used through round 3) and through conv_bf16, the outputs
 // are compared BIT FOR BIT (the two must be interchangeable per launch), and both are timed.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I e2e_tts_amd/csrc tools/bconv_bench.hip e2e_tts_amd/csrc/conv_bf16.hip \
-//          e2e_tts_amd/csrc/conv_gemm.hip e2e_tts_amd/csrc/resblock_pair.hip e2e_tts_amd/csrc/small_kernels.hip -o tools/bin/bconv_bench
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DE2ETTS_TEST_HOOKS -I e2e_tts_amd/csrc tools/bconv_bench.hip e2e_tts_amd/csrc/conv_bf16.hip \
+//          e2e_tts_amd/csrc/conv_gemm.hip e2e_tts_amd/csrc/resblock_pair.hip e2e_tts_amd/csrc/small_kernels.hip e2e_tts_amd/csrc/tuning.hip \
+//          -o tools/bin/bconv_bench
+// (-DE2ETTS_TEST_HOOKS: tuning.hip reads the tuning switches from the environment, as in the library's test build)
 // Usage: bconv_bench [reps] [name-filter | -] [frames: 542 = one streaming window (default), 5632 = the whole utterance]
 #include <hip/hip_runtime.h>
 

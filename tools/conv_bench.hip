@@ -1,5 +1,7 @@
 // Micro-benchmark + self-check of conv_gemm on the shapes of the B = 32, T = 768 workload.
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I e2e_tts_amd/csrc tools/conv_bench.hip e2e_tts_amd/csrc/conv_gemm.hip e2e_tts_amd/csrc/small_kernels.hip -o tools/bin/conv_bench
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -DE2ETTS_TEST_HOOKS -I e2e_tts_amd/csrc tools/conv_bench.hip e2e_tts_amd/csrc/conv_gemm.hip e2e_tts_amd/csrc/small_kernels.hip \
+//          e2e_tts_amd/csrc/conv_ksplit.hip e2e_tts_amd/csrc/tuning.hip -o tools/bin/conv_bench
+// (-DE2ETTS_TEST_HOOKS: tuning.hip reads the tuning switches from the environment, as in the library's test build)
 // Usage: [CONV_BENCH_B=1] [CONV_BENCH_KERNEL=rows|ksplit] conv_bench [reps] [name-filter | -] [f32 | f32f | x3 | x3f]
 //   (f32f / x3f: weights in MFMA-fragment order; CONV_BENCH_KERNEL: check and time conv_ksplit.hip's kernels -- they need f32f / x3f --
 //   instead of conv_gemm where they support the shape)
