@@ -14,6 +14,10 @@ companion library (include/e2etts_align.h): ``AlignmentEncoder``, ``b_mas`` and 
 The analysis side -- the reference's ``TorchSTFT.mel_spectrogram`` / ``generate_melspecs`` (e2e_tts/src/tools/stft.py), a recording to
 log-mel frames and frame energies -- is served by the mel library (include/e2etts_mel.h): ``TorchSTFT``, ``generate_melspecs`` and
 ``UnsupervisedFastSpeech2.align_audio`` (recording -> mel -> durations, all on the device).
+
+The f0 track of a recording and the data loader's pitch targets -- the reference's ``extract_f0`` (parselmouth) and ``get_f0`` -- are
+served by the pitch library (include/e2etts_f0.h; unpinned against parselmouth): ``extract_f0``, ``f0_targets`` and
+``UnsupervisedFastSpeech2.forward_audio(p_targets="extract")``.
 """
 from __future__ import annotations
 
@@ -304,8 +308,10 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         c.apply(gain, want=("pcm",), fetch=False)
         return c.resident()[0], a["n_out"].astype(np.int64), c.hip_stream()
 
-    def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition=None):
-        """``align_audio``'s work -> (its 4-tuple, the frame energies or None, the mel front-end's mel_lens [B] int64 on the host)."""
+    def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition=None, tap=None):
+        """``align_audio``'s work -> (its 4-tuple, the frame energies or None, the mel front-end's mel_lens [B] int64 on the host).
+        ``tap``: a dict that receives what the mel front-end was handed -- "x" (the samples, resident in the stage before when there is
+        one), "lens", "after" (that stage's stream, or None), "stft" -- for ``forward_audio``'s pitch tracker."""
         from . import aligner as al
         torch = _torch()
         if stft is None:
@@ -324,6 +330,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         spk = spk_table[sp].contiguous()
         fe = stft.frontend
         wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
+        after = None
         if condition is not None:
             x, wl, after = self._conditioned(wavs, wl, stft, wav_rate, condition)
             fe._call("order_after", after)                          # the mel's stream after the conditioner's
@@ -339,7 +346,10 @@ class UnsupervisedFastSpeech2(_EngineBacked):
             rsm = cache[key]
             wl = rsm.forward(x, n_valid=wl, want=())["n_out"]   # raises ValueError on a bad length before anything is enqueued
             x = rsm.resident()[0]                                # [B, width] float32 in the resampler's HBM, until its next forward
-            fe._call("order_after", rsm.hip_stream())           # the mel's stream after the resampler's
+            after = rsm.hip_stream()
+            fe._call("order_after", after)                       # the mel's stream after the resampler's
+        if tap is not None:
+            tap.update(x=x, lens=wl, after=after, stft=stft)
         energy = None
         if return_energy:
             energy = torch.zeros((B, max(1, int(wl.max()) // fe.hop)), dtype=torch.float32, device=dev)
@@ -456,20 +466,59 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         """``align_audio`` followed by the teacher-forced pass: recordings -> ground-truth-aligned mels, with the mel, the soft map and the
         durations never leaving the device.  p_targets / e_targets: frame-level targets [B, T] as for ``forward`` (T = the mel frames of
         the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``, ``condition``: as for ``align_audio`` (with
-        ``condition`` T follows from the kept samples).
+        ``condition`` T follows from the kept samples).  ``p_targets="extract"``: the pitch targets are made from the recordings
+        themselves, on the device: the pitch tracker (e2e_tts_amd.f0; unpinned against parselmouth, see there) reads the same samples
+        the mel front-end reads -- after ``condition`` and / or ``wav_rate`` too --, its track lies on the mel grid, and the data
+        loader's targets (``f0_targets`` with this model's stats and pitch_quantization) feed the pass where they lie.  That needs a
+        use_uv model: one without takes pyworld's extract_pitch in the reference, which is out of scope, and raises ValueError.
         -> ``forward``'s two tuples."""
-        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate, condition)
+        tap = None
+        if isinstance(p_targets, str):
+            if p_targets != "extract":
+                raise ValueError(f"p_targets must be None, targets, or 'extract' (got {p_targets!r})")
+            if not self.config["variance"]["variance_embedding"]["use_uv"]:
+                raise ValueError("p_targets='extract' needs a use_uv model: the targets of a model without come from pyworld's extract_pitch "
+                                 "in the reference, which this package does not restate")
+            tap = {}
+        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate, condition, tap=tap)
         self._check_lengths(txt_lens, ml)
         T = int(attn_out[0].shape[2])
+        if tap is not None:
+            p_targets = self._extracted_targets(tap, T)
         return self._forced(speaker, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, self._ensure_aligner()[0].encoder.stream())
+
+    def _extracted_targets(self, tap, T):
+        """{"f0", "uv"} [B, T] on the device from the samples the mel front-end was handed."""
+        from .f0 import PitchTracker
+        torch = _torch()
+        stft = tap["stft"]
+        key = (int(stft.sampling_rate), int(stft.hop_length), self._device)
+        cache = self.__dict__.setdefault("_trackers", {})
+        if key not in cache:
+            cache[key] = PitchTracker(key[0], key[1], device=self._device)
+        trk = cache[key]
+        if tap["after"]:
+            trk.order_after_stream(tap["after"])                   # the tracker's stream after the stage the samples lie in
+        r = trk.forward(tap["x"], tap["lens"], want=())
+        if r["T"] != T:
+            raise RuntimeError(f"the pitch track has {r['T']} frames, the mel {T}")
+        dev = torch.device("cuda", self._device)
+        B = len(tap["lens"])
+        f0 = torch.empty((B, T), dtype=torch.float32, device=dev)
+        uv = torch.empty((B, T), dtype=torch.float32, device=dev)
+        ve = self.config["variance"]["variance_embedding"]
+        trk.targets(self.stats, ve["pitch_quantization"], out_f0=f0, out_uv=uv)
+        return {"f0": f0, "uv": uv}
 
 
 def f0_targets(f0_hz, stats: Mapping[str, object], pitch_quantization: str = "linear", pitch_eps: float = 0.000000001):
     """A recording's f0 track in Hz (0 = unvoiced) -> (f0 target, uv target) as the reference's data loader makes them (get_f0,
     src/tools/dataloader.py:185-196): uv = f0 == 0; f0 normalised with stats["f0"] -- or log2(f0 + pitch_eps) for pitch_quantization
     "log" --; unvoiced stretches filled by linear interpolation between their voiced neighbours (np.interp: constant beyond the first and
-    the last voiced frame), an all-unvoiced track set to 0.  The f0 extractor itself (parselmouth in the reference) is not part of this
-    package: callers bring the Hz track.  -> (f0 in the input's float dtype, uv float32), numpy arrays of one utterance [T]."""
+    the last voiced frame), an all-unvoiced track set to 0.  The Hz track comes from ``extract_f0`` below (the pitch library,
+    e2e_tts_amd.f0: Boersma's autocorrelation method restated, unpinned against the parselmouth the reference calls) or from any
+    extractor of the caller's; ``PitchTracker.targets`` computes the same on the device.
+    -> (f0 in the input's float dtype, uv float32), numpy arrays of one utterance [T]."""
     f0 = np.array(f0_hz, copy=True)
     if f0.ndim != 1:
         raise ValueError(f"f0_targets takes one utterance's track [T], got shape {f0.shape}")
@@ -482,6 +531,45 @@ def f0_targets(f0_hz, stats: Mapping[str, object], pitch_quantization: str = "li
     elif sum(uv) > 0:
         f0[uv] = np.interp(np.where(uv)[0], np.where(~uv)[0], f0[~uv])
     return f0, uv.astype(np.float32)
+
+
+_TRACKER_CACHE = {}
+# f0_to_coarse's constants (src/tools/utils.py:15-19)
+_F0_BIN, _F0_MIN, _F0_MAX = 256, 50.0, 1100.0
+
+
+def f0_to_coarse(f0):
+    """The reference's f0_to_coarse (src/tools/utils.py:81-90), restated: Hz -> mel-scaled bins 1 .. 255 (np.rint, then a plain integer
+    cast where the reference uses the retired ``np.int``)."""
+    f0 = np.asarray(f0, np.float64)
+    mel_min, mel_max = 1127 * np.log(1 + _F0_MIN / 700), 1127 * np.log(1 + _F0_MAX / 700)
+    f0_mel = 1127 * np.log(1 + f0 / 700)
+    f0_mel[f0_mel > 0] = (f0_mel[f0_mel > 0] - mel_min) * (_F0_BIN - 2) / (mel_max - mel_min) + 1
+    f0_mel[f0_mel <= 1] = 1
+    f0_mel[f0_mel > _F0_BIN - 1] = _F0_BIN - 1
+    return np.rint(f0_mel).astype(np.int64)
+
+
+def extract_f0(wav_data, mel_len: int, sample_rate: int, hop_length: int, with_pitch: bool = False, device=None):
+    """The reference's ``extract_f0`` (src/tools/utils.py:46-78) for one utterance, on the pitch library: wav_data [n] (float in [-1, 1]
+    or int16 PCM) -> the f0 track in Hz [mel_len] float64, 0 = unvoiced (and ``f0_to_coarse`` of it with ``with_pitch``).  The reference
+    calls parselmouth and then truncates and pads its track onto the mel length; here the track is computed on the mel grid (frame t is
+    centred where mel frame t of ``TorchSTFT`` is), so it has floor(n / hop_length) frames by construction: ``mel_len`` must be that
+    number, and nothing is padded.  Unpinned against parselmouth (e2e_tts_amd.f0)."""
+    from .f0 import PitchTracker
+    x = np.asarray(wav_data)
+    if x.ndim != 1:
+        raise ValueError(f"extract_f0 takes one utterance [n], got shape {x.shape}")
+    if x.dtype != np.int16:
+        x = x.astype(np.float32)
+    frames = x.shape[0] // int(hop_length)
+    if int(mel_len) != frames:
+        raise ValueError(f"mel_len = {int(mel_len)}, but {x.shape[0]} samples at hop {int(hop_length)} are {frames} mel frames")
+    key = (int(sample_rate), int(hop_length), _device_index(device))
+    if key not in _TRACKER_CACHE:
+        _TRACKER_CACHE[key] = PitchTracker(*key[:2], device=key[2])
+    f0 = _TRACKER_CACHE[key].forward(x[None])["f0"][0].astype(np.float64)
+    return (f0, f0_to_coarse(f0)) if with_pitch else f0
 
 
 class AlignmentEncoder:
