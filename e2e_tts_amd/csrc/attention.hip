@@ -62,7 +62,7 @@ __device__ __forceinline__ float seg_merge_o(const float o, const float o_s, con
 
 // (utterance b, head, query block qblk) of this workgroup.  Padded grid: (x, y, z) = (query block, head, utterance).  Compact grid of a
 // ragged batch whose lengths the host knows (kernels.h: RowMap): 1-D, utterance b owns ceil(len_b / rows) x n_head consecutive blocks,
-// heads fastest -- no block of padded queries exists (their output rows keep what they held: every consumer masks them, engine.hip).
+// heads fastest -- no block of padded queries exists (their output rows keep what they held: every consumer masks them, engine_acoustic.hip).
 #define ATT_BLOCK_OF_GRID(rows)                                    \
   int b, head, qblk;                                               \
   if (rm.n > 0) {                                                  \

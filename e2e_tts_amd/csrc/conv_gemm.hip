@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256, OCC) void conv_gemm_kernel(const ConvParams p,
     bx = g - b * gx;
   }
   const int n0 = by * BN;
-  // ragged batches: rows >= act_rows[b] are not needed by anyone (see engine.hip) -- whole tiles beyond them are skipped
+  // ragged batches: rows >= act_rows[b] are not needed by anyone (see engine_acoustic.hip, engine_vocoder.hip) -- whole tiles beyond them are skipped
   const int t_act = p.act_rows ? min(p.act_rows[b], p.T) : p.T;
   const int mtiles = (t_act + BM - 1) / BM;
   const int tile0 = bx * tiles_per_block;

@@ -2,11 +2,11 @@
 //
 // The reference's STFT is a strided convolution with the windowed Fourier basis and its inverse a transposed convolution with the
 // windowed pseudo-inverse.  With hop = filter_length / n_overlap both are "same" convolutions over ROWS of hop samples, which
-// conv_gemm computes in exact fp32 (engine.hip: denoise_impl):
+// conv_gemm computes in exact fp32 (engine_denoise.hip: denoise_impl):
 //   forward   the reflect-padded signal as rows [B, F + n_overlap - 1, hop]; frame f is rows f .. f + n_overlap - 1, so the
 //             spectrum is a KW = n_overlap, Cin = hop, Cout = filter_length + 2, pad = 0 convolution;
 //   inverse   Cin = filter_length + 2, Cout = hop, the taps reversed: output row q = sum_s frame[q - s] . W_s holds samples q * hop ..
-//             q * hop + hop - 1 of the overlap-add.  Run as one accumulated KW = 1 launch per tap (engine.hip: denoise_impl says why).
+//             q * hop + hop - 1 of the overlap-add.  Run as one accumulated KW = 1 launch per tap (engine_denoise.hip: denoise_impl says why).
 // What is left are three HBM-bound passes, each a sweep of float4 rows:
 //   stft_pad_kernel            F.pad(mode = 'reflect') per utterance at ITS OWN end, into the row layout (:98-101)
 //   spectral_subtract_kernel   magnitude, - strength * bias, clamp at 0, back to re / im without the three transcendentals (:115-123, :182-184)

@@ -1,6 +1,6 @@
-// libe2etts_forced.so: the entry points of include/e2etts_forced.h.  The pass itself lives in engine.hip (acoustic_impl's forced plan) and
+// libe2etts_forced.so: the entry points of include/e2etts_forced.h.  The pass itself lives in engine_acoustic.hip (acoustic_impl's forced plan) and
 // teacher.hip; this file only gives it exported names, because the main library's set of exports is frozen.  Linked with the engine
-// object and every kernel object of the main library.
+// objects and every kernel object of the main library.
 #include "../forced_entry.h"
 
 #ifndef E2EFORCED_SRC_HASH

@@ -1,7 +1,8 @@
 // Host-side logic of the engine that touches no HIP API: weight-blob header / directory validation, engine-config validation,
-// the vocoder's receptive field, and the tile choice of conv_gemm.  Kept free of <hip/...> so that tests/csrc/host_logic_test.cc can
-// build it with gcc -fsanitize=address,undefined and feed it truncated / corrupt blobs (tests/test_host_sanitizer.py); engine.hip and
-// conv_gemm.hip include the same header, so what the sanitizer run exercises is the code the library ships.
+// the vocoder's receptive field, the ragged row limits, and the tile choice of conv_gemm.  Kept free of <hip/...> so that
+// tests/csrc/host_logic_test.cc can build it with gcc -fsanitize=address,undefined and feed it truncated / corrupt blobs
+// (tests/test_host_sanitizer.py); the engine's sources (engine.h), conv_gemm.hip and small_kernels.hip include the same header, so what the
+// sanitizer run exercises is the code the library ships.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -195,6 +196,32 @@ inline void ragged_counts(const int32_t* rows, int B, int T, int Cout, long long
   }
   *t128 = t * (((long long)Cout + 127) / 128);
   *nrows = r;
+}
+
+// ---- ragged-batch row limits: the rows of utterance b that a layer computes, min(cap, (len + add) * mul + add_rows).  Written once:
+// act_rows_kernel (small_kernels.hip) computes the device copy with it, host_row_limits the host copy that the compact grids
+// (kernels.h: RowMap) are built from -- the two must agree row for row.
+#ifdef __HIPCC__
+#define E2ETTS_HOST_DEVICE __host__ __device__
+#else
+#define E2ETTS_HOST_DEVICE
+#endif
+E2ETTS_HOST_DEVICE inline long long row_limit(long long len, int add, int mul, long long cap, long long add_rows) {
+  const long long v = (len + add) * mul + add_rows;
+  return v < cap ? v : cap;
+}
+// out[0 .. B) (may be null): the limits the kernel writes for these lengths, which it reads as int32 (a length beyond INT32_MAX reached it
+// as INT32_MAX).  Returns the sum over b of the limit of len[b] as given, a negative one counting as no rows (profile FLOP fractions).
+template <typename Len>
+inline double host_row_limits(int32_t* out, const Len* len, int B, int add, int mul, long long cap, long long add_rows) {
+  double sum = 0;
+  for (int b = 0; b < B; ++b) {
+    const long long l = (long long)len[b], l32 = l < 0x7fffffffLL ? l : 0x7fffffffLL;
+    if (out) out[b] = (int32_t)row_limit(l32, add, mul, cap, add_rows);
+    const long long v = row_limit(l, add, mul, cap, add_rows);
+    sum += (double)(v > 0 ? v : 0);
+  }
+  return sum;
 }
 
 // ---- e2etts_acoustic_forced (include/e2etts_forced.h): what the struct asks for, checked before anything is enqueued.

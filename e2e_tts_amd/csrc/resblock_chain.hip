@@ -15,7 +15,7 @@
 //   * LDS holds two A-operand images (bf16 hi | lo rows of 144 B per 32 channels, as in conv_gemm.hip): X = lrelu(x_m) with d_max guard
 //     rows of zeros at either end (conv1's dilated taps read row-shifted views of it) and I = lrelu(c1 + b1) with one guard row (conv2);
 //     positions outside [0, T) are written as zeros into both (the zero padding of the two convolutions);
-//   * weights come as MFMA fragments from L2, conv1 | conv2 of pair 0, 1, 2 contiguous (engine.hip lays the ResBlock's images out so);
+//   * weights come as MFMA fragments from L2, conv1 | conv2 of pair 0, 1, 2 contiguous (engine_weights.hip lays the ResBlock's images out so);
 //   * the MFMAs compute the TRANSPOSED product D^T = W . X^T (weights as the A operand, activations as B; the operand images are the
 //     same either way): an accumulator lane then holds ONE position and, per register quad, four CONSECUTIVE channels -- so x_0 comes
 //     in and x_3 goes out as float4 per lane, and an A-operand image row is written with two ds_write_b64 per quad (packed

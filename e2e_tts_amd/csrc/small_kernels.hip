@@ -5,6 +5,7 @@
 
 #include <algorithm>
 
+#include "host_logic.h"
 #include "kernels.h"
 #include "tuning.h"
 
@@ -343,8 +344,7 @@ __global__ __launch_bounds__(128) void add_positions_kernel(float* __restrict__ 
 __global__ void act_rows_kernel(const int32_t* __restrict__ lens, int32_t* __restrict__ out, int B, int add, int mul, long long cap, long long add_rows) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < B) {
-    const long long v = ((long long)lens[i] + add) * mul + add_rows;
-    out[i] = (int32_t)(v < cap ? v : cap);
+    out[i] = (int32_t)row_limit(lens[i], add, mul, cap, add_rows);
   }
 }
 
@@ -882,7 +882,7 @@ const char* launch_add_positions(float* y, const float* pos, int B, int T, int H
   return CHECK_LAUNCH("add_positions");
 }
 
-// S = (S + Sj) [/ div]: joins the stage sums of ResBlocks that ran side by side (engine.hip, small batches); the operations the
+// S = (S + Sj) [/ div]: joins the stage sums of ResBlocks that ran side by side (engine_vocoder.hip, small batches); the operations the
 // accumulating epilogues of conv_gemm / resblock_pair / resblock_chain perform, in their order.
 __global__ void accum_div_kernel(float* __restrict__ S, const float* __restrict__ Sj, const float* __restrict__ Sk, long long n4, float div) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

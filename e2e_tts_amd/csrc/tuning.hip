@@ -17,7 +17,7 @@ const Tuning& tuning() {
     // conv_gemm.hip
     t.wg_per_cu = (int)num("E2ETTS_WG_PER_CU", t.wg_per_cu);   // =n: row groups per CU that conv_gemm sizes its persistent workgroups for
     t.frag64 = on("E2ETTS_FRAG64");                            // =0: the 64 x 64 few-rows tile on the LDS weight tile, not on fragments
-    // engine.hip
+    // engine_weights.hip, engine_core.hip, engine_vocoder.hip
     t.frag32 = getenv("E2ETTS_NO_FRAG32") == nullptr;          // set at all: fp32 weights through the LDS tile (A/B against the fragments)
     t.rows = on("E2ETTS_ROWS");                                // =0: few-rows convolutions on conv_gemm's 64 x 64 tile instead of conv_rows
     t.bconv = on("E2ETTS_BCONV");                              // =0: plain-bf16 convolutions stay on conv_gemm's mode 2

@@ -127,7 +127,7 @@ def polyphase_upsampler(w: np.ndarray, b: np.ndarray, stride: int):
 
 
 def pack_tensors(dims: EngineDims, acoustic: Optional[Mapping[str, object]], vocoder: Optional[Mapping[str, object]]) -> "OrderedDict[str, np.ndarray]":
-    """Engine tensor name -> fp32 array (consumers: bind_acoustic() / bind_vocoder() in csrc/engine.hip).
+    """Engine tensor name -> fp32 array (consumers: bind_acoustic() / bind_vocoder() in csrc/engine_weights.hip).
     Either state dict may be None: the blob then carries only the other model."""
     out: "OrderedDict[str, np.ndarray]" = OrderedDict()
     if acoustic is not None:

@@ -1,10 +1,11 @@
 // Sanitizer harness for e2e_tts_amd/csrc/host_logic.h (the engine's HIP-free host logic: blob header / directory validation, config
-// validation, vocoder halo, conv_gemm tile choice).  Built by tests/test_host_sanitizer.py with
+// validation, vocoder halo, ragged row limits, conv_gemm tile choice).  Built by tests/test_host_sanitizer.py with
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all
 // and fed valid, truncated and corrupt inputs; any out-of-bounds read or integer overflow aborts the process (non-zero exit).
 //   host_logic_test blob <file>         -> "OK <n_tensors> <sum of numel>" | "ERR <message>"
 //   host_logic_test config <file>       -> "OK halo=<frames> stage_rows=<r0,r1,..>" | "ERR <message>"     (file = raw e2etts_config bytes)
 //   host_logic_test tiles B T Cout      -> "few=<0|1> half=<0|1>"
+//   host_logic_test limits add mul cap add_rows len... -> "sum=<sum> out=<limit_0,limit_1,..>"      (host_row_limits)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -77,6 +78,20 @@ int main(int argc, char** argv) {
     printf("t128=%lld rows=%lld few=%d half=%d\n", t128, n, tile_few_rows_n(t128, n, Cout) ? 1 : 0, tile_half_rows_n(t128, n, Cout) ? 1 : 0);
     return 0;
   }
-  fprintf(stderr, "usage: host_logic_test blob|config <file> | tiles B T Cout | ragged T Cout rows...\n");
+  if (argc >= 7 && !strcmp(argv[1], "limits")) {  // limits add mul cap add_rows len_0 len_1 ...: the host copy of act_rows_kernel's limits and their sum
+    const int add = atoi(argv[2]), mul = atoi(argv[3]);
+    const long long cap = atoll(argv[4]), add_rows = atoll(argv[5]);
+    std::vector<int64_t> lens;
+    for (int i = 6; i < argc; ++i) lens.push_back((int64_t)atoll(argv[i]));
+    std::vector<int32_t> out(lens.size() + 1, 12345);   // (one guard element: the helper writes B values)
+    const double sum = host_row_limits(out.data(), lens.data(), (int)lens.size(), add, mul, cap, add_rows);
+    const double sum_only = host_row_limits((int32_t*)nullptr, lens.data(), (int)lens.size(), add, mul, cap, add_rows);
+    if (out.back() != 12345 || sum_only != sum) { puts("ERR guard overwritten or the sum depends on out"); return 0; }
+    printf("sum=%.0f out=", sum);
+    for (size_t b = 0; b < lens.size(); ++b) printf(b ? ",%d" : "%d", out[b]);
+    printf("\n");
+    return 0;
+  }
+  fprintf(stderr, "usage: host_logic_test blob|config <file> | tiles B T Cout | ragged T Cout rows... | limits add mul cap add_rows lens...\n");
   return 2;
 }

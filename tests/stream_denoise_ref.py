@@ -1,5 +1,5 @@
 """Numpy restatement of the denoised vocoder stream (include/e2etts.h: e2etts_vocoder_stream_begin_denoised; engine.hip:
-e2etts_vocoder_stream_push, denoise_stream_impl), for the host tests.
+e2etts_vocoder_stream_push; engine_denoise.hip: denoise_stream_impl), for the host tests.
 
 ``stream_plan``      the window arithmetic of _push, in mel frames: what each push's window holds and which of its frames it emits.
 ``denoise_window``   the denoiser as a function of one window of a longer signal, in ``denoiser_ref.denoise_rows``' arithmetic (float32 rows of

@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the vocoder-bias denoiser (csrc/denoiser.hip, engine.hip: denoise_impl; include/e2etts.h: e2etts_denoiser_*,
+"""GPU tests (-m gpu) of the vocoder-bias denoiser (csrc/denoiser.hip, engine_denoise.hip: denoise_impl; include/e2etts.h: e2etts_denoiser_*,
 e2etts_denoise, e2etts_set_denoise) against tests/golden/denoiser.npz, which tools/make_denoiser_goldens.py wrote from the reference's
 own module (V/denoiser.py) run on every row alone.
 
@@ -181,7 +181,7 @@ def test_vocoder_audio_with_the_references_bias(eng, gold):
     This audio (a random-weight vocoder's output) carries a constant offset, and the reference's own distance on it is half that of (a)
     and (b), so it is the hardest of the three for a GEMM that sums in one chain.  With the inverse transform as ONE KW = n_overlap
     convolution (a chain of 4 224 terms per sample) the MI355X measured mean-L1 5.934e-08 against the bar of 5.214e-08 and max 7.888e-07
-    against 6.009e-07: not met.  The inverse now runs as one accumulated launch per tap (engine.hip: denoise_impl); measured in that
+    against 6.009e-07: not met.  The inverse now runs as one accumulated launch per tap (engine_denoise.hip: denoise_impl); measured in that
     form: 2.595e-08 / 2.448e-07."""
     load_geometry(eng, 1024, 4)
     eng.denoiser_set_bias(gold["c_bias_spec"])

@@ -1,5 +1,5 @@
 """GPU parity (-m gpu) of the Fastformer encoder / decoder blocks (building_block.block_type "fastformer", csrc/fastformer.hip +
-engine.hip: fastformer_stack) against the fixtures tools/make_fastformer_goldens.py wrote from the reference's own run, and against the
+engine_acoustic.hip: fastformer_stack) against the fixtures tools/make_fastformer_goldens.py wrote from the reference's own run, and against the
 numpy restatement tests/fastformer_ref.py on geometries no fixture has.
 
 Bars: those tests/test_gpu_parity.py holds the Conformer fixtures to -- discrete outputs exact, taps / predictions / mel mean-L1 < 1e-5 on

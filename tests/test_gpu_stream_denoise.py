@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the denoised vocoder stream (include/e2etts.h: e2etts_vocoder_stream_begin_denoised; engine.hip:
+"""GPU tests (-m gpu) of the denoised vocoder stream (include/e2etts.h: e2etts_vocoder_stream_begin_denoised; engine_denoise.hip:
 denoise_stream_impl; csrc/denoiser.hip: the stream forms of the pad and overlap-add passes).
 
 The contract is bit equality: the concatenated pieces of a denoised stream are e2etts_denoise of the one-shot vocoder's waveform, as fp32

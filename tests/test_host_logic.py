@@ -353,21 +353,23 @@ def test_tuning_switches_are_one_table_that_only_the_test_build_reads():
     """csrc/tuning.hip is the one table of the tuning switches and their one reader; only its -DE2ETTS_TEST_HOOKS object names them.  So the
     product libraries hold none of the names (they cannot read what they do not name), the test build and the kernel harness hold all
     thirteen, and the twenty-one retired switches are in no library.  Elsewhere in csrc/ the environment is read for E2ETTS_PROFILE_FINE
-    and E2ETTS_RCCL_LIB alone, in engine.hip."""
+    and E2ETTS_RCCL_LIB alone, in the engine's sources (engine*.hip and engine.h, taken together: one call each)."""
     import glob
     import __graft_entry__ as g
     assert len(TUNING_SWITCHES) == 13 and len(RETIRED_SWITCHES) == 21
     table = open(os.path.join(g.CSRC, "tuning.hip")).read()
     assert set(re.findall(r'"(E2ETTS_[A-Z0-9_]+)"', table)) == set(TUNING_SWITCHES)
+    engine_text = ""
     for path in glob.glob(os.path.join(g.CSRC, "**", "*"), recursive=True):
         if not os.path.isfile(path) or os.path.basename(path) == "tuning.hip":
             continue
         text = open(path, errors="replace").read()
-        if os.path.relpath(path, g.CSRC) == "engine.hip":
-            assert sorted(re.findall(r'getenv\(\s*("[^"]*"|[^)]*)\)', text)) == ['"E2ETTS_PROFILE_FINE"', '"E2ETTS_RCCL_LIB"']
-            assert text.count("getenv(") == 2
+        if re.fullmatch(r"engine(_\w+)?\.hip|engine\.h", os.path.relpath(path, g.CSRC)):
+            engine_text += text
         else:
             assert "getenv(" not in text, path
+    assert sorted(re.findall(r'getenv\(\s*("[^"]*"|[^)]*)\)', engine_text)) == ['"E2ETTS_PROFILE_FINE"', '"E2ETTS_RCCL_LIB"']
+    assert engine_text.count("getenv(") == 2
     if g.built_hash() != g.source_hash() or g.built_hash(g.TEST_LIB) != g.source_hash():
         g.build()
     product = [g.LIB] + [c["lib"] for c in g.COMPANIONS]

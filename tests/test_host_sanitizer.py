@@ -1,7 +1,7 @@
 """The engine's HIP-free host logic (e2e_tts_amd/csrc/host_logic.h: weight-blob header / directory validation, config
-validation, vocoder halo, conv_gemm tile choice) built with AddressSanitizer + UBSan on the CPU (the reference
-has no sanitizer target; GPU ASan is not available on this pool) and fed valid, truncated and corrupt inputs.  engine.hip and
-conv_gemm.hip include the same header, so this is the code the library ships."""
+validation, vocoder halo, ragged row limits, conv_gemm tile choice) built with AddressSanitizer + UBSan on the CPU (the
+reference has no sanitizer target; GPU ASan is not available on this pool) and fed valid, truncated and corrupt inputs.  The engine's
+sources (csrc/engine.h), conv_gemm.hip and small_kernels.hip include the same header, so this is the code the library ships."""
 import ctypes
 import os
 import struct
@@ -152,6 +152,32 @@ def test_ragged_counts(harness):
     assert out.startswith("t128=") and out.endswith("few=0 half=1"), out
     assert run(harness, "tiles", 32, 1200, 1024) == "few=0 half=0"
     assert run(harness, "ragged", 0x7FFFFFFF, 0x7FFFFFFF, *([0x7FFFFFFF] * 64)).startswith("t128=")
+
+
+def test_row_limits(harness):
+    """host_logic.h: host_row_limits, the host copy of the ragged row limits (act_rows_kernel computes the device copy with the same
+    row_limit; tests/test_gpu_small_kernels.py: test_act_rows ties the kernel to these numbers).  Against the arithmetic written out here:
+    the limit is min(cap, (len + add) * mul + add_rows); what is WRITTEN comes from the length as the kernel reads it (int32: beyond
+    INT32_MAX it arrived as INT32_MAX) and is stored as int32; the SUM is over the lengths as given, a negative limit counting as 0."""
+    i32max = 0x7FFFFFFF
+
+    def as_i32(v):
+        return (v + (1 << 31)) % (1 << 32) - (1 << 31)
+
+    n = 0
+    for cap in (1000, 1 << 42):   # below the long lengths' products / above the product of every int32 length ((2^42 + 8) * 256 + 109 < 2^63: no overflow)
+        lens = (-5, 0, cap - 1, cap, cap + 1, i32max)
+        for mul in (1, 256):
+            for add in (0, 7):
+                for add_rows in (0, 109):
+                    for batch in [(v,) for v in lens] + [lens[:3], lens[3:]]:   # B = 1 and B = 3
+                        want_out = [as_i32(min(cap, (min(v, i32max) + add) * mul + add_rows)) for v in batch]
+                        want_sum = sum(max(min(cap, (v + add) * mul + add_rows), 0) for v in batch)
+                        assert want_sum < 1 << 53   # exact in the double the helper returns
+                        got = run(harness, "limits", add, mul, cap, add_rows, *batch)
+                        assert got == f"sum={want_sum} out=" + ",".join(map(str, want_out)), (cap, mul, add, add_rows, batch, got)
+                        n += 1
+    assert n == 2 * 2 * 2 * 2 * 8
 
 
 def _exact_stage_rows(rates, kernels, dils, resblock=1, tail=3):

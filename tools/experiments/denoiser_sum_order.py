@@ -4,7 +4,7 @@ output accumulated as conv_gemm accumulates it -- ONE float32 chain per output, 
 tap, then channel) -- instead of BLAS's blocked sums, compared with the reference's float64 run stored in tests/golden/denoiser.npz.
 
 Variants: the forward / inverse GEMM exact (float64, rounded once) to see which one carries the error; the forward / inverse GEMM as
-one chain per tap, the taps added afterwards (what engine.hip: denoise_impl does for the inverse).
+one chain per tap, the taps added afterwards (what engine_denoise.hip: denoise_impl does for the inverse).
 
 On fixture (c) (the tiny vocoder's audio, which has a constant offset) this printed, mean-L1 / max against float64:
     one chain each            5.888e-08 / 7.739e-07     (MI355X, inverse as one KW = 4 convolution: 5.934e-08 / 7.888e-07)
