@@ -77,6 +77,148 @@ __device__ __forceinline__ float seg_merge_o(const float o, const float o_s, con
     qblk = blockIdx.x;                                             \
   }
 
+// ---- The phases the kernels share, one definition each.  The bit-level guarantees of this file -- serial and split forms agree, the
+// workspace merge equals the in-register merge, a B = 1 utterance equals its row of a batch -- hold because every kernel runs THESE
+// operations in this order; none of them knows another kernel's arithmetic.
+
+template <int DT>
+__device__ __forceinline__ void att_clear(f32x16 (&o)[DT]) {
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+}
+
+// A tile that holds only padded queries: their rows are zero (padded grids; a compact grid has no such block).  ROWS queries, NTH threads.
+template <int ROWS, int NTH, int DK>
+__device__ __forceinline__ void att_zero_tile(float* __restrict__ out, const int b, const int qblk, const int head, const int N, const int H,
+                                              const int tid) {
+  for (int i = tid; i < ROWS * (DK / 4); i += NTH) {
+    const int q = qblk * ROWS + i / (DK / 4);
+    if (q < N) *reinterpret_cast<float4*>(out + ((long long)b * N + q) * H + head * DK + (i % (DK / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// Q fragments, fp32 operands: lane (query li, half lh) holds Q[q][8 qq + 4 lh + r]; qr points at Q[q][4 lh]
+template <int QQ>
+__device__ __forceinline__ void att_load_q_f32(float4 (&qf)[QQ], const float* __restrict__ qr) {
+#pragma unroll
+  for (int qq = 0; qq < QQ; ++qq) qf[qq] = *reinterpret_cast<const float4*>(qr + qq * 8);
+}
+
+// One partial chain of S^T[key][query] = sum_d K[key][d] Q[query][d] over the Q fragments [Q0, Q1) (fp32 operands); ka points at this
+// lane's K row in LDS, at the channel of fragment 0.  The sum over an even number of 32-wide head-dim tiles is ALWAYS taken as
+// (d < DK / 2) + (d >= DK / 2): a split kernel runs one chain per wavefront and the pair adds them through LDS, a one-wavefront kernel
+// runs both chains itself and adds them -- so the two forms give the same bits and the launcher may pick by grid size (two independent
+// MFMA chains in the serial form, as a side effect).
+template <int Q0, int Q1, int NQ>
+__device__ __forceinline__ void att_qk_f32(f32x16& s, const float* ka, const float4 (&qf)[NQ]) {
+#pragma unroll
+  for (int qq = Q0; qq < Q1; ++qq) {
+    const float4 a = *reinterpret_cast<const float4*>(ka + qq * 8);
+    s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[qq].x, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[qq].y, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[qq].z, s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[qq].w, s, 0, 0, 0);
+  }
+}
+
+// Scale, key mask, online softmax of one 32-key chunk (per query = per lane, both lane halves hold the same query): s holds the raw
+// scores of keys key0 + (r & 3) + 8 (r >> 2) + 4 lh on entry and their probabilities P on return; keys >= limit are masked.  Returns the
+// factor by which the running sum and O shrink.  m_new is finite: every chunk a kernel walks has at least one key < limit.
+// EXACT: score / scale and expf (the fp32 kernels); otherwise score * scale and the hardware exp (the split-precision kernels pass
+// scale = 1 / temperature: a multiply and the hardware exp are within their error budget).
+template <bool EXACT>
+__device__ __forceinline__ float att_softmax_step(f32x16& s, const int key0, const int lh, const int limit, const float scale, float& m_run,
+                                                  float& l_run) {
+  float mx = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = key0 + ((r & 3) + 8 * (r >> 2) + 4 * lh);
+    float v = EXACT ? s[r] / scale : s[r] * scale;
+    v = key < limit ? v : -INFINITY;
+    s[r] = v;
+    mx = fmaxf(mx, v);
+  }
+  mx = fmaxf(mx, __shfl_xor(mx, 32));
+  const float m_new = fmaxf(m_run, mx);
+  const float corr = EXACT ? expf(m_run - m_new) : __expf(m_run - m_new);
+  float psum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const float pv = EXACT ? expf(s[r] - m_new) : __expf(s[r] - m_new);
+    s[r] = pv;
+    psum += pv;
+  }
+  psum += __shfl_xor(psum, 32);
+  l_run = l_run * corr + psum;
+  m_run = m_new;
+  return corr;
+}
+
+// O^T[d][query] = O^T * corr + sum_key V[key][d] P[key][query] on DT head-dim tiles, fp32 operands: vcol points at V[key 0][this lane's
+// channel of tile 0] in LDS (row stride LD); MFMA step r consumes the key pair {k0(r), k0(r) + 4} the lane halves hold in s[r].
+template <int DT, int LD>
+__device__ __forceinline__ void att_pv_f32(f32x16 (&o)[DT], const f32x16& s, const float corr, const float* vcol, const int lh) {
+#pragma unroll
+  for (int d = 0; d < DT; ++d) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[d][r] *= corr;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const float a = vcol[key * LD + d * 32];
+      o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[r], o[d], 0, 0, 0);
+    }
+  }
+}
+
+// A key segment ends (see ATT_SEG_CHUNKS): merge (o, m_run, l_run) into the total (ot, m_tot, l_tot) and start the next segment from
+// scratch.  The first segment IS the total so far: every merging kernel assigns here (no parked registers to fetch).
+template <int DT>
+__device__ __forceinline__ void att_segment_close(f32x16 (&o)[DT], float& m_run, float& l_run, f32x16 (&ot)[DT], float& m_tot, float& l_tot,
+                                                  const bool first) {
+  if (first) {
+#pragma unroll
+    for (int d = 0; d < DT; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[d][r] = o[d][r];
+    m_tot = m_run;
+    l_tot = l_run;
+  } else {
+    float ma, mb;
+    seg_merge_ml(m_tot, l_tot, m_run, l_run, ma, mb);
+#pragma unroll
+    for (int d = 0; d < DT; ++d)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ot[d][r] = seg_merge_o(ot[d][r], o[d][r], ma, mb);
+  }
+  att_clear(o);
+  m_run = -INFINITY;
+  l_run = 0.f;
+}
+
+// Epilogue: normalise by the softmax sum l and store one query's DT head-dim tiles.  O^T tile d: column = query (lane & 31), row =
+// head-dim offset (r & 3) + 8 (r >> 2) + 4 lh -> 4 x float4 per tile; orow points at this query's row, channel 4 lh of tile 0.  A padded
+// query (!valid) gets zeros.  Channels >= DK_BOUND (a head dim that is no multiple of 32) are not stored.
+template <int DT, int DK_BOUND>
+__device__ __forceinline__ void att_store_rows(const f32x16 (&o)[DT], const float l, const bool valid, float* __restrict__ orow, const int lh) {
+  const float inv = valid ? 1.0f / l : 0.f;
+#pragma unroll
+  for (int d = 0; d < DT; ++d)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (DK_BOUND % 32 == 0 || d * 32 + 8 * g + 4 * lh < DK_BOUND) {
+        float4 v;
+        v.x = valid ? o[d][4 * g + 0] * inv : 0.f;
+        v.y = valid ? o[d][4 * g + 1] * inv : 0.f;
+        v.z = valid ? o[d][4 * g + 2] * inv : 0.f;
+        v.w = valid ? o[d][4 * g + 3] * inv : 0.f;
+        *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
+      }
+    }
+}
+
 template <int DK>
 __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                         const int32_t* __restrict__ lens, int N, int H, float temperature, const RowMap rm) {
@@ -92,11 +234,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
   ATT_BLOCK_OF_GRID(128)
   const int q0 = qblk * 128 + wave * 32;
   const int len = min(lens ? lens[b] : N, N);
-  if (qblk * 128 >= len) {  // a tile of padded queries only: their rows are zero (padded grids; a compact grid has no such block)
-    for (int i = tid; i < 128 * (DK / 4); i += 256) {
-      const int q = qblk * 128 + i / (DK / 4);
-      if (q < N) *reinterpret_cast<float4*>(out + ((long long)b * N + q) * H + head * DK + (i % (DK / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  if (qblk * 128 >= len) {
+    att_zero_tile<128, 256, DK>(out, b, qblk, head, N, H, tid);
     return;
   }
   const int ld = 3 * H;
@@ -105,27 +244,15 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
   const float* kp = base + H + head * DK;
   const float* vp = base + 2 * H + head * DK;
 
-  // Q fragments: lane (query li, half lh) holds Q[q][8 qq + 4 lh + r]
   float4 qf[QQ];
-  {
-    const int qrow = min(q0 + li, N - 1);
-    const float* qr = qp + (long long)qrow * ld + lh * 4;
-#pragma unroll
-    for (int qq = 0; qq < QQ; ++qq) qf[qq] = *reinterpret_cast<const float4*>(qr + qq * 8);
-  }
+  att_load_q_f32(qf, qp + (long long)min(q0 + li, N - 1) * ld + lh * 4);
 
   f32x16 o[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
-  // (o, m_run, l_run) accumulate the current key segment, (ot, m_tot, l_tot) the merged segments before it -- attention_split_kernel's order
+  // (o, m_run, l_run) accumulate the current key segment, (ot, m_tot, l_tot) the merged segments before it
   f32x16 ot[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
+  att_clear(ot);
   float m_tot = -INFINITY, l_tot = 0.f;
 
   const int nchunks = (len + 31) / 32;
@@ -146,33 +273,22 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     }
     __syncthreads();
 
-    // S^T[key][query] = sum_d K[key][d] Q[query][d].  With an even number of 32-wide head-dim tiles the sum is taken as
-    // (d < DK / 2) + (d >= DK / 2): the order attention_split_kernel below produces with one wavefront per half, so the two kernels
-    // give the same bits and the launcher may pick by grid size (two independent MFMA chains here, as a side effect).
-    f32x16 s, s1;
+    f32x16 s;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f, s1[r] = 0.f;
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
     const float* ka = Ks + li * LDS_LD + lh * 4;
+    if constexpr (HALVES) {   // both half chains of att_qk_f32's order, here in one wavefront
+      f32x16 s1;
 #pragma unroll
-    for (int qq = 0; qq < QQ; ++qq) {
-      const float4 a = *reinterpret_cast<const float4*>(ka + qq * 8);
-      if (!HALVES || qq < QQ / 2) {
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[qq].x, s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[qq].y, s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[qq].z, s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[qq].w, s, 0, 0, 0);
-      } else {
-        s1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[qq].x, s1, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[qq].y, s1, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[qq].z, s1, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[qq].w, s1, 0, 0, 0);
-      }
-    }
-    if constexpr (HALVES) {
+      for (int r = 0; r < 16; ++r) s1[r] = 0.f;
+      att_qk_f32<0, QQ / 2>(s, ka, qf);
+      att_qk_f32<QQ / 2, QQ>(s1, ka, qf);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = s[r] + s1[r];
+    } else {
+      att_qk_f32<0, QQ>(s, ka, qf);
     }
-    // scale, key-padding mask, online softmax (per query = per lane, both lane halves hold the same query)
+    // att_softmax_step<true>(s, kc * 32, lh, len, temperature, m_run, l_run), kept inline: as a call it cost DK = 64 a wave of occupancy and DK = 192 ten more spilled registers
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -183,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
       mx = fmaxf(mx, v);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);  // finite: chunk kc has at least one valid key
+    const float m_new = fmaxf(m_run, mx);
     const float corr = expf(m_run - m_new);
     float psum = 0.f;
 #pragma unroll
@@ -195,67 +311,13 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
     psum += __shfl_xor(psum, 32);
     l_run = l_run * corr + psum;
     m_run = m_new;
-    // O^T[d][query] = O^T * corr + sum_key V[key][d] P[key][query]
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= corr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float a = Vs[key * LDS_LD + d * 32 + li];
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[r], o[d], 0, 0, 0);
-      }
-    }
+    att_pv_f32<DT, LDS_LD>(o, s, corr, Vs + li, lh);
   }
-    {   // the key segment ends (see ATT_SEG_CHUNKS): merge it, start the next from scratch
-      if (sg0 == 0) {   // the first segment is the total so far
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[d][r] = o[d][r];
-        m_tot = m_run;
-        l_tot = l_run;
-      } else {
-        float ma, mb;
-        seg_merge_ml(m_tot, l_tot, m_run, l_run, ma, mb);
-#pragma unroll
-        for (int d = 0; d < DT; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[d][r] = seg_merge_o(ot[d][r], o[d][r], ma, mb);
-      }
-#pragma unroll
-      for (int d = 0; d < DT; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-      m_run = -INFINITY;
-      l_run = 0.f;
-    }
+    att_segment_close(o, m_run, l_run, ot, m_tot, l_tot, sg0 == 0);
   }
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = ot[d][r];
-  l_run = l_tot;
 
-  // O^T tile d: column = query (lane & 31), row = head-dim offset (r & 3) + 8 (r >> 2) + 4 lh -> 4 x float4 per tile
   const int q = q0 + li;
-  if (q < N) {
-    const bool valid = q < len;
-    const float inv = valid ? 1.0f / l_run : 0.f;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 v;
-        v.x = valid ? o[d][4 * g + 0] * inv : 0.f;
-        v.y = valid ? o[d][4 * g + 1] * inv : 0.f;
-        v.z = valid ? o[d][4 * g + 2] * inv : 0.f;
-        v.w = valid ? o[d][4 * g + 3] * inv : 0.f;
-        *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-      }
-  }
+  if (q < N) att_store_rows<DT, DK>(ot, l_tot, q < len, out + ((long long)b * N + q) * H + head * DK + 4 * lh, lh);
 }
 
 // ---- the same attention for SMALL grids (B = 1: the latency path; small batches): two wavefronts per 32-query tile, each owning HALF of
@@ -264,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const float* __restri
 // 2 x DK / 2 dependent v_mfma_f32_32x32x2_f32 (192 at DK = 192: 12 k cycles = 5 us) -- and at B = 1, T = 768 only 48 wavefronts exist:
 // 24 chunks x 9 us = 225 us per decoder layer on 12 of 256 CUs.  Here the pair (w, w ^ 1) splits it: each computes the partial S^T over
 // its DK / 2 channels (Q fragments: half the registers), the two partial tiles meet in LDS and BOTH add them in the order
-// (d < DK / 2) + (d >= DK / 2) -- the order attention_kernel uses -- run the same softmax, and accumulate O^T for their own DK / 64
+// (d < DK / 2) + (d >= DK / 2) -- att_qk_f32's order -- run the same softmax, and accumulate O^T for their own DK / 64
 // head-dim tiles.  Same bits as attention_kernel, half the chain, twice the wavefronts; and with half the registers there is room to
 // request the next chunk's K / V rows before this chunk's arithmetic (the staging round trip was exposed once per chunk).
 template <int DK, int QT>
@@ -295,11 +357,8 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
   const int q0 = qblk * (QT * 32) + qt * 32;
   const int len = min(lens ? lens[b] : N, N);
   if (par_nseg > 0 && qblk * (QT * 32) >= len) return;   // attention_combine_kernel writes the zero rows
-  if (qblk * (QT * 32) >= len) {  // a tile of padded queries only: their rows are zero (padded grids)
-    for (int i = tid; i < QT * 32 * (DK / 4); i += NTH) {
-      const int q = qblk * (QT * 32) + i / (DK / 4);
-      if (q < N) *reinterpret_cast<float4*>(out + ((long long)b * N + q) * H + head * DK + (i % (DK / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  if (qblk * (QT * 32) >= len) {
+    att_zero_tile<QT * 32, NTH, DK>(out, b, qblk, head, N, H, tid);
     return;
   }
   const int ld = 3 * H;
@@ -309,17 +368,9 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
   const float* vp = base + 2 * H + head * DK;
 
   float4 qf[QQH];
-  {
-    const int qrow = min(q0 + li, N - 1);
-    const float* qr = qp + (long long)qrow * ld + lh * 4;
-#pragma unroll
-    for (int qq = 0; qq < QQH; ++qq) qf[qq] = *reinterpret_cast<const float4*>(qr + qq * 8);
-  }
+  att_load_q_f32(qf, qp + (long long)min(q0 + li, N - 1) * ld + lh * 4);
   f32x16 o[DTH];
-#pragma unroll
-  for (int d = 0; d < DTH; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
 
   float4 kreg[NLD], vreg[NLD];
@@ -355,10 +406,7 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
   const int kc_end = par_nseg > 0 ? min(nchunks, (seg_id + 1) * ATT_SEG_CHUNKS) : nchunks;
   if (kc_begin >= kc_end) return;   // a segment beyond this utterance's keys (uniform for the workgroup, before any barrier)
   f32x16 ot[DTH];
-#pragma unroll
-  for (int d = 0; d < DTH; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ot[d][r] = 0.f;
+  att_clear(ot);
   float m_tot = -INFINITY, l_tot = 0.f;
   fetch(kc_begin);
   // (two loops on purpose: the inner one never touches `ot`, so the register allocator may park the merged segments outside it -- as one
@@ -375,15 +423,8 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
-    const float* ka = Ks + li * LDS_LD + part * DH + lh * 4;
-#pragma unroll
-    for (int qq = 0; qq < QQH; ++qq) {
-      const float4 a = *reinterpret_cast<const float4*>(ka + qq * 8);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[qq].x, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[qq].y, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[qq].z, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[qq].w, s, 0, 0, 0);
-    }
+    att_qk_f32<0, QQH>(s, Ks + li * LDS_LD + part * DH + lh * 4, qf);
+    // the two partial tiles meet in LDS and BOTH wavefronts of the pair add them, (d < DK / 2) + (d >= DK / 2), and run the same softmax
 #pragma unroll
     for (int r = 0; r < 16; ++r) Sx[wave][r * 64 + lane] = s[r];
     lds_barrier();
@@ -393,64 +434,10 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = s0[r * 64 + lane] + s1[r * 64 + lane];
     }
-    // scale, key-padding mask, online softmax: as in attention_kernel, computed by both wavefronts of the pair
-    float mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = kc * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      float v = s[r] / temperature;
-      v = key < len ? v : -INFINITY;
-      s[r] = v;
-      mx = fmaxf(mx, v);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);
-    const float corr = expf(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = expf(s[r] - m_new);
-      s[r] = pv;
-      psum += pv;
-    }
-    psum += __shfl_xor(psum, 32);
-    l_run = l_run * corr + psum;
-    m_run = m_new;
-#pragma unroll
-    for (int d = 0; d < DTH; ++d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= corr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float a = Vs[key * LDS_LD + (part * DTH + d) * 32 + li];
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[r], o[d], 0, 0, 0);
-      }
-    }
+    const float corr = att_softmax_step<true>(s, kc * 32, lh, len, temperature, m_run, l_run);
+    att_pv_f32<DTH, LDS_LD>(o, s, corr, Vs + part * DH + li, lh);
   }
-    if (par_nseg == 0) {   // the segment ends: merge it, start the next one from scratch
-      if (sg0 == kc_begin) {   // the first segment IS the total so far (every merging kernel assigns here: no parked registers to fetch)
-#pragma unroll
-        for (int d = 0; d < DTH; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[d][r] = o[d][r];
-        m_tot = m_run;
-        l_tot = l_run;
-      } else {
-        float ma, mb;
-        seg_merge_ml(m_tot, l_tot, m_run, l_run, ma, mb);
-#pragma unroll
-        for (int d = 0; d < DTH; ++d)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) ot[d][r] = seg_merge_o(ot[d][r], o[d][r], ma, mb);
-      }
-#pragma unroll
-      for (int d = 0; d < DTH; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-      m_run = -INFINITY;
-      l_run = 0.f;
-    }
+    if (par_nseg == 0) att_segment_close(o, m_run, l_run, ot, m_tot, l_tot, sg0 == kc_begin);
   }
 
   const int q = q0 + li;
@@ -467,27 +454,13 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_split_kernel(const floa
     }
     return;
   }
+  // (copied back into `o` first: stored straight from `ot`, DK = 192 spilled nine more registers)
 #pragma unroll
   for (int d = 0; d < DTH; ++d)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[d][r] = ot[d][r];
   l_run = l_tot;
-  if (q < N) {
-    const bool valid = q < len;
-    const float inv = valid ? 1.0f / l_run : 0.f;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + part * DH + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DTH; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 v;
-        v.x = valid ? o[d][4 * g + 0] * inv : 0.f;
-        v.y = valid ? o[d][4 * g + 1] * inv : 0.f;
-        v.z = valid ? o[d][4 * g + 2] * inv : 0.f;
-        v.w = valid ? o[d][4 * g + 3] * inv : 0.f;
-        *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-      }
-  }
+  if (q < N) att_store_rows<DTH, DH>(o, l_run, q < len, out + ((long long)b * N + q) * H + head * DK + part * DH + 4 * lh, lh);
 }
 
 // Merges the key segments attention_split_kernel left in the workspace (par_nseg > 0): per (utterance, head, query) the segments in key
@@ -601,10 +574,7 @@ __global__ __launch_bounds__(256, 2) void rel_attention_kernel(const float* __re
   }
 
   f32x16 o[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
 
   // The band SLIDES: the next key chunk's band is this one's shifted by 32 table rows, so its first G^T tile (t < 32) is this chunk's
@@ -708,65 +678,13 @@ __global__ __launch_bounds__(256, 2) void rel_attention_kernel(const float* __re
     f32x16 s;   // the content scores accumulate on top of the position term (one array instead of two)
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = pterm[r];
-    const float* ka = Ks + li * LDS_LD + lh * 4;
-#pragma unroll
-    for (int qq = 0; qq < QQ; ++qq) {
-      const float4 a = *reinterpret_cast<const float4*>(ka + qq * 8);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, qf[qq].x, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, qf[qq].y, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, qf[qq].z, s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, qf[qq].w, s, 0, 0, 0);
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = j0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      float v = s[r] / temperature;
-      v = key < N ? v : -INFINITY;
-      s[r] = v;
-      mx = fmaxf(mx, v);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);  // finite: every chunk has a key < N
-    const float corr = expf(m_run - m_new);
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float pv = expf(s[r] - m_new);
-      s[r] = pv;
-      psum += pv;
-    }
-    psum += __shfl_xor(psum, 32);
-    l_run = l_run * corr + psum;
-    m_run = m_new;
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= corr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = (r & 3) + 8 * (r >> 2) + 4 * lh;
-        const float a = Vs[key * LDS_LD + d * 32 + li];
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, s[r], o[d], 0, 0, 0);
-      }
-    }
+    att_qk_f32<0, QQ>(s, Ks + li * LDS_LD + lh * 4, qf);
+    const float corr = att_softmax_step<true>(s, j0, lh, N, temperature, m_run, l_run);   // nothing is masked but the keys past N
+    att_pv_f32<DT, LDS_LD>(o, s, corr, Vs + li, lh);
   }
 
   const int q = i0 + li;
-  if (q < N) {
-    const float inv = 1.0f / l_run;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (d * 32 + 8 * g + 4 * lh < DK) {
-          float4 v;
-          v.x = o[d][4 * g + 0] * inv; v.y = o[d][4 * g + 1] * inv; v.z = o[d][4 * g + 2] * inv; v.w = o[d][4 * g + 3] * inv;
-          *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-        }
-      }
-  }
+  if (q < N) att_store_rows<DT, DK>(o, l_run, true, out + ((long long)b * N + q) * H + head * DK + 4 * lh, lh);   // padded queries are computed
 }
 
 // ---- split-precision ("bf16x3") form, for the decoder when its FFT blocks run in that arithmetic (the encoder keeps the
@@ -798,13 +716,94 @@ __device__ __forceinline__ void split8(const float* v, bf16x8_t& hi, bf16x8_t& l
   lo = __builtin_bit_cast(bf16x8_t, l);
 }
 
+// ---- the shared phases on split-precision operands (the fp32 ones are above the first kernel)
+constexpr int VS = 36;   // words per Vt row: 16 (32 hi slots) + 16 (32 lo slots) + 4 pad
+
+// Q fragments: lane (query li, half lh) holds Q[q][16 s + 8 lh .. + 7] for every k-step s, split once; qr points at Q[q][8 lh]
+template <int NS>
+__device__ __forceinline__ void att_load_q_x3(bf16x8_t (&qh)[NS], bf16x8_t (&ql)[NS], const float* __restrict__ qr) {
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    const float4 a = *reinterpret_cast<const float4*>(qr + s * 16), c = *reinterpret_cast<const float4*>(qr + s * 16 + 4);
+    const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+    split8(v, qh[s], ql[s]);
+  }
+}
+
+// One staged float4 pair of the split-precision kernels: K[key r][4 c4 .. + 3] and V[key r][4 c4 .. + 3] of a DK-wide head.
+// VROWS: physical Vt rows per residue of the head-dim row mod 4 (DK / 4, or a padded head dim's 8 ceil(DK / 32)).
+template <int DK, int VROWS>
+__device__ __forceinline__ void att_stage_kv_x3(unsigned* Kh, unsigned* Vt, const int r, const int c4, const float4 kv, const float4 vv) {
+  constexpr int KS = DK + 4;
+  // K row: [hi d 0 .. DK-1 | lo d 0 .. DK-1] as bf16
+  const unsigned k0 = pk_bf16(kv.x, kv.y), k1 = pk_bf16(kv.z, kv.w);
+  const float kx = __builtin_bit_cast(float, k0 << 16), ky = __builtin_bit_cast(float, k0 & 0xffff0000u);
+  const float kz = __builtin_bit_cast(float, k1 << 16), kw = __builtin_bit_cast(float, k1 & 0xffff0000u);
+  *reinterpret_cast<uint2*>(Kh + r * KS + c4 * 2) = make_uint2(k0, k1);
+  *reinterpret_cast<uint2*>(Kh + r * KS + DK / 2 + c4 * 2) = make_uint2(pk_bf16(kv.x - kx, kv.y - ky), pk_bf16(kv.z - kz, kv.w - kw));
+  // V transposed, key r -> slot: r = k(rr) + 4 h with rr = (r & 3) + 4 (r >> 3), h = (r >> 2) & 1; slot = 16 (rr >> 3) + 8 h + (rr & 7)
+  const int rr = (r & 3) + 4 * (r >> 3), h = (r >> 2) & 1;
+  const int slot = 16 * (rr >> 3) + 8 * h + (rr & 7);
+  // head-dim row d = 4 c4 + e lives at physical row (d & 3) VROWS + (d >> 2) = e VROWS + c4: consecutive lanes
+  // (consecutive c4) then write consecutive rows, 36 words apart.  Stored by row d they were 4 rows = 144 words = 16 banks apart.
+  unsigned short* vt = reinterpret_cast<unsigned short*>(Vt) + c4 * (VS * 2) + slot;
+  const float vs[4] = {vv.x, vv.y, vv.z, vv.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const __bf16 hb = (__bf16)vs[e];
+    const __bf16 lb = (__bf16)(vs[e] - (float)hb);
+    vt[e * VROWS * (VS * 2)] = __builtin_bit_cast(unsigned short, hb);
+    vt[e * VROWS * (VS * 2) + 32] = __builtin_bit_cast(unsigned short, lb);
+  }
+}
+
+// One partial chain of S^T = K . Q^T over the k-steps [S0, S1) (att_qk_f32's contract and summation order): ka points at this lane's
+// staged K row, at the hi words of k-step 0; the matching lo words are LO further.  A product keeps lo*hi + hi*lo + hi*hi.
+template <int S0, int S1, int LO, int NS>
+__device__ __forceinline__ void att_qk_x3(f32x16& s, const unsigned* ka, const bf16x8_t (&qh)[NS], const bf16x8_t (&ql)[NS]) {
+#pragma unroll
+  for (int ks = S0; ks < S1; ++ks) {
+    const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + ks * 8));
+    const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + LO + ks * 8));
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[ks], s, 0, 0, 0);
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[ks], s, 0, 0, 0);
+  }
+}
+
+// O^T[d][query] = O^T * corr + sum_key V[key][d] P[key][query] on DT head-dim tiles, split bf16 operands.  P fragments: k-step s2 takes
+// registers 8 s2 .. 8 s2 + 7 of s (their keys are what the Vt slots of that step hold).  The kernel's tiles are t0 .. t0 + DT - 1 of the
+// head dimension; PHYS: physical Vt rows per residue of the head-dim row mod 4 (att_stage_kv_x3's VROWS).
+template <int DT, int PHYS>
+__device__ __forceinline__ void att_pv_x3(f32x16 (&o)[DT], const f32x16& s, const float corr, const unsigned* Vt, const int t0, const int li, const int lh) {
+  float pv[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) pv[r] = s[r];
+  bf16x8_t ph[2], pl[2];
+  split8(pv, ph[0], pl[0]);
+  split8(pv + 8, ph[1], pl[1]);
+#pragma unroll
+  for (int d = 0; d < DT; ++d) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[d][r] *= corr;
+    const unsigned* va = Vt + ((li & 3) * PHYS + (t0 + d) * 8 + (li >> 2)) * VS + lh * 4;  // physical row of head-dim row (t0 + d) * 32 + li
+#pragma unroll
+    for (int s2 = 0; s2 < 2; ++s2) {
+      const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + s2 * 8));
+      const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + 16 + s2 * 8));
+      o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, ph[s2], o[d], 0, 0, 0);
+      o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, pl[s2], o[d], 0, 0, 0);
+      o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ph[s2], o[d], 0, 0, 0);
+    }
+  }
+}
+
 // NW: wavefronts (32 queries each) per workgroup.  Every workgroup of an (utterance, head) pulls ALL its K / V chunks through L2, and that
 // traffic, not arithmetic, is what the staging costs: 8 waves = 256 queries per workgroup halve it against 4.
 template <int DK, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                            const int32_t* __restrict__ lens, int N, int H, float temperature, const RowMap rm) {
   constexpr int KS = DK + 4;   // words per K row: DK/2 (hi bf16) + DK/2 (lo bf16) + 4 pad; KS mod 64 == 4 -> conflict-free b128
-  constexpr int VS = 36;       // words per Vt row: 16 (32 hi slots) + 16 (32 lo slots) + 4 pad
   constexpr int DT = DK / 32;  // 32-wide tiles of the head dimension
   constexpr int NS = DK / 16;  // k-steps of S^T = K . Q^T
   constexpr bool HALVES = DT % 2 == 0;
@@ -817,11 +816,8 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(const float* _
   ATT_BLOCK_OF_GRID(NW * 32)
   const int q0 = qblk * (NW * 32) + wave * 32;
   const int len = min(lens ? lens[b] : N, N);
-  if (qblk * (NW * 32) >= len) {  // a tile of padded queries only: their rows are zero (padded grids)
-    for (int i = tid; i < NW * 32 * (DK / 4); i += NW * 64) {
-      const int q = qblk * (NW * 32) + i / (DK / 4);
-      if (q < N) *reinterpret_cast<float4*>(out + ((long long)b * N + q) * H + head * DK + (i % (DK / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+  if (qblk * (NW * 32) >= len) {
+    att_zero_tile<NW * 32, NW * 64, DK>(out, b, qblk, head, N, H, tid);
     return;
   }
   const int ld = 3 * H;
@@ -830,26 +826,13 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(const float* _
   const float* kp = base + H + head * DK;
   const float* vp = base + 2 * H + head * DK;
 
-  // Q fragments: lane (query li, half lh) holds Q[q][16 s + 8 lh .. + 7] for every k-step s, split once
   bf16x8_t qh[NS], ql[NS];
-  {
-    const int qrow = min(q0 + li, N - 1);
-    const float* qr = qp + (long long)qrow * ld + lh * 8;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(qr + s * 16), c = *reinterpret_cast<const float4*>(qr + s * 16 + 4);
-      const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-      split8(v, qh[s], ql[s]);
-    }
-  }
+  att_load_q_x3(qh, ql, qp + (long long)min(q0 + li, N - 1) * ld + lh * 8);
 
   f32x16 o[DT];
-#pragma unroll
-  for (int d = 0; d < DT; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
-  const float inv_temp = 1.0f / temperature;  // split-precision path: a multiply and the hardware exp are within its error budget
+  const float inv_temp = 1.0f / temperature;
 
   const int nchunks = (len + 31) / 32;
   for (int kc = 0; kc < nchunks; ++kc) {
@@ -862,115 +845,31 @@ __global__ __launch_bounds__(NW * 64, 2) void attention_x3_kernel(const float* _
         kv = *reinterpret_cast<const float4*>(kp + (key * ld + c4 * 4));
         vv = *reinterpret_cast<const float4*>(vp + (key * ld + c4 * 4));
       }
-      // K row: [hi d 0 .. DK-1 | lo d 0 .. DK-1] as bf16
-      const unsigned k0 = pk_bf16(kv.x, kv.y), k1 = pk_bf16(kv.z, kv.w);
-      const float kx = __builtin_bit_cast(float, k0 << 16), ky = __builtin_bit_cast(float, k0 & 0xffff0000u);
-      const float kz = __builtin_bit_cast(float, k1 << 16), kw = __builtin_bit_cast(float, k1 & 0xffff0000u);
-      *reinterpret_cast<uint2*>(Kh + r * KS + c4 * 2) = make_uint2(k0, k1);
-      *reinterpret_cast<uint2*>(Kh + r * KS + DK / 2 + c4 * 2) = make_uint2(pk_bf16(kv.x - kx, kv.y - ky), pk_bf16(kv.z - kz, kv.w - kw));
-      // V transposed, key r -> slot: r = k(rr) + 4 h with rr = (r & 3) + 4 (r >> 3), h = (r >> 2) & 1; slot = 16 (rr >> 3) + 8 h + (rr & 7)
-      const int rr = (r & 3) + 4 * (r >> 3), h = (r >> 2) & 1;
-      const int slot = 16 * (rr >> 3) + 8 * h + (rr & 7);
-      // head-dim row d = 4 c4 + e lives at physical row (d & 3) (DK / 4) + (d >> 2) = e (DK / 4) + c4: consecutive lanes
-      // (consecutive c4) then write consecutive rows, 36 words apart.  Stored by row d they were 4 rows = 144 words = 16 banks apart.
-      unsigned short* vt = reinterpret_cast<unsigned short*>(Vt) + c4 * (VS * 2) + slot;
-      const float vs[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = (__bf16)vs[e];
-        const __bf16 lb = (__bf16)(vs[e] - (float)hb);
-        vt[e * (DK / 4) * (VS * 2)] = __builtin_bit_cast(unsigned short, hb);
-        vt[e * (DK / 4) * (VS * 2) + 32] = __builtin_bit_cast(unsigned short, lb);
-      }
+      att_stage_kv_x3<DK, DK / 4>(Kh, Vt, r, c4, kv, vv);
     }
     __syncthreads();
 
-    // S^T[key][query] = sum_d K[key][d] Q[query][d]
-    // (with an even number of head-dim tiles: as (d < DK / 2) + (d >= DK / 2), the order of attention_x3_split_kernel -- see the fp32 kernels)
-    f32x16 s, s1;
+    f32x16 s;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) s[r] = 0.f, s1[r] = 0.f;
+    for (int r = 0; r < 16; ++r) s[r] = 0.f;
     const unsigned* ka = Kh + li * KS + lh * 4;
+    if constexpr (HALVES) {   // both half chains of att_qk_x3's order, here in one wavefront
+      f32x16 s1;
 #pragma unroll
-    for (int ks = 0; ks < NS; ++ks) {
-      const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + ks * 8));
-      const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + DK / 2 + ks * 8));
-      if (!HALVES || ks < NS / 2) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[ks], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[ks], s, 0, 0, 0);
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[ks], s, 0, 0, 0);
-      } else {
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[ks], s1, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[ks], s1, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[ks], s1, 0, 0, 0);
-      }
-    }
-    if constexpr (HALVES) {
+      for (int r = 0; r < 16; ++r) s1[r] = 0.f;
+      att_qk_x3<0, NS / 2, DK / 2>(s, ka, qh, ql);
+      att_qk_x3<NS / 2, NS, DK / 2>(s1, ka, qh, ql);
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = s[r] + s1[r];
+    } else {
+      att_qk_x3<0, NS, DK / 2>(s, ka, qh, ql);
     }
-    // scale, key-padding mask, online softmax (per query = per lane, both lane halves hold the same query)
-    float mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = kc * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      float v = s[r] * inv_temp;
-      v = key < len ? v : -INFINITY;
-      s[r] = v;
-      mx = fmaxf(mx, v);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);  // finite: chunk kc has at least one valid key
-    const float corr = __expf(m_run - m_new);
-    float psum = 0.f;
-    float pv[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      pv[r] = __expf(s[r] - m_new);
-      psum += pv[r];
-    }
-    psum += __shfl_xor(psum, 32);
-    l_run = l_run * corr + psum;
-    m_run = m_new;
-    // P fragments: k-step s2 takes registers 8 s2 .. 8 s2 + 7 (their keys are what the Vt slots of that step hold)
-    bf16x8_t ph[2], pl[2];
-    split8(pv, ph[0], pl[0]);
-    split8(pv + 8, ph[1], pl[1]);
-    // O^T[d][query] = O^T * corr + sum_key V[key][d] P[key][query]
-#pragma unroll
-    for (int d = 0; d < DT; ++d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= corr;
-      const unsigned* va = Vt + ((li & 3) * (DK / 4) + d * 8 + (li >> 2)) * VS + lh * 4;  // physical row of head-dim row d * 32 + li
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + s2 * 8));
-        const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + 16 + s2 * 8));
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, ph[s2], o[d], 0, 0, 0);
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, pl[s2], o[d], 0, 0, 0);
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ph[s2], o[d], 0, 0, 0);
-      }
-    }
+    const float corr = att_softmax_step<false>(s, kc * 32, lh, len, inv_temp, m_run, l_run);
+    att_pv_x3<DT, DK / 4>(o, s, corr, Vt, 0, li, lh);
   }
 
-  // O^T tile d: column = query (lane & 31), row = head-dim offset (r & 3) + 8 (r >> 2) + 4 lh -> 4 x float4 per tile
   const int q = q0 + li;
-  if (q < N) {
-    const bool valid = q < len;
-    const float inv = valid ? 1.0f / l_run : 0.f;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DT; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 v;
-        v.x = valid ? o[d][4 * g + 0] * inv : 0.f;
-        v.y = valid ? o[d][4 * g + 1] * inv : 0.f;
-        v.z = valid ? o[d][4 * g + 2] * inv : 0.f;
-        v.w = valid ? o[d][4 * g + 3] * inv : 0.f;
-        *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-      }
-  }
+  if (q < N) att_store_rows<DT, DK>(o, l_run, q < len, out + ((long long)b * N + q) * H + head * DK + 4 * lh, lh);
 }
 
 // ---- Conformer relative-position attention in split precision (the decoder when its GEMMs run in bf16x3): rel_attention_kernel's
@@ -984,7 +883,6 @@ __global__ __launch_bounds__(256, 2) void rel_attention_x3_kernel(const float* _
                                                                   float* __restrict__ out, int N, int H, float temperature) {
   static_assert(DK % 16 == 0, "head dim must be a multiple of 16");
   constexpr int KS = DK + 4;            // words per K / band row: DK/2 (hi bf16) + DK/2 (lo bf16) + 4 pad
-  constexpr int VS = 36;                // words per Vt row: 16 (32 hi slots) + 16 (32 lo slots) + 4 pad
   constexpr int DTP = (DK + 31) / 32;   // 32-wide tiles of the (padded) head dimension
   constexpr int NS = DK / 16;           // k-steps over the head dimension
   constexpr int GLD = 68;               // rel_attention_kernel's exchange layout: [query a][t 0..63], 64 + 4
@@ -1024,10 +922,7 @@ __global__ __launch_bounds__(256, 2) void rel_attention_x3_kernel(const float* _
   load_frag(qi, vb, xh, xl);
 
   f32x16 o[DTP];
-#pragma unroll
-  for (int d = 0; d < DTP; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
   const float inv_temp = 1.0f / temperature;
 
@@ -1092,25 +987,9 @@ __global__ __launch_bounds__(256, 2) void rel_attention_x3_kernel(const float* _
         kv = *reinterpret_cast<const float4*>(kp + (key * ld + c4 * 4));
         vv = *reinterpret_cast<const float4*>(vp + (key * ld + c4 * 4));
       }
-      // K row: [hi d 0 .. DK-1 | lo d 0 .. DK-1] as bf16 (attention_x3_kernel's staging)
-      const unsigned k0 = pk_bf16(kv.x, kv.y), k1 = pk_bf16(kv.z, kv.w);
-      const float kx = __builtin_bit_cast(float, k0 << 16), ky = __builtin_bit_cast(float, k0 & 0xffff0000u);
-      const float kz = __builtin_bit_cast(float, k1 << 16), kw = __builtin_bit_cast(float, k1 & 0xffff0000u);
-      *reinterpret_cast<uint2*>(Kh + r * KS + c4 * 2) = make_uint2(k0, k1);
-      *reinterpret_cast<uint2*>(Kh + r * KS + DK / 2 + c4 * 2) = make_uint2(pk_bf16(kv.x - kx, kv.y - ky), pk_bf16(kv.z - kz, kv.w - kw));
-      // V transposed, key r -> slot (attention_x3_kernel); head-dim row d = 4 c4 + e at physical row (d & 3) (8 DTP) + (d >> 2): the
-      // padded rows DK .. 32 DTP - 1 get rows of their own, which nobody writes and whose products land in output rows nobody stores
-      const int rr = (r & 3) + 4 * (r >> 3), h = (r >> 2) & 1;
-      const int slot = 16 * (rr >> 3) + 8 * h + (rr & 7);
-      unsigned short* vt = reinterpret_cast<unsigned short*>(Vt) + c4 * (VS * 2) + slot;
-      const float vs[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const __bf16 hb = (__bf16)vs[e];
-        const __bf16 lb = (__bf16)(vs[e] - (float)hb);
-        vt[e * (8 * DTP) * (VS * 2)] = __builtin_bit_cast(unsigned short, hb);
-        vt[e * (8 * DTP) * (VS * 2) + 32] = __builtin_bit_cast(unsigned short, lb);
-      }
+      // head-dim row d = 4 c4 + e at physical row (d & 3) (8 DTP) + (d >> 2): the padded rows DK .. 32 DTP - 1 get rows of their own,
+      // which nobody writes and whose products land in output rows nobody stores
+      att_stage_kv_x3<DK, 8 * DTP>(Kh, Vt, r, c4, kv, vv);
     }
     float pterm[16];
     if (j0 <= i0) {         // lower form (see rel_attention_kernel)
@@ -1142,6 +1021,9 @@ __global__ __launch_bounds__(256, 2) void rel_attention_x3_kernel(const float* _
     f32x16 s;   // the content scores accumulate on top of the position term
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = pterm[r];
+    // The three in-loop phases stay inline in this kernel -- att_qk_x3<0, NS, DK / 2>(s, ka, fh, fl), att_softmax_step<false>(s, j0, lh, N,
+    // inv_temp, m_run, l_run) and att_pv_x3<DTP, 8 * DTP>(o, s, corr, Vt, 0, li, lh): it sits at 256 registers with spills at DK = 64 and
+    // 96, and every combination of calls tried added spills at one of the two.
     const unsigned* ka = Kh + li * KS + lh * 4;
 #pragma unroll
     for (int ks = 0; ks < NS; ++ks) {
@@ -1193,20 +1075,7 @@ __global__ __launch_bounds__(256, 2) void rel_attention_x3_kernel(const float* _
   }
 
   const int q = i0 + li;
-  if (q < N) {
-    const float inv = 1.0f / l_run;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DTP; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (d * 32 + 8 * g + 4 * lh < DK) {
-          float4 v;
-          v.x = o[d][4 * g + 0] * inv; v.y = o[d][4 * g + 1] * inv; v.z = o[d][4 * g + 2] * inv; v.w = o[d][4 * g + 3] * inv;
-          *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-        }
-      }
-  }
+  if (q < N) att_store_rows<DTP, DK>(o, l_run, true, out + ((long long)b * N + q) * H + head * DK + 4 * lh, lh);
 }
 
 // ---- split-precision attention for small grids: attention_split_kernel's arrangement (two wavefronts per 32-query tile, half the head
@@ -1216,7 +1085,6 @@ template <int DK, int QT>
 __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const float* __restrict__ qkv, float* __restrict__ out,
                                                                     const int32_t* __restrict__ lens, int N, int H, float temperature, const RowMap rm) {
   constexpr int KS = DK + 4;
-  constexpr int VS = 36;
   constexpr int DH = DK / 2, DTH = DH / 32, NSH = DH / 16;
   static_assert(DK % 64 == 0, "the split form needs an even number of 32-wide head-dim tiles");
   constexpr int NF4 = 32 * (DK / 4);
@@ -1233,10 +1101,7 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
   const int q0 = qblk * (QT * 32) + qt * 32;
   const int len = min(lens ? lens[b] : N, N);
   if (qblk * (QT * 32) >= len) {
-    for (int i = tid; i < QT * 32 * (DK / 4); i += NTH) {
-      const int q = qblk * (QT * 32) + i / (DK / 4);
-      if (q < N) *reinterpret_cast<float4*>(out + ((long long)b * N + q) * H + head * DK + (i % (DK / 4)) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    att_zero_tile<QT * 32, NTH, DK>(out, b, qblk, head, N, H, tid);
     return;
   }
   const int ld = 3 * H;
@@ -1246,21 +1111,9 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
   const float* vp = base + 2 * H + head * DK;
 
   bf16x8_t qh[NSH], ql[NSH];
-  {
-    const int qrow = min(q0 + li, N - 1);
-    const float* qr = qp + (long long)qrow * ld + lh * 8;
-#pragma unroll
-    for (int s = 0; s < NSH; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(qr + s * 16), c = *reinterpret_cast<const float4*>(qr + s * 16 + 4);
-      const float v[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
-      split8(v, qh[s], ql[s]);
-    }
-  }
+  att_load_q_x3(qh, ql, qp + (long long)min(q0 + li, N - 1) * ld + lh * 8);
   f32x16 o[DTH];
-#pragma unroll
-  for (int d = 0; d < DTH; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+  att_clear(o);
   float m_run = -INFINITY, l_run = 0.f;
   const float inv_temp = 1.0f / temperature;
 
@@ -1275,7 +1128,7 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
       vreg[i] = *reinterpret_cast<const float4*>(vp + (long long)key * ld + c4 * 4);
     }
   };
-  auto stash = [&](int kc) __attribute__((always_inline)) {  // attention_x3_kernel's staging, from the registers
+  auto stash = [&](int kc) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
       const int idx = tid + i * NTH;
@@ -1284,22 +1137,7 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
         const bool ok = kc * 32 + r < N;
         const float4 kv = make_float4(ok ? kreg[i].x : 0.f, ok ? kreg[i].y : 0.f, ok ? kreg[i].z : 0.f, ok ? kreg[i].w : 0.f);
         const float4 vv = make_float4(ok ? vreg[i].x : 0.f, ok ? vreg[i].y : 0.f, ok ? vreg[i].z : 0.f, ok ? vreg[i].w : 0.f);
-        const unsigned k0 = pk_bf16(kv.x, kv.y), k1 = pk_bf16(kv.z, kv.w);
-        const float kx = __builtin_bit_cast(float, k0 << 16), ky = __builtin_bit_cast(float, k0 & 0xffff0000u);
-        const float kz = __builtin_bit_cast(float, k1 << 16), kw = __builtin_bit_cast(float, k1 & 0xffff0000u);
-        *reinterpret_cast<uint2*>(Kh + r * KS + c4 * 2) = make_uint2(k0, k1);
-        *reinterpret_cast<uint2*>(Kh + r * KS + DK / 2 + c4 * 2) = make_uint2(pk_bf16(kv.x - kx, kv.y - ky), pk_bf16(kv.z - kz, kv.w - kw));
-        const int rr = (r & 3) + 4 * (r >> 3), h = (r >> 2) & 1;
-        const int slot = 16 * (rr >> 3) + 8 * h + (rr & 7);
-        unsigned short* vt = reinterpret_cast<unsigned short*>(Vt) + c4 * (VS * 2) + slot;
-        const float vs[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const __bf16 hb = (__bf16)vs[e];
-          const __bf16 lb = (__bf16)(vs[e] - (float)hb);
-          vt[e * (DK / 4) * (VS * 2)] = __builtin_bit_cast(unsigned short, hb);
-          vt[e * (DK / 4) * (VS * 2) + 32] = __builtin_bit_cast(unsigned short, lb);
-        }
+        att_stage_kv_x3<DK, DK / 4>(Kh, Vt, r, c4, kv, vv);
       }
     }
   };
@@ -1315,15 +1153,8 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
     f32x16 s;
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
-    const unsigned* ka = Kh + li * KS + part * (DH / 2) + lh * 4;   // this half's hi words; its lo words are DK / 2 further
-#pragma unroll
-    for (int ks = 0; ks < NSH; ++ks) {
-      const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + ks * 8));
-      const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(ka + DK / 2 + ks * 8));
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, qh[ks], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ql[ks], s, 0, 0, 0);
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, qh[ks], s, 0, 0, 0);
-    }
+    // this half's hi words; its lo words are DK / 2 further
+    att_qk_x3<0, NSH, DK / 2>(s, Kh + li * KS + part * (DH / 2) + lh * 4, qh, ql);
 #pragma unroll
     for (int r = 0; r < 16; ++r) Sx[wave][r * 64 + lane] = s[r];
     lds_barrier();
@@ -1333,64 +1164,12 @@ __global__ __launch_bounds__(QT * 128, 2) void attention_x3_split_kernel(const f
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[r] = s0[r * 64 + lane] + s1[r * 64 + lane];
     }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = kc * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      float v = s[r] * inv_temp;
-      v = key < len ? v : -INFINITY;
-      s[r] = v;
-      mx = fmaxf(mx, v);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m_run, mx);
-    const float corr = __expf(m_run - m_new);
-    float psum = 0.f;
-    float pv[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      pv[r] = __expf(s[r] - m_new);
-      psum += pv[r];
-    }
-    psum += __shfl_xor(psum, 32);
-    l_run = l_run * corr + psum;
-    m_run = m_new;
-    bf16x8_t ph[2], pl[2];
-    split8(pv, ph[0], pl[0]);
-    split8(pv + 8, ph[1], pl[1]);
-#pragma unroll
-    for (int d = 0; d < DTH; ++d) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) o[d][r] *= corr;
-      const unsigned* va = Vt + ((li & 3) * (DK / 4) + (part * DTH + d) * 8 + (li >> 2)) * VS + lh * 4;
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8_t ah = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + s2 * 8));
-        const bf16x8_t al = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(va + 16 + s2 * 8));
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, ph[s2], o[d], 0, 0, 0);
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, pl[s2], o[d], 0, 0, 0);
-        o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ph[s2], o[d], 0, 0, 0);
-      }
-    }
+    const float corr = att_softmax_step<false>(s, kc * 32, lh, len, inv_temp, m_run, l_run);
+    att_pv_x3<DTH, DK / 4>(o, s, corr, Vt, part * DTH, li, lh);
   }
 
   const int q = q0 + li;
-  if (q < N) {
-    const bool valid = q < len;
-    const float inv = valid ? 1.0f / l_run : 0.f;
-    float* orow = out + ((long long)b * N + q) * H + head * DK + part * DH + 4 * lh;
-#pragma unroll
-    for (int d = 0; d < DTH; ++d)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 v;
-        v.x = valid ? o[d][4 * g + 0] * inv : 0.f;
-        v.y = valid ? o[d][4 * g + 1] * inv : 0.f;
-        v.z = valid ? o[d][4 * g + 2] * inv : 0.f;
-        v.w = valid ? o[d][4 * g + 3] * inv : 0.f;
-        *reinterpret_cast<float4*>(orow + d * 32 + 8 * g) = v;
-      }
-  }
+  if (q < N) att_store_rows<DTH, DH>(o, l_run, q < len, out + ((long long)b * N + q) * H + head * DK + part * DH + 4 * lh, lh);
 }
 
 }  // namespace

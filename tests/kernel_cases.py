@@ -103,7 +103,9 @@ CONV_BY_NAME = {c["name"]: c for c in CONV_CASES}
 assert len(CONV_BY_NAME) == len(CONV_CASES)
 
 ALL_CONV_CLASSES = {f"conv_{m}_{t}" for m in ("gemm", "x3") for t in ("256x32", "256x64", "64x64", "64x128", "128x128")}
-ENV_OF = {"wg1": {"E2ETTS_WG_PER_CU": "1"}, "frag64": {"E2ETTS_FRAG64": "0"}}
+# att_serial: the launcher never takes the split attention kernels, so the head dims that have a split form run on attention_kernel<dk> /
+# attention_x3_kernel<dk, 8> (test_attention_serial_form_gives_the_split_forms_bits)
+ENV_OF = {"wg1": {"E2ETTS_WG_PER_CU": "1"}, "frag64": {"E2ETTS_FRAG64": "0"}, "att_serial": {"E2ETTS_ATT_SPLIT_MAX": "0"}}
 
 
 def modes_of(c):
@@ -226,6 +228,8 @@ ATT_CASES = [
     _att("b40_n257_dk64", 40, 257, 4, 64, [257 - 6 * i for i in range(40)]),     # x3: 5 * 4 * 40 = 800 > 512 workgroups -> attention_x3_kernel<64, 8>
     _att("b40_n65_dk128_host", 40, 65, 8, 128, [(7 * i) % 66 for i in range(40)], host=True),
 ]
+
+ATT_SPLIT_DK = (64, 128, 192)   # the head dims at which launch_attention has a split form
 
 # ---- rel_attention: (name, B, N, n_head, dk, pos_rows); run with and without pos_x3 where the split form has the head dim
 REL_CASES = [

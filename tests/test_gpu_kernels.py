@@ -18,6 +18,7 @@ from dyadic grids whose partial sums are exact in float32 in any order -- the ou
 element.  General tier: Gaussian data under an interval rule (each output between the epilogue of ref - bar and of ref + bar, no element
 excluded) and an aggregate rule (the share of elements that differ from the epilogue of fl32(ref), against 4 x the float32 yardstick's
 share plus one element).  The fused forms are tied to that reference bit for bit: pair = two convolutions, rb = three pairs, stage = rb's."""
+import hashlib
 import json
 import os
 import subprocess
@@ -284,7 +285,7 @@ def test_attention(kh, c):
             assert guard_ok and qkv.unchanged() and (ws is None or ws.fetch()[1])
             ok, worst = kr.check_att(got, o, W, dev, valid)
             print(f"attention {c['name']} x3={x3} ws={use_ws}: float32 deviation {dev:.3g} (relative to sum p |v|), worst err/bar {worst:.3g}")
-            record("attention", case=c["name"], x3=x3, ws=use_ws, dev=dev, elem=worst)
+            record("attention", case=c["name"], x3=x3, ws=use_ws, dev=dev, elem=worst, sha=hashlib.sha256(got.tobytes()).hexdigest()[:16])
             assert ok, (c["name"], x3, use_ws, worst)
             assert np.all(got[zero] == 0), "query rows >= lens[b] must be written as 0"
             assert np.all(got[keep] == SENTINEL), "query rows past the last block must keep their contents under lens_host"
@@ -294,6 +295,51 @@ def test_attention(kh, c):
         if len(outs) == 2:
             assert N > 32 * 8, "the workspace cases have at least two key segments"
             assert np.all(bits_equal(outs[0], outs[1])), "parallel key segments differ from the in-register merge: kernels.h promises the same bits"
+
+
+def att_outputs_without_workspace(kh):
+    """{"<case>/<x3>": out [B, N, H]} of every ATT_CASES entry at a head dim that has a split form, in both precisions, without workspace."""
+    outs = {}
+    for c in kc.ATT_CASES:
+        if c["dk"] not in kc.ATT_SPLIT_DK:
+            continue
+        B, N, nh, dk = c["B"], c["N"], c["n_head"], c["dk"]
+        qkv = Guarded(kr.att_data(c)["qkv"])
+        lens = i32(c["lens"]) if c["lens"] is not None else None
+        for x3 in (0, 1):
+            out = Guarded(shape=(B, N, nh * dk), sentinel=SENTINEL)
+            msg = kh.attention(qkv.ptr, out.ptr, lens.data_ptr() if lens is not None else None, B, N, nh * dk, nh, x3,
+                               lens_host=c["lens"] if c["host"] else None, ws=None, ws_bytes=0)
+            assert msg is None, msg
+            got, guard_ok = out.fetch()
+            assert guard_ok and qkv.unchanged(), (c["name"], x3)
+            outs[f"{c['name']}/{x3}"] = got
+    return outs
+
+
+def test_attention_serial_form_gives_the_split_forms_bits(kh, tmp_path):
+    """Per head dimension and per precision: the split form (two wavefronts per query tile, half the head dimension each; what the launcher
+    takes by default) and the one-wavefront form (attention_kernel<dk>, attention_x3_kernel<dk, 8>) give the same bits on every query row
+    < lens[b], and both write 0 on the rows that must be 0.  The one-wavefront form is read once per process (E2ETTS_ATT_SPLIT_MAX=0), so a
+    child runs it and hands its outputs over in a file.  (b40_n257_dk64 in split precision is above the launcher's grid limit and takes the
+    one-wavefront form in this process too: that comparison is trivial.)"""
+    mine = att_outputs_without_workspace(kh)
+    path = str(tmp_path / "att_serial.npz")
+    env = dict(os.environ, **kc.ENV_OF["att_serial"])
+    rr = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "att_serial", path], env=env, capture_output=True, text=True, timeout=600)
+    assert rr.returncode == 0, (rr.stdout[-3000:], rr.stderr[-3000:])
+    assert "child att_serial ok" in rr.stdout
+    theirs = np.load(path)
+    assert sorted(theirs.files) == sorted(mine) and len(mine) == 2 * sum(c["dk"] in kc.ATT_SPLIT_DK for c in kc.ATT_CASES)
+    assert {c["dk"] for c in kc.ATT_CASES} >= set(kc.ATT_SPLIT_DK)
+    for c in kc.ATT_CASES:
+        if c["dk"] not in kc.ATT_SPLIT_DK:
+            continue
+        valid, zero, _ = att_rows(c)
+        for x3 in (0, 1):
+            split, serial = mine[f"{c['name']}/{x3}"], theirs[f"{c['name']}/{x3}"]
+            assert np.all(bits_equal(split[valid], serial[valid])), f"{c['name']} x3 = {x3}: the one-wavefront form differs from the split form"
+            assert np.all(split[zero] == 0) and np.all(serial[zero] == 0), f"{c['name']} x3 = {x3}: query rows >= lens[b] must be written as 0"
 
 
 @pytest.mark.parametrize("c", kc.REL_CASES, ids=lambda c: c["name"])
@@ -313,7 +359,7 @@ def test_rel_attention(kh, c):
         assert guard_ok and all(g.unchanged() for g in (qkv, pos, u, v)) and (px is None or px.unchanged())
         ok, worst = kr.check_att(got, o, W, dev)
         print(f"rel_attention {c['name']} x3={x3}: float32 deviation {dev:.3g}, worst err/bar {worst:.3g}")
-        record("rel_attention", case=c["name"], x3=int(x3), dev=dev, elem=worst)
+        record("rel_attention", case=c["name"], x3=int(x3), dev=dev, elem=worst, sha=hashlib.sha256(got.tobytes()).hexdigest()[:16])
         assert ok, (c["name"], x3, worst)
 
 
@@ -1059,14 +1105,17 @@ def test_wall_time_is_recorded():
     record("wall", seconds=time.time() - _T0)
 
 
-# ---------------------------------------------------------------- child process of test_conv_gemm_env_variants_in_a_child_process
+# ---------------------------------------------------------------- child process of test_conv_gemm_env_variants_in_a_child_process and of
+# test_attention_serial_form_gives_the_split_forms_bits
 if __name__ == "__main__":
-    assert len(sys.argv) == 3 and sys.argv[1] == "--child" and sys.argv[2] in kc.ENV_OF
+    assert len(sys.argv) in (3, 4) and sys.argv[1] == "--child" and sys.argv[2] in kc.ENV_OF
     group = sys.argv[2]
     for k, v in kc.ENV_OF[group].items():
         assert os.environ.get(k) == v, f"{k} must be set before the library reads it"
     import kernel_harness
     kernel_harness.load()
+    if group == "att_serial":   # test_attention_serial_form_gives_the_split_forms_bits: the outputs go to the file named last
+        np.savez(sys.argv[3], **att_outputs_without_workspace(kernel_harness))
     for case in kc.CONV_CASES:
         if case["env"] == group:
             conv_case_body(kernel_harness, case)
