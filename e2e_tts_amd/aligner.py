@@ -17,14 +17,15 @@ from ._lib import _addr, _expect, _is_cuda
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align.so")
-# the TEST build of the same source (-DE2EALIGN_TEST_HOOKS: two more exports, e2ealign_debug_poison_workspace and e2ealign_debug_attention), loaded instead of the product
+# the TEST build of the same source (-DE2EALIGN_TEST_HOOKS: the e2ealign_debug_* exports of the header), loaded instead of the product
 # library only when E2ETTS_TEST_HOOKS=1 is in the environment (_companion.load)
 TEST_LIB_PATH = os.path.join(_HERE, "lib", "libe2etts_align_test.so")
-ABI_VERSION = 1   # E2EALIGN_ABI_VERSION of the include/e2etts_align.h this binding mirrors
+ABI_VERSION = 2   # E2EALIGN_ABI_VERSION of the include/e2etts_align.h this binding mirrors
 LOG_MAP = 1       # E2EALIGN_LOG_MAP
 MAX_ATT, MAX_L, MAX_B = 128, 2048, 4096
+MAX_PRIOR_SCALING = 1048576.0   # E2EALIGN_MAX_PRIOR_SCALING
 
-_P, _I, _F, _SZ = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+_P, _I, _F, _SZ, _D = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_double
 # every entry point include/e2etts_align.h declares, and all the library exports (tests/test_aligner_host.py compares the three):
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -41,11 +42,15 @@ SIGNATURES = {
     "e2ealign_forward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "e2ealign_mas": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
     "e2ealign_align": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "e2ealign_prior": (_I, [_P, _P, _P, _I, _I, _I, _D, _P]),
+    "e2ealign_forward_bb": (_I, [_P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P]),
+    "e2ealign_align_bb": (_I, [_P, _P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P, _P, _P]),
     "e2ealign_profile_enable": (_I, [_P, _I]),
     "e2ealign_profile_read": (_I, [_P, C.POINTER(C.c_double)]),
 }
 HOOK_SIGNATURES = {"e2ealign_debug_poison_workspace": (_I, [_P]),
-                   "e2ealign_debug_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P])}
+                   "e2ealign_debug_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+                   "e2ealign_debug_attention_bb": (_I, [_P, _P, _P, _P, _P, _D, _I, _I, _I, _P, _P])}
 EXPORTED_SYMBOLS = list(SIGNATURES)
 TEST_HOOK_SYMBOLS = list(HOOK_SIGNATURES)
 
@@ -113,15 +118,46 @@ class Aligner(_companion.CompanionHandle):
         _expect(x, name, "int64", B)
         return x
 
-    def forward(self, mel, keys, speaker=None, txt_lens=None, prior=None, out_attn=None, out_logprob=None, want=("attn", "attn_logprob")):
-        """mel [B, T, n_mel] (channels-last), keys [B, L, n_text], speaker [B, n_text] | None, txt_lens [B] | None, prior [B, T, L] | None
+    @staticmethod
+    def _device_prior(prior, txt_lens, mel_lens) -> bool:
+        """True for ``prior="device"`` (the beta-binomial prior generated inside the attention pass), which needs both length arrays."""
+        if not isinstance(prior, str):
+            return False
+        if prior != "device":
+            raise ValueError(f"prior must be None, a [B, T, L] array, or 'device' (got {prior!r})")
+        if txt_lens is None or mel_lens is None:
+            raise ValueError("prior='device' needs txt_lens and mel_lens")
+        return True
+
+    def prior(self, txt_lens, mel_lens, T: int, L: int, scaling_factor: float = 1.0, out=None):
+        """The padded beta-binomial prior batch [B, T, L] float32 of rows with txt_lens[b] phonemes and mel_lens[b] frames -- what
+        ``batch_prior`` computes with scipy on the host -- generated on the device (e2ealign_prior; the definition stands in
+        include/e2etts_align.h: the reference's P trials evaluated at 0 .. P - 1, so rows do not sum to 1).  Written into ``out``
+        (numpy array or torch tensor, host or GPU) and returned; a fresh numpy array without one."""
+        B, T, L = (int(txt_lens.numel()) if _is_cuda(txt_lens) else int(np.asarray(txt_lens).size)), int(T), int(L)
+        txt_lens, mel_lens = self._lens(txt_lens, B, "txt_lens"), self._lens(mel_lens, B, "mel_lens")
+        if out is None:
+            out = np.empty((B, T, L), np.float32)
+        _expect(out, "out", "float32", B * T * L)
+        self._order(txt_lens, mel_lens, out)
+        self._check(self.lib.e2ealign_prior(self._h, _addr(txt_lens), _addr(mel_lens), B, T, L, float(scaling_factor), _addr(out)), "e2ealign_prior")
+        return out
+
+    def forward(self, mel, keys, speaker=None, txt_lens=None, prior=None, out_attn=None, out_logprob=None, want=("attn", "attn_logprob"),
+                mel_lens=None, prior_scaling: float = 1.0):
+        """mel [B, T, n_mel] (channels-last), keys [B, L, n_text], speaker [B, n_text] | None, txt_lens [B] | None, prior [B, T, L] | None |
+        "device" (the beta-binomial prior of ``prior()`` for txt_lens, ``mel_lens`` and ``prior_scaling``, generated inside the attention
+        pass: the same bits, no [B, T, L] prior in memory)
         -> dict with the numpy arrays named in ``want`` (besides whatever ``out_*`` received); the maps stay resident for mas(None, ...)."""
         B, T, L = int(mel.shape[0]), int(mel.shape[1]), int(keys.shape[1])
         _expect(mel, "mel", "float32", B * T * self.n_mel)
         _expect(keys, "keys", "float32", B * L * self.n_text)
         _expect(speaker, "speaker", "float32", B * self.n_text)
+        gen = self._device_prior(prior, txt_lens, mel_lens)
+        if gen:
+            prior = None
         _expect(prior, "prior", "float32", B * T * L)
-        txt_lens = self._lens(txt_lens, B, "txt_lens")
+        txt_lens, mel_lens = self._lens(txt_lens, B, "txt_lens"), self._lens(mel_lens, B, "mel_lens")
         r = {}
         if out_attn is None and "attn" in want:
             out_attn = r["attn"] = np.empty((B, T, L), np.float32)
@@ -130,6 +166,10 @@ class Aligner(_companion.CompanionHandle):
         _expect(out_attn, "out_attn", "float32", B * T * L)
         _expect(out_logprob, "out_logprob", "float32", B * T * L)
         self._order(mel, keys, speaker, txt_lens, prior, out_attn, out_logprob)
+        if gen:
+            self._check(self.lib.e2ealign_forward_bb(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(mel_lens),
+                                                     float(prior_scaling), B, T, L, _addr(out_attn), _addr(out_logprob)), "e2ealign_forward_bb")
+            return r
         self._check(self.lib.e2ealign_forward(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(prior), B, T, L,
                                               _addr(out_attn), _addr(out_logprob)), "e2ealign_forward")
         return r
@@ -145,6 +185,18 @@ class Aligner(_companion.CompanionHandle):
         r = {name: np.empty((B, T, L), np.float32) for name in want}
         self._order(q, k, prior, txt_lens)
         self._hook("attention", _addr(q), _addr(k), _addr(prior), _addr(txt_lens), B, T, L, _addr(r.get("attn")), _addr(r.get("attn_logprob")))
+        return r
+
+    def debug_attention_bb(self, q, k, txt_lens, mel_lens, scaling_factor: float = 1.0, want=("attn", "attn_logprob")):
+        """Test build only: ``debug_attention`` with the generated prior of ``forward(..., prior="device")``."""
+        B, T, L = int(q.shape[0]), int(q.shape[1]), int(k.shape[1])
+        _expect(q, "q", "float32", B * T * self.n_att)
+        _expect(k, "k", "float32", B * L * self.n_att)
+        txt_lens, mel_lens = self._lens(txt_lens, B, "txt_lens"), self._lens(mel_lens, B, "mel_lens")
+        r = {name: np.empty((B, T, L), np.float32) for name in want}
+        self._order(q, k, txt_lens, mel_lens)
+        self._hook("attention_bb", _addr(q), _addr(k), _addr(txt_lens), _addr(mel_lens), float(scaling_factor), B, T, L, _addr(r.get("attn")),
+                   _addr(r.get("attn_logprob")))
         return r
 
     def mas(self, attn, in_lens, out_lens, B: Optional[int] = None, T: Optional[int] = None, L: Optional[int] = None, log_map: bool = False,
@@ -168,12 +220,16 @@ class Aligner(_companion.CompanionHandle):
         return r
 
     def align(self, mel, keys, speaker, txt_lens, mel_lens, prior=None, out_dur=None, out_hard=None, out_attn=None, out_logprob=None,
-              want=("dur",)):
-        """forward + mas in one call -> dict with the arrays of ``want`` ("dur", "attn_hard", "attn", "attn_logprob")."""
+              want=("dur",), prior_scaling: float = 1.0):
+        """forward + mas in one call -> dict with the arrays of ``want`` ("dur", "attn_hard", "attn", "attn_logprob").  ``prior="device"``:
+        as for ``forward``, with this call's mel_lens."""
         B, T, L = int(mel.shape[0]), int(mel.shape[1]), int(keys.shape[1])
         _expect(mel, "mel", "float32", B * T * self.n_mel)
         _expect(keys, "keys", "float32", B * L * self.n_text)
         _expect(speaker, "speaker", "float32", B * self.n_text)
+        gen = self._device_prior(prior, txt_lens, mel_lens)
+        if gen:
+            prior = None
         _expect(prior, "prior", "float32", B * T * L)
         txt_lens, mel_lens = self._lens(txt_lens, B, "txt_lens"), self._lens(mel_lens, B, "mel_lens")
         r = {}
@@ -189,6 +245,11 @@ class Aligner(_companion.CompanionHandle):
         for x, n in ((out_hard, "out_hard"), (out_attn, "out_attn"), (out_logprob, "out_logprob")):
             _expect(x, n, "float32", B * T * L)
         self._order(mel, keys, speaker, txt_lens, mel_lens, prior, out_dur, out_hard, out_attn, out_logprob)
+        if gen:
+            self._check(self.lib.e2ealign_align_bb(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(mel_lens),
+                                                   float(prior_scaling), B, T, L, _addr(out_dur), _addr(out_hard), _addr(out_attn),
+                                                   _addr(out_logprob)), "e2ealign_align_bb")
+            return r
         self._check(self.lib.e2ealign_align(self._h, _addr(mel), _addr(keys), _addr(speaker), _addr(txt_lens), _addr(mel_lens), _addr(prior),
                                             B, T, L, _addr(out_dur), _addr(out_hard), _addr(out_attn), _addr(out_logprob)), "e2ealign_align")
         return r

@@ -10,6 +10,9 @@
 //   search        aln_mas_wave_kernel (L <= 256): one wavefront per utterance, 1, 2 or 4 phonemes per lane by the row width, the previous log_p row
 //                 in registers, one shuffle per frame; aln_mas_kernel (wider rows): one workgroup per utterance, threads over phonemes, the row ping-ponged in
 //                 LDS, one barrier per frame.  Back-pointers one bit per cell, one lane backtracks.
+// The beta-binomial attention prior (e2ealign_prior; the *_bb entry points) is generated in float64: aln_prior_cols_kernel forms the column
+// terms of the batch once, aln_prior_kernel writes the padded tensor, and the generated-prior form of aln_attn_kernel evaluates the same
+// cells where the given-prior form loads them.  Argument checks, table size and index formulas: prior_plan.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +28,7 @@
 #include "../companion/handle.h"
 #include "../host_logic.h"
 #include "../kernels.h"
+#include "prior_plan.h"
 
 #ifndef E2EALIGN_SRC_HASH
 #define E2EALIGN_SRC_HASH "unknown"
@@ -35,6 +39,10 @@ using namespace e2etts::companion;
 
 static_assert(E2EALIGN_OK == E_OK && E2EALIGN_EINVAL == E_INVAL && E2EALIGN_EHIP == E_HIP && E2EALIGN_ESTATE == E_STATE && E2EALIGN_ENOMEM == E_NOMEM,
               "include/e2etts_align.h and csrc/companion/handle.h disagree on the error codes");
+
+namespace pp = e2ealign_prior_plan;
+static_assert(pp::MAX_B == E2EALIGN_MAX_B && pp::MAX_L == E2EALIGN_MAX_L && pp::MAX_SCALING == E2EALIGN_MAX_PRIOR_SCALING,
+              "include/e2etts_align.h and csrc/align/prior_plan.h disagree on the limits");
 
 namespace {
 
@@ -62,16 +70,77 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// ---- the generated prior.  Every float64 product lives in the two functions below, which are never inlined: aln_prior_kernel and the
+// generated-prior form of aln_attn_kernel call the SAME machine code, so a cell has the same bits wherever it is formed (no contraction
+// or scheduling choice of the compiler can differ between the two kernels).  What the callers add around them are sums and differences.
+
+// log-gamma of frame argument `which` of frame t: 0 alpha, 1 beta, 2 alpha + beta, 3 P + alpha + beta
+__device__ __noinline__ double aln_prior_frame_lgamma(int P, int M, double s, int t, int which) {
+#pragma clang fp contract(off)
+  const double a = pp::alpha_of(s, t), b = pp::beta_of(s, M, t);
+  const double ab = a + b;
+  const double x = which == 0 ? a : which == 1 ? b : which == 2 ? ab : (double)P + ab;
+  return lgamma(x);
+}
+
+// The frame term -log B(alpha, beta) - lgamma(P + alpha + beta), formed once per frame by the wavefront that owns it: lanes 0 .. 3 take one
+// log-gamma each (every lane evaluates one; the four are broadcast).  All 64 lanes must be active.
+__device__ __forceinline__ double aln_prior_frame_term(int P, int M, double s, int t, int lane) {
+  const double v = aln_prior_frame_lgamma(P, M, s, t, lane & 3);
+  const double la = __shfl(v, 0, 64), lb = __shfl(v, 1, 64), lab = __shfl(v, 2, 64), ln = __shfl(v, 3, 64);
+  return (lab - (la + lb)) - ln;
+}
+
+// The column term log C(P, k), k < P.
+__device__ __forceinline__ double aln_prior_col_term(int P, int k) { return (lgamma((double)P + 1.0) - lgamma((double)k + 1.0)) - lgamma((double)(P - k) + 1.0); }
+
+// THE prior value of cell (t, k), t < M, k < P, of a row with P phonemes and M frames (include/e2etts_align.h): float64 throughout,
+// rounded to fp32 once.  `col` and `frame` are the terms above.
+__device__ __noinline__ float aln_prior_value(int P, int M, double s, int t, int k, double col, double frame) {
+#pragma clang fp contract(off)
+  const double a = pp::alpha_of(s, t), b = pp::beta_of(s, M, t);
+  const double e = lgamma((double)k + a) + lgamma((double)(P - k) + b);
+  return (float)exp((col + frame) + e);
+}
+
+// cols[b, k] = log C(txt_lens[b], k) for k < txt_lens[b], 0 beyond (never read)
+__global__ void aln_prior_cols_kernel(const int32_t* __restrict__ txt_lens, double* __restrict__ cols, int B, int L) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pp::col_table_doubles(B, L)) return;
+  const int b = (int)(i / (size_t)L), k = (int)(i - (size_t)b * L);
+  const int P = txt_lens[b];
+  cols[pp::col_index(b, k, L)] = k < P ? aln_prior_col_term(P, k) : 0.0;
+}
+
+// What a kernel needs to generate the prior: the column table, the frames of every row, the scaling factor (txt_lens travels apart).
+struct PriorGen {
+  const double* cols;
+  const int32_t* mel_lens;
+  double s;
+};
+
+// The padded [B, T, L] prior: one wavefront per frame (workgroup x = frames 4 x .. 4 x + 3 of utterance blockIdx.y), lanes stride the columns.
+__global__ __launch_bounds__(256) void aln_prior_kernel(const int32_t* __restrict__ txt_lens, PriorGen gen, float* __restrict__ out, int T, int L) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63, t = blockIdx.x * pp::FRAMES_PER_GROUP + (threadIdx.x >> 6);
+  if (t >= T) return;   // wave-uniform
+  const int P = txt_lens[b], M = gen.mel_lens[b];
+  const bool live = t < M;   // wave-uniform
+  const double frame = live ? aln_prior_frame_term(P, M, gen.s, t, lane) : 0.0;
+  for (int j = lane; j < L; j += 64)
+    out[pp::cell_index(b, t, j, T, L)] = (live && j < P) ? aln_prior_value(P, M, gen.s, t, j, gen.cols[pp::col_index(b, j, L)], frame) : 0.f;
+}
+
 // One workgroup = TI = 4 * FPT frames of one utterance against ALL its L keys (padded ones included: the prior's log-softmax runs over
 // them).  Phase 1: 64 keys at a time in LDS (row stride odd: conflict-free), thread (wave g, lane j) accumulates the squared distance of key j
 // to the FPT frames of wave g in four interleaved fma chains per frame (channel c goes to chain c mod 4; chains summed (0 + 1) + (2 + 3)),
 // score = -temperature * d into the tile's score rows in LDS.  Phase 2: wave g owns its FPT rows; lanes stride the columns, so every lane
 // rereads only what it wrote: log_softmax over L columns + log(prior + 1e-8) when a prior is given, attn_logprob out, then the masked softmax
-// (masked keys exactly 0).  Every global access is guarded by t < T and j < L.
-template <int FPT>
+// (masked keys exactly 0).  Every global access is guarded by t < T and j < L.  GEN: the prior is not loaded but generated -- cell (t, j) is
+// aln_prior_value where t < mel_lens[b] and j < txt_lens[b] (which is then required) and 0 elsewhere, the tensor aln_prior_kernel writes.
+template <int FPT, bool GEN>
 __global__ __launch_bounds__(256) void aln_attn_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ prior,
                                                        const int32_t* __restrict__ txt_lens, float* __restrict__ attn, float* __restrict__ logp,
-                                                       int T, int L, int C, float temperature) {
+                                                       int T, int L, int C, float temperature, PriorGen gen) {
   constexpr int TI = 4 * FPT;
   extern __shared__ __attribute__((aligned(16))) float aln_smem[];
   const int Cs = C | 1;
@@ -130,7 +199,7 @@ __global__ __launch_bounds__(256) void aln_attn_kernel(const float* __restrict__
     if (t >= T) break;   // wave-uniform
     float* row = ss + (g * FPT + f) * L;
     const size_t base = ((size_t)b * T + t) * L;
-    if (prior) {
+    if (GEN || prior) {
       float m = -INFINITY;
       for (int j = lane; j < L; j += 64) m = fmaxf(m, row[j]);
       m = wave_max(m);
@@ -138,7 +207,17 @@ __global__ __launch_bounds__(256) void aln_attn_kernel(const float* __restrict__
       for (int j = lane; j < L; j += 64) s += expf(row[j] - m);
       s = wave_sum(s);
       const float ls = logf(s);
-      for (int j = lane; j < L; j += 64) row[j] = ((row[j] - m) - ls) + logf(prior[base + j] + 1e-8f);
+      if constexpr (GEN) {
+        const int M = gen.mel_lens[b];
+        const bool live = t < M;   // wave-uniform
+        const double frame = live ? aln_prior_frame_term(len, M, gen.s, t, lane) : 0.0;
+        for (int j = lane; j < L; j += 64) {
+          const float p = (live && j < len) ? aln_prior_value(len, M, gen.s, t, j, gen.cols[pp::col_index(b, j, L)], frame) : 0.f;
+          row[j] = ((row[j] - m) - ls) + logf(p + 1e-8f);
+        }
+      } else {
+        for (int j = lane; j < L; j += 64) row[j] = ((row[j] - m) - ls) + logf(prior[base + j] + 1e-8f);
+      }
     }
     float m2 = -INFINITY;
     for (int j = lane; j < L; j += 64) {
@@ -343,10 +422,10 @@ struct e2ealign_handle : Handle {
 namespace {
 
 int check_lens(e2ealign_handle* h, const std::vector<int64_t>& v, long long hi, const char* name, const char* hi_name) {
-  for (size_t b = 0; b < v.size(); ++b)
-    if (v[b] < 1 || v[b] > hi)
-      return h->fail(E2EALIGN_EINVAL, std::string(name) + "[" + std::to_string(b) + "] = " + std::to_string((long long)v[b]) + " outside [1, " + hi_name +
-                                          " = " + std::to_string(hi) + "]");
+  const int64_t b = pp::first_bad_len(v.data(), (int64_t)v.size(), hi);
+  if (b >= 0)
+    return h->fail(E2EALIGN_EINVAL, std::string(name) + "[" + std::to_string(b) + "] = " + std::to_string((long long)v[b]) + " outside [1, " + hi_name +
+                                        " = " + std::to_string(hi) + "]");
   return E2EALIGN_OK;
 }
 
@@ -385,6 +464,8 @@ struct FwdArgs {
   const float *mel, *keys, *speaker, *prior;
   const std::vector<int64_t>* txt_lens;   // null: no mask
   int B, T, L;
+  const std::vector<int64_t>* gen_mel_lens = nullptr;   // not null: the prior is generated from txt_lens, these and gen_scaling (`prior` is NULL)
+  double gen_scaling = 0.0;
 };
 
 int check_attention_tile(e2ealign_handle* h, int L) {
@@ -403,19 +484,52 @@ int check_forward(e2ealign_handle* h, const FwdArgs& a) {
   return check_attention_tile(h, a.L);
 }
 
+// The checks of a generated prior's arguments (prior_plan.h), lengths fetched to the host: what e2ealign_prior and the *_bb entry points
+// refuse before they look at anything else.
+int check_prior_args(e2ealign_handle* h, const int64_t* txt_lens, const int64_t* mel_lens, int B, int T, int L, double scaling, std::vector<int64_t>& tl,
+                     std::vector<int64_t>& ml) {
+  if (const char* m = pp::check_shape(B, T, L)) return h->fail(E2EALIGN_EINVAL, m);
+  if (!txt_lens || !mel_lens) return h->fail(E2EALIGN_EINVAL, "txt_lens and mel_lens must not be NULL");
+  if (const char* m = pp::check_scaling(scaling)) return h->fail(E2EALIGN_EINVAL, m);
+  RET(fetch_host(h, txt_lens, B, tl));
+  RET(check_lens(h, tl, L, "txt_lens", "L"));
+  RET(fetch_host(h, mel_lens, B, ml));
+  return check_lens(h, ml, T, "mel_lens", "T");
+}
+
+// What the kernels that generate the prior need besides txt_lens, which the caller has uploaded to lens_txt: mel_lens on the device (in
+// lens_out, where the search puts them too) and the column table.  The table lives in `ky`, the key projection's intermediate: a forward
+// has finished with that buffer when the attention pass starts, so generating the prior holds no memory of its own.
+int prepare_prior_gen(e2ealign_handle* h, const std::vector<int64_t>& mel_lens, double scaling, int B, int L, PriorGen& gen) {
+  RET(upload_lens(h, h->lens_out, h->host_out, mel_lens));
+  const size_t n = pp::col_table_doubles(B, L);
+  RET(reserve(h, h->ky, n * sizeof(double)));
+  hipLaunchKernelGGL(aln_prior_cols_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, (const int32_t*)h->lens_txt.p, (double*)h->ky.p, B, L);
+  HIPCHK(h, hipGetLastError());
+  gen = PriorGen{(const double*)h->ky.p, (const int32_t*)h->lens_out.p, scaling};
+  return E2EALIGN_OK;
+}
+
 // The attention pass on device q [B, T, n_att] and k [B, L, n_att] into the handle's attn / attn_logprob: the ONE place that chooses the frame
 // tile (16 frames per workgroup while the tile fits the LDS limit, 4 otherwise; check_attention_tile has refused what 4 cannot hold).
-// run_forward and the test build's e2ealign_debug_attention both launch through it.
-int launch_attention(e2ealign_handle* h, const float* q, const float* k, const float* prior, const int32_t* lens, int B, int T, int L) {
+// run_forward and the test build's e2ealign_debug_attention / _bb launch through it.  `gen` (not null: `prior` is) selects the
+// generated-prior form.
+int launch_attention(e2ealign_handle* h, const float* q, const float* k, const float* prior, const int32_t* lens, int B, int T, int L,
+                     const PriorGen* gen = nullptr) {
   const int A = h->n_att;
   hipStream_t s = h->stream;
+  const PriorGen g = gen ? *gen : PriorGen{nullptr, nullptr, 0.0};
+#define ALN_ATTN(FPT, GEN)                                                                                                                              \
+  hipLaunchKernelGGL((aln_attn_kernel<FPT, GEN>), dim3((T + 4 * FPT - 1) / (4 * FPT), B), dim3(256), attn_lds_bytes(4 * FPT, L, A), s, q, k, prior, lens, \
+                     (float*)h->attn.p, (float*)h->logp.p, T, L, A, h->temperature, g)
   if (attn_lds_bytes(16, L, A) <= ATTN_LDS_MAX) {
-    hipLaunchKernelGGL(aln_attn_kernel<4>, dim3((T + 15) / 16, B), dim3(256), attn_lds_bytes(16, L, A), s, q, k, prior, lens, (float*)h->attn.p,
-                       (float*)h->logp.p, T, L, A, h->temperature);
+    if (gen) ALN_ATTN(4, true);
+    else ALN_ATTN(4, false);
   } else {
-    hipLaunchKernelGGL(aln_attn_kernel<1>, dim3((T + 3) / 4, B), dim3(256), attn_lds_bytes(4, L, A), s, q, k, prior, lens, (float*)h->attn.p,
-                       (float*)h->logp.p, T, L, A, h->temperature);
+    if (gen) ALN_ATTN(1, true);
+    else ALN_ATTN(1, false);
   }
+#undef ALN_ATTN
   HIPCHK(h, hipGetLastError());
   return E2EALIGN_OK;
 }
@@ -467,7 +581,13 @@ int run_forward(e2ealign_handle* h, const FwdArgs& a) {
   KCHK(h, launch_conv_gemm(conv(qx, h->q4w, h->q4b, qy, B, T, M, A, 1, ACT_NONE), s));
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[1], s));
   const int32_t* lens = a.txt_lens ? (const int32_t*)h->lens_txt.p : nullptr;
-  RET(launch_attention(h, qy, kenc, prior, lens, B, T, L));
+  if (a.gen_mel_lens) {
+    PriorGen gen;
+    RET(prepare_prior_gen(h, *a.gen_mel_lens, a.gen_scaling, B, L, gen));   // (ky is free: key_proj has been enqueued)
+    RET(launch_attention(h, qy, kenc, nullptr, lens, B, T, L, &gen));
+  } else {
+    RET(launch_attention(h, qy, kenc, prior, lens, B, T, L));
+  }
   if (h->profile) HIPCHK(h, hipEventRecord(h->ev[2], s));
   h->rB = B; h->rT = T; h->rL = L;
   return E2EALIGN_OK;
@@ -692,6 +812,63 @@ int e2ealign_align(e2ealign_handle* h, const float* mel, const float* keys, cons
   return finish(h, true, true);
 }
 
+int e2ealign_prior(e2ealign_handle* h, const int64_t* txt_lens, const int64_t* mel_lens, int B, int T, int L, double scaling, float* prior_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl, ml;
+  RET(check_prior_args(h, txt_lens, mel_lens, B, T, L, scaling, tl, ml));
+  if (!prior_out) return h->fail(E2EALIGN_EINVAL, "prior_out must not be NULL");
+  RET(begin_call(h));
+  const size_t n = (size_t)B * T * L * 4;
+  float* dst = prior_out;
+  if (!is_device_pointer(prior_out)) {
+    RET(reserve(h, h->prior, n));
+    dst = (float*)h->prior.p;
+  }
+  RET(upload_lens(h, h->lens_txt, h->host_txt, tl));
+  PriorGen gen;
+  RET(prepare_prior_gen(h, ml, scaling, B, L, gen));
+  hipLaunchKernelGGL(aln_prior_kernel, dim3(pp::frame_groups(T), B), dim3(256), 0, h->stream, (const int32_t*)h->lens_txt.p, gen, dst, T, L);
+  HIPCHK(h, hipGetLastError());
+  if (dst != prior_out) RET(copy_out(h, prior_out, dst, n));
+  return finish(h, false, false);
+}
+
+int e2ealign_forward_bb(e2ealign_handle* h, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens, const int64_t* mel_lens,
+                        double scaling, int B, int T, int L, float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl, ml;
+  RET(check_prior_args(h, txt_lens, mel_lens, B, T, L, scaling, tl, ml));
+  FwdArgs a{mel, keys, speaker, nullptr, &tl, B, T, L, &ml, scaling};
+  RET(check_forward(h, a));
+  RET(begin_call(h));
+  RET(run_forward(h, a));
+  const size_t n = (size_t)B * T * L * 4;
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, true, false);
+}
+
+int e2ealign_align_bb(e2ealign_handle* h, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens, const int64_t* mel_lens,
+                      double scaling, int B, int T, int L, float* dur_out, float* attn_hard_out, float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl, ml;
+  RET(check_prior_args(h, txt_lens, mel_lens, B, T, L, scaling, tl, ml));
+  FwdArgs a{mel, keys, speaker, nullptr, &tl, B, T, L, &ml, scaling};
+  RET(check_forward(h, a));
+  RET(begin_call(h));
+  RET(run_forward(h, a));
+  RET(run_mas(h, (const float*)h->attn.p, 0, tl, ml, B, T, L, attn_hard_out != nullptr));
+  const size_t n = (size_t)B * T * L * 4;
+  RET(copy_out(h, dur_out, h->dur.p, (size_t)B * L * 4));
+  RET(copy_out(h, attn_hard_out, h->hard.p, n));
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, true, true);
+}
+
 int e2ealign_profile_enable(e2ealign_handle* h, int on) { return companion::profile_enable(h, on); }
 int e2ealign_profile_read(e2ealign_handle* h, double ms_out[3]) { return companion::profile_read(h, ms_out); }
 
@@ -733,6 +910,33 @@ int e2ealign_debug_attention(e2ealign_handle* h, const float* q, const float* k,
   HIPCHK(h, hipMemcpyAsync(h->qy.p, q, (size_t)B * T * A * 4, hipMemcpyDefault, h->stream));
   HIPCHK(h, hipMemcpyAsync(h->kenc.p, k, (size_t)B * L * A * 4, hipMemcpyDefault, h->stream));
   RET(launch_attention(h, (const float*)h->qy.p, (const float*)h->kenc.p, dprior, txt_lens ? (const int32_t*)h->lens_txt.p : nullptr, B, T, L));
+  h->rB = B; h->rT = T; h->rL = L;
+  RET(copy_out(h, attn_out, h->attn.p, n));
+  RET(copy_out(h, attn_logprob_out, h->logp.p, n));
+  return finish(h, false, false);
+}
+
+int e2ealign_debug_attention_bb(e2ealign_handle* h, const float* q, const float* k, const int64_t* txt_lens, const int64_t* mel_lens, double scaling,
+                                int B, int T, int L, float* attn_out, float* attn_logprob_out) {
+  if (!h) return E2EALIGN_EINVAL;
+  std::lock_guard<std::mutex> lk(h->mu);
+  std::vector<int64_t> tl, ml;
+  RET(check_prior_args(h, txt_lens, mel_lens, B, T, L, scaling, tl, ml));
+  if (!q || !k) return h->fail(E2EALIGN_EINVAL, "q and k must not be NULL");
+  RET(check_attention_tile(h, L));
+  RET(begin_call(h));
+  const size_t A = h->n_att, n = (size_t)B * T * L * 4;
+  h->rB = h->rT = h->rL = 0;
+  RET(reserve(h, h->qy, (size_t)B * T * A * 4));
+  RET(reserve(h, h->kenc, (size_t)B * L * A * 4));
+  RET(reserve(h, h->attn, n));
+  RET(reserve(h, h->logp, n));
+  RET(upload_lens(h, h->lens_txt, h->host_txt, tl));
+  PriorGen gen;
+  RET(prepare_prior_gen(h, ml, scaling, B, L, gen));
+  HIPCHK(h, hipMemcpyAsync(h->qy.p, q, (size_t)B * T * A * 4, hipMemcpyDefault, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->kenc.p, k, (size_t)B * L * A * 4, hipMemcpyDefault, h->stream));
+  RET(launch_attention(h, (const float*)h->qy.p, (const float*)h->kenc.p, nullptr, (const int32_t*)h->lens_txt.p, B, T, L, &gen));
   h->rB = B; h->rT = T; h->rL = L;
   RET(copy_out(h, attn_out, h->attn.p, n));
   RET(copy_out(h, attn_logprob_out, h->logp.p, n));

@@ -188,7 +188,9 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         """Forced alignment of recordings with the model's own aligner: the reference's ``attn_out`` (U/layers.py:203-212) without the rest
         of the training forward.  speaker [B] (or one id for the batch), texts [B, L] int64, txt_lens [B], mels [B, T, n_mel] (the layout
         ``inference`` returns; the reference's parse_batch transposes to it, U/model.py:80), mel_lens [B], attn_prior [B, T, L] or None -- the
-        beta-binomial prior is then built per row, as the reference's data preparation does.
+        beta-binomial prior is then built per row, as the reference's data preparation does (scipy on the host, then uploaded) -- or
+        "device": the same prior (P trials evaluated at 0 .. P - 1, include/e2etts_align.h) generated inside the aligner's attention
+        pass; no prior array is built or uploaded.
         -> (attn_soft [B, 1, T, L], attn_hard [B, 1, T, L], attn_hard_dur [B, L], attn_logprob [B, 1, T, L]), torch tensors on the GPU."""
         from . import aligner as al
         torch = _torch()
@@ -211,12 +213,21 @@ class UnsupervisedFastSpeech2(_EngineBacked):
             if tl.shape != (B,) or ml.shape != (B,) or (tl < 1).any() or (tl > L).any() or (ml < 1).any() or (ml > T).any():
                 raise ValueError("txt_lens must lie in [1, L] and mel_lens in [1, T], one per row")
             attn_prior = al.batch_prior(tl, ml, T, L)
-        prior = torch.as_tensor(attn_prior, dtype=torch.float32).to(dev).contiguous()
+        prior = self._prior_argument(attn_prior, dev)
         soft = torch.empty((B, T, L), dtype=torch.float32, device=dev)
         hard, logprob = torch.empty_like(soft), torch.empty_like(soft)
         dur = torch.empty((B, L), dtype=torch.float32, device=dev)
         enc.encoder.align(mel, keys, spk, tl, ml, prior, out_dur=dur, out_hard=hard, out_attn=soft, out_logprob=logprob, want=())
         return soft.unsqueeze(1), hard.unsqueeze(1), dur, logprob.unsqueeze(1)
+
+    @staticmethod
+    def _prior_argument(attn_prior, dev):
+        """What ``Aligner.align`` takes as its prior: "device" as it is (generated there), anything else as a float32 tensor on the GPU."""
+        if isinstance(attn_prior, str):
+            if attn_prior != "device":
+                raise ValueError(f"attn_prior must be None, a [B, T, L] array, or 'device' (got {attn_prior!r})")
+            return attn_prior
+        return _torch().as_tensor(attn_prior, dtype=_torch().float32).to(dev).contiguous()
 
     def set_audio_config(self, audio: Mapping[str, object]):
         """The ``audio`` section of the reference's preprocessing configuration (``stft.filter_length / hop_length / win_length``,
@@ -256,7 +267,8 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         (e2e_tts_amd.condition; unpinned against pydub, see there), on the device and in its order: downmix ([B, n, 2] or [B, 2 n]
         interleaved frames, wav_lens in frames), rate, silence trim, loudness; wav_lens and mel_lens then follow from the kept samples.
         Conditioning works on int16 PCM: with ``wav_rate`` it takes the resampler's int16 output, float32 ``wavs`` at the transform's own
-        rate raise ValueError.  None: today's path, bit for bit."""
+        rate raise ValueError.  None: today's path, bit for bit.  ``attn_prior``: as for ``align``; with "device" the mel lengths the mel
+        front-end returned go straight to the aligner, which generates the prior in its attention pass."""
         out, energy, _ = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition)
         return out + (energy,) if return_energy else out
 
@@ -359,7 +371,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
             if tl.shape != (B,) or (tl < 1).any() or (tl > L).any():
                 raise ValueError("txt_lens must lie in [1, L], one per row")
             attn_prior = al.batch_prior(tl, ml, T, L)
-        prior = torch.as_tensor(attn_prior, dtype=torch.float32).to(dev).contiguous()
+        prior = self._prior_argument(attn_prior, dev)
         soft = torch.empty((B, T, L), dtype=torch.float32, device=dev)
         hard, logprob = torch.empty_like(soft), torch.empty_like(soft)
         dur = torch.empty((B, L), dtype=torch.float32, device=dev)
@@ -440,7 +452,8 @@ class UnsupervisedFastSpeech2(_EngineBacked):
 
     def forward(self, inputs=None, step=0):
         """The reference's teacher-forced forward in eval() (U/model.py:95-153; what generate_mel calls): ``inputs`` is its 10-tuple
-        (speakers, texts, mels [B, T, n_mel], attn_priors, p_targets, e_targets, txt_lens, max_txt_len, mel_lens, max_mel_len) with the
+        (speakers, texts, mels [B, T, n_mel], attn_priors (as ``align``'s attn_prior: an array, None or "device"), p_targets, e_targets,
+        txt_lens, max_txt_len, mel_lens, max_mel_len) with the
         targets at FRAME level ({"f0", "uv"} of [B, T], or one [B, T] tensor for a model without use_uv; None = embed the prediction).
         -> the reference's two tuples, (mel, mel_post, log_d, pitch_pred, energy_pred, txt_lens, txt_masks, mel_lens, mel_masks, attn_out),
         (p_targets, e_targets) as embedded; attn_out comes from the aligner library, and its soft map and durations are handed to the
@@ -462,11 +475,12 @@ class UnsupervisedFastSpeech2(_EngineBacked):
 
     __call__ = forward
 
-    def forward_audio(self, speaker, texts, txt_lens, wavs, wav_lens, p_targets=None, e_targets=None, step=0, wav_rate=None, condition=None):
+    def forward_audio(self, speaker, texts, txt_lens, wavs, wav_lens, p_targets=None, e_targets=None, step=0, wav_rate=None, condition=None,
+                      attn_prior=None):
         """``align_audio`` followed by the teacher-forced pass: recordings -> ground-truth-aligned mels, with the mel, the soft map and the
         durations never leaving the device.  p_targets / e_targets: frame-level targets [B, T] as for ``forward`` (T = the mel frames of
-        the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``, ``condition``: as for ``align_audio`` (with
-        ``condition`` T follows from the kept samples).  ``p_targets="extract"``: the pitch targets are made from the recordings
+        the longest recording: max(wav_lens) // hop at the transform's rate).  ``wav_rate``, ``condition``, ``attn_prior``: as for
+        ``align_audio`` (with ``condition`` T follows from the kept samples).  ``p_targets="extract"``: the pitch targets are made from the recordings
         themselves, on the device: the pitch tracker (e2e_tts_amd.f0; unpinned against parselmouth, see there) reads the same samples
         the mel front-end reads -- after ``condition`` and / or ``wav_rate`` too --, its track lies on the mel grid, and the data
         loader's targets (``f0_targets`` with this model's stats and pitch_quantization) feed the pass where they lie.  That needs a
@@ -480,7 +494,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
                 raise ValueError("p_targets='extract' needs a use_uv model: the targets of a model without come from pyworld's extract_pitch "
                                  "in the reference, which this package does not restate")
             tap = {}
-        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, None, False, None, wav_rate, condition, tap=tap)
+        attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, False, None, wav_rate, condition, tap=tap)
         self._check_lengths(txt_lens, ml)
         T = int(attn_out[0].shape[2])
         if tap is not None:

@@ -22,7 +22,8 @@
  *  - arithmetic is exact fp32 throughout (durations are a discrete decision: no split-precision or bf16 path);
  *  - workspaces grow with the largest (B, T, L) seen and are never shrunk; steady state allocates nothing.  Device memory is
  *    O(B * T * L): three [B, T, L] maps (attn, attn_logprob, attn_hard), one back-pointer BIT per cell, and O(B * (T + L) * channels)
- *    for the projections.  The reference's [B, n_att, T, L] difference tensor is never formed.
+ *    for the projections.  The reference's [B, n_att, T, L] difference tensor is never formed.  A prior given in host memory is staged
+ *    in one more [B, T, L] buffer; a generated one (e2ealign_forward_bb / e2ealign_align_bb) holds nothing of its own.
  *  - one handle is used by one thread at a time (calls are serialised by a mutex inside).
  */
 #ifndef E2ETTS_ALIGN_H
@@ -41,7 +42,7 @@ extern "C" {
 #define E2EALIGN_API
 #endif
 
-#define E2EALIGN_ABI_VERSION 1
+#define E2EALIGN_ABI_VERSION 2
 
 #define E2EALIGN_OK 0
 #define E2EALIGN_EINVAL (-1)   /* bad argument / shape / length, a weight blob without one of the aligner's tensors */
@@ -53,6 +54,7 @@ extern "C" {
 #define E2EALIGN_MAX_ATT 128   /* n_att_channels */
 #define E2EALIGN_MAX_L 2048    /* phonemes per row */
 #define E2EALIGN_MAX_B 4096
+#define E2EALIGN_MAX_PRIOR_SCALING 1048576.0   /* 2^20: the largest `scaling` of a generated prior (every log-gamma argument stays finite) */
 
 /* e2ealign_mas / e2ealign_align flags */
 #define E2EALIGN_LOG_MAP 1     /* `map` already holds log-probabilities: the search does not take the logarithm */
@@ -108,6 +110,32 @@ E2EALIGN_API int e2ealign_align(e2ealign_handle* handle, const float* mel, const
                                 const int64_t* mel_lens, const float* prior, int B, int T, int L, float* dur_out, float* attn_hard_out,
                                 float* attn_out, float* attn_logprob_out);
 
+/* The beta-binomial attention prior of the reference's data preparation (beta_binomial_prior_distribution, TOOLS/utils.py:129-139, padded
+ * by the collate function, dataloader.py:274-281; TOOLS/ = e2e_tts/src/tools/), generated on the device.  For row b with
+ * P = txt_lens[b] phonemes, M = mel_lens[b] frames and a scaling factor s = `scaling`:
+ *
+ *     prior[b, t, k] = fp32( C(n, k) * B(k + alpha, n - k + beta) / B(alpha, beta) )
+ *                      with n = P, alpha = s * (t + 1), beta = s * (M - t),   for 0 <= t < M, 0 <= k < P
+ *     prior[b, t, k] = 0 everywhere else in the padded [T, L]
+ *
+ *  - the reference's quirk is kept: n = P trials, but only the outcomes 0 .. P - 1 are stored, so a row does not sum to 1;
+ *  - the value is evaluated in float64 through log-gamma terms and rounded to fp32 once; a result below fp32's normal range may come out
+ *    as the subnormal or as 0;
+ *  - 1 <= txt_lens[b] <= L, 1 <= mel_lens[b] <= T, both arrays required; `scaling` finite, > 0 and <= E2EALIGN_MAX_PRIOR_SCALING.
+ * `prior_out` [B, T, L] fp32, host or device memory, must not be NULL (it is the call's only result).  Needs no weights and leaves the
+ * resident maps alone. */
+E2EALIGN_API int e2ealign_prior(e2ealign_handle* handle, const int64_t* txt_lens, const int64_t* mel_lens, int B, int T, int L, double scaling,
+                                float* prior_out);
+
+/* e2ealign_forward / e2ealign_align with the prior of e2ealign_prior(txt_lens, mel_lens, scaling) GENERATED inside the attention pass: the
+ * same bits as the call that is handed e2ealign_prior's tensor, without a [B, T, L] prior in memory (nothing is uploaded, no staging
+ * buffer is held).  Both length arrays are required; txt_lens is also the mask. */
+E2EALIGN_API int e2ealign_forward_bb(e2ealign_handle* handle, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens,
+                                     const int64_t* mel_lens, double scaling, int B, int T, int L, float* attn_out, float* attn_logprob_out);
+E2EALIGN_API int e2ealign_align_bb(e2ealign_handle* handle, const float* mel, const float* keys, const float* speaker, const int64_t* txt_lens,
+                                   const int64_t* mel_lens, double scaling, int B, int T, int L, float* dur_out, float* attn_hard_out,
+                                   float* attn_out, float* attn_logprob_out);
+
 /* Measurement aid: with profiling on, every forward / mas / align records HIP events around its phases; e2ealign_profile_read gives the
  * last call's milliseconds as {projections, attention pass, search} (0 for a phase the call did not run). */
 E2EALIGN_API int e2ealign_profile_enable(e2ealign_handle* handle, int on);
@@ -122,6 +150,10 @@ E2EALIGN_API int e2ealign_debug_poison_workspace(e2ealign_handle* handle);
  * validation of B, T, L and txt_lens as e2ealign_forward, same choice of the frame tile (one function launches both), same outputs. */
 E2EALIGN_API int e2ealign_debug_attention(e2ealign_handle* handle, const float* q, const float* k, const float* prior, const int64_t* txt_lens,
                                           int B, int T, int L, float* attn_out, float* attn_logprob_out);
+/* Test build only: the same with the generated prior that e2ealign_forward_bb takes: txt_lens and mel_lens are required. */
+E2EALIGN_API int e2ealign_debug_attention_bb(e2ealign_handle* handle, const float* q, const float* k, const int64_t* txt_lens,
+                                             const int64_t* mel_lens, double scaling, int B, int T, int L, float* attn_out,
+                                             float* attn_logprob_out);
 #endif
 
 #ifdef __cplusplus

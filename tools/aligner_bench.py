@@ -4,7 +4,11 @@
 Records (median over --repeats calls after --warmup): HIP-event times of the projections, the attention pass and the search inside one
 e2ealign_align call, the wall time of the whole call (it returns after the handle's stream has drained), the handle's device memory next to
 the size of one [B, T, L] map and of the reference's [B, n_att, T, L] tensor, and, for scale, the plain-loop numpy search of
-tests/aligner_ref.py over the same batch on --cpus processes.  Prints one JSON line.  Nothing in the tests depends on these times."""
+tests/aligner_ref.py over the same batch on --cpus processes.  Prints one JSON line.  Nothing in the tests depends on these times.
+
+--prior says where the beta-binomial prior comes from: ``given`` (built before the loop and resident in HBM: e2ealign_align), ``device``
+(generated inside the attention pass: e2ealign_align_bb) or ``host`` (aligner.batch_prior, scipy, and its upload INSIDE the timed loop,
+reported as host_prior_ms: what attn_prior=None costs a caller per batch)."""
 from __future__ import annotations
 
 import argparse
@@ -38,6 +42,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=30)
     ap.add_argument("--cpus", type=int, default=16)
     ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--prior", choices=("given", "device", "host"), default="given")
     a = ap.parse_args()
     import torch
     from e2e_tts_amd import aligner as al, packer, synth_weights as sw
@@ -60,17 +65,26 @@ def main():
     attn = torch.empty((B, T, L), device="cuda")
     torch.cuda.synchronize()
     rows = {"proj": [], "attn": [], "mas": [], "call_wall": []}
+    if a.prior == "host":
+        rows["host_prior"] = []
     for i in range(a.warmup + a.repeats):
         t0 = time.perf_counter()
-        h.align(mel, keys, spk, txt_lens, mel_lens, prior, out_dur=dur, want=())
+        if a.prior == "host":
+            prior = dev(al.batch_prior(txt_lens, mel_lens, T, L))
+            torch.cuda.synchronize()
+            built = (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+        h.align(mel, keys, spk, txt_lens, mel_lens, "device" if a.prior == "device" else prior, out_dur=dur, want=())
         wall = (time.perf_counter() - t0) * 1e3
         if i >= a.warmup:
             ms = h.profile_read()
             for k in ("proj", "attn", "mas"):
                 rows[k].append(ms[k])
             rows["call_wall"].append(wall)
+            if a.prior == "host":
+                rows["host_prior"].append(built)
     out = {f"{k}_ms": round(statistics.median(v), 4) for k, v in rows.items()}
-    out.update(B=B, L=L, T=T, hidden=H, n_mel=M, repeats=a.repeats, device_bytes=h.device_bytes(), weight_bytes=int(blob.size),
+    out.update(prior=a.prior, B=B, L=L, T=T, hidden=H, n_mel=M, repeats=a.repeats, device_bytes=h.device_bytes(), weight_bytes=int(blob.size),
                map_bytes=B * T * L * 4, reference_4d_tensor_bytes=B * M * T * L * 4)
     out["maps_held"] = round((out["device_bytes"] - out["weight_bytes"]) / out["map_bytes"], 3)
     if not a.no_cpu:
