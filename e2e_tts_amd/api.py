@@ -304,6 +304,15 @@ class TTS:
         ``output_rate`` (None or the model's rate: today's path, bit for bit): every utterance's PCM -- denoised, when that is asked for --
         is converted to that rate on the GPU (e2e_tts_amd.resample, n_valid = mel_lens * hop) and the silence between utterances is
         int(silence_distance * output_rate) samples."""
+        pcms, lengths, rs = self._synthesize_requests(sequences, speaker_id, pitch_control, energy_control, duration_control, denoise_strength, output_rate)
+        if rs is not None:
+            return self._combine_samples(pcms, lengths, int(silence_distance * int(output_rate)))
+        return self._combine_pcm(pcms, lengths, int(silence_distance * self.sample_rate))
+
+    def _synthesize_requests(self, sequences, speaker_id, pitch_control, energy_control, duration_control, denoise_strength, output_rate):
+        """The batch loop of ``inference_ids``: plans the requests, runs the batches and puts the utterances back into request order.
+        -> (one int16 PCM row per request, its length -- in mel frames, or in samples when the PCM was converted to ``output_rate`` --, the
+        resampler used or None)."""
         denoise_strength = float(denoise_strength)
         rs = None
         if output_rate is not None and int(output_rate) != int(self.sample_rate):
@@ -341,9 +350,62 @@ class TTS:
                     self.engine.set_denoise(0.0)
         pcms = [pcms[i] for i in revert.tolist()]
         lengths = [lengths[i] for i in revert.tolist()]
-        if rs is not None:
-            return self._combine_samples(pcms, lengths, int(silence_distance * int(output_rate)))
-        return self._combine_pcm(pcms, lengths, int(silence_distance * self.sample_rate))
+        return pcms, lengths, rs
+
+    def _recording_chain(self):
+        """The mirror whose recording chain (condition, rate, mel front-end, pitch tracker) ``evaluate_ids`` uses: built without an
+        engine of its own, with this checkpoint's audio configuration."""
+        m = self.__dict__.get("_recording_model")
+        if m is None:
+            m = UnsupervisedFastSpeech2(self._dims.n_symbols, len(self.speakers), self._dims.n_mel, self.config["models"]["fastspeech2"], self.stats,
+                                        device=self._device_index, hop_length=self.hop_length, sampling_rate=self.sample_rate)
+            audio = self.config.get("audio", {})
+            if all(k in audio for k in ("stft", "mel", "signal")):
+                m.set_audio_config(audio)
+            self._recording_model = m
+        return m
+
+    def evaluate_ids(self, sequences: Sequence[Sequence[int]], recordings, recording_lens, speaker_id, pitch_control=1.0, energy_control=1.0,
+                     duration_control=1.0, denoise_strength: float = 0.0, wav_rate: Optional[int] = None, condition=None, mode: str = "dtw",
+                     band: Optional[int] = None, return_path: bool = False, n_cep: int = 13):
+        """How close every synthesized request is to the recording it should resemble: request i is synthesized through the path
+        ``inference_ids`` uses (same planning, batching, controls and denoiser) and compared with row i of ``recordings`` [R, n] (float32
+        in [-1, 1] or int16 PCM; numpy or torch, host or GPU; ``recording_lens`` [R] samples).  Both sides go down to log-mel and f0 on the
+        GPU -- the recordings through the chain ``align_audio`` uses (``wav_rate``, ``condition``: as there), the synthesized PCM through
+        the same mel front-end and pitch tracker at the model's rate -- and e2e_tts_amd.compare aligns them (``mode``, ``band``: as
+        ``Comparator.run``).  -> one dict per request, in request order: ``mcd_db`` (on DCT cepstra of this project's log-mel: not
+        comparable with SPTK / WORLD figures), ``mel_l1``, ``f0_rmse_hz``, ``f0_rmse_cents``, ``n_voiced_both``, ``n_vuv_mismatch``,
+        ``n_path``, ``dist_total``, ``status``.  Side A is the recording, side B the synthesized utterance."""
+        from .compare import Comparator
+        seqs = [list(q) for q in sequences]
+        if len(recordings) != len(seqs):
+            raise ValueError(f"{len(recordings)} recordings for {len(seqs)} sequences")
+        pcms, lengths, _ = self._synthesize_requests(seqs, speaker_id, pitch_control, energy_control, duration_control, denoise_strength, None)
+        n = [int(k) * self.hop_length for k in lengths]
+        synth = np.zeros((len(pcms), max(n)), np.int16)
+        for i, (pcm, k) in enumerate(zip(pcms, n)):
+            synth[i, :k] = pcm[:k]
+        m = self._recording_chain()
+        cmp_ = self.__dict__.get("_comparator")
+        if cmp_ is None or cmp_.n_cep != int(n_cep):
+            cmp_ = self._comparator = Comparator(self._dims.n_mel, int(n_cep), device=self._device_index)
+        fe, trk, ml = m.recording_features(recordings, recording_lens, wav_rate=wav_rate, condition=condition)
+        cmp_.set_a(fe, ml, trk)
+        fe, trk, ml = m.recording_features(synth, np.asarray(n, np.int64))
+        cmp_.set_b(fe, ml, trk)
+        return cmp_.run(mode, band, return_path)
+
+    def evaluate(self, texts: list, recordings, recording_lens, speaker_id, **kwargs):
+        """``evaluate_ids`` from texts: one recording per text.  A text that ``arrange_text`` would cut into pieces is refused: a
+        recording is compared with one utterance."""
+        if isinstance(texts, str):
+            texts = [texts]
+        if self.text_to_sequence is None:
+            raise RuntimeError("TTS was built without a text front-end: pass text_to_sequence=... or call evaluate_ids()")
+        pieces, owners = self.arrange_text_owners(texts, self.max_len)
+        if len(pieces) != len(texts):
+            raise ValueError("a text is cut into several utterances (arrange_text): evaluate it piece by piece, one recording per piece")
+        return self.evaluate_ids([list(self.text_to_sequence(t)) for t in pieces], recordings, recording_lens, speaker_id, **kwargs)
 
     def inference(self, texts: list, speaker_id, pitch_control=1.0, energy_control=1.0, duration_control=1.0,
                   silence_distance: float = 0.5, denoise_strength: float = 0.0, output_rate: Optional[int] = None) -> np.ndarray:

@@ -320,6 +320,58 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         c.apply(gain, want=("pcm",), fetch=False)
         return c.resident()[0], a["n_out"].astype(np.int64), c.hip_stream()
 
+    def _recording_input(self, wavs, wl, stft, wav_rate, condition):
+        """The samples the mel front-end of ``stft`` is handed for recordings ``wavs`` of ``wl`` samples: after ``condition`` and / or
+        ``wav_rate`` they lie resident in the stage before, and the front-end's stream is ordered after that stage's.
+        -> (samples, their lengths, that stage's stream or None)."""
+        fe = stft.frontend
+        after = None
+        if condition is not None:
+            x, wl, after = self._conditioned(wavs, wl, stft, wav_rate, condition)
+            fe._call("order_after", after)                          # the mel's stream after the conditioner's
+            wav_rate = None
+        else:
+            x = stft._audio(wavs)
+        if wav_rate is not None and int(wav_rate) != int(stft.sampling_rate):
+            from .resample import Resampler
+            cache = self.__dict__.setdefault("_resamplers", {})
+            key = (int(wav_rate), int(stft.sampling_rate), self._device)
+            if key not in cache:
+                cache[key] = Resampler(key[0], key[1], device=self._device)
+            rsm = cache[key]
+            wl = rsm.forward(x, n_valid=wl, want=())["n_out"]   # raises ValueError on a bad length before anything is enqueued
+            x = rsm.resident()[0]                                # [B, width] float32 in the resampler's HBM, until its next forward
+            after = rsm.hip_stream()
+            fe._call("order_after", after)                       # the mel's stream after the resampler's
+        return x, wl, after
+
+    def recording_features(self, wavs, wav_lens, stft=None, wav_rate=None, condition=None, with_f0=True):
+        """Recordings down to mel and f0, through the chain ``align_audio`` uses (``condition``, ``wav_rate``, the mel front-end) and the
+        pitch tracker on the same samples, everything left where it lies on the device.  -> (the ``MelFrontend`` holding the log-mel
+        [B, T, n_mel] resident, the ``PitchTracker`` holding the f0 track [B, T] resident or None, mel_lens [B] int64): what
+        ``compare.Comparator.set_a`` / ``set_b`` take.  Valid until the next call that uses this model's front-end or tracker."""
+        torch = _torch()
+        if stft is None:
+            stft = self._default_stft()
+        wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
+        x, wl, after = self._recording_input(wavs, wl, stft, wav_rate, condition)
+        fe = stft.frontend
+        r = fe.forward(x, wl, want=())
+        trk = None
+        if with_f0:
+            from .f0 import PitchTracker
+            key = (int(stft.sampling_rate), int(stft.hop_length), self._device)
+            cache = self.__dict__.setdefault("_trackers", {})
+            if key not in cache:
+                cache[key] = PitchTracker(key[0], key[1], device=self._device)
+            trk = cache[key]
+            if after:
+                trk.order_after_stream(after)
+            t = trk.forward(x, wl, want=())
+            if t["T"] != r["T"]:
+                raise RuntimeError(f"the pitch track has {t['T']} frames, the mel {r['T']}")
+        return fe, trk, np.asarray(r["mel_lens"], dtype=np.int64).reshape(-1)
+
     def _align_audio(self, speaker, texts, txt_lens, wavs, wav_lens, attn_prior, return_energy, stft, wav_rate, condition=None, tap=None):
         """``align_audio``'s work -> (its 4-tuple, the frame energies or None, the mel front-end's mel_lens [B] int64 on the host).
         ``tap``: a dict that receives what the mel front-end was handed -- "x" (the samples, resident in the stage before when there is
@@ -342,24 +394,7 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         spk = spk_table[sp].contiguous()
         fe = stft.frontend
         wl = np.asarray(torch.as_tensor(wav_lens).cpu(), dtype=np.int64).reshape(-1)
-        after = None
-        if condition is not None:
-            x, wl, after = self._conditioned(wavs, wl, stft, wav_rate, condition)
-            fe._call("order_after", after)                          # the mel's stream after the conditioner's
-            wav_rate = None
-        else:
-            x = stft._audio(wavs)
-        if wav_rate is not None and int(wav_rate) != int(stft.sampling_rate):
-            from .resample import Resampler
-            cache = self.__dict__.setdefault("_resamplers", {})
-            key = (int(wav_rate), int(stft.sampling_rate), self._device)
-            if key not in cache:
-                cache[key] = Resampler(key[0], key[1], device=self._device)
-            rsm = cache[key]
-            wl = rsm.forward(x, n_valid=wl, want=())["n_out"]   # raises ValueError on a bad length before anything is enqueued
-            x = rsm.resident()[0]                                # [B, width] float32 in the resampler's HBM, until its next forward
-            after = rsm.hip_stream()
-            fe._call("order_after", after)                       # the mel's stream after the resampler's
+        x, wl, after = self._recording_input(wavs, wl, stft, wav_rate, condition)
         if tap is not None:
             tap.update(x=x, lens=wl, after=after, stft=stft)
         energy = None
@@ -485,7 +520,20 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         the mel front-end reads -- after ``condition`` and / or ``wav_rate`` too --, its track lies on the mel grid, and the data
         loader's targets (``f0_targets`` with this model's stats and pitch_quantization) feed the pass where they lie.  That needs a
         use_uv model: one without takes pyworld's extract_pitch in the reference, which is out of scope, and raises ValueError.
-        -> ``forward``'s two tuples."""
+        -> ``forward``'s two tuples.
+
+        How close the teacher-forced ``mel_post`` (the second element of the first tuple, [B, T, n_mel] on the device) is to the
+        recording's own mel: both lie on one frame grid, so they are compared frame-synchronously, without a search
+        (e2e_tts_amd.compare, mode "sync")::
+
+            out, _ = model.forward_audio(speaker, texts, txt_lens, wavs, wav_lens)
+            fe, trk, mel_lens = model.recording_features(wavs, wav_lens)      # the recording's mel (and f0), resident
+            cmp = compare.Comparator(n_mel)
+            cmp.set_a(fe, mel_lens, trk)
+            cmp.set_b(out[1], out[7])                                        # mel_post, mel_lens
+            figures = cmp.run(mode="sync")                                   # mcd_db, mel_l1 per utterance
+
+        (``mcd_db`` there is on DCT cepstra of this project's log-mel, see include/e2etts_compare.h.)"""
         tap = None
         if isinstance(p_targets, str):
             if p_targets != "extract":
