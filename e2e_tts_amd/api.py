@@ -395,6 +395,39 @@ class TTS:
         cmp_.set_b(fe, ml, trk)
         return cmp_.run(mode, band, return_path)
 
+    def evaluate_vocoder(self, recordings, recording_lens, critic, wav_rate: Optional[int] = None, condition=None):
+        """Copy synthesis, judged as the reference judges a vocoder: every recording goes down to log-mel through the chain ``align_audio``
+        uses (``wav_rate``, ``condition``: as there), the mel goes through this checkpoint's vocoder, and ``critic`` (a loaded
+        ``e2e_tts_amd.critic.Critic`` on this device) compares the result with the recording the mel was made from, cut to
+        ``mel_len * hop`` samples: discriminator scores and the feature loss, sample-aligned (int16 recordings against the vocoder's int16
+        PCM, float32 ones against its float32 waveform).  Everything stays on the device: the
+        vocoder reads the front-end's resident mel, the critic reads the resident recording and the vocoder's output, its stream ordered
+        after theirs.  -> ``Critic.run``'s list of dicts, one per recording.  Separates "the vocoder is worse" from "the acoustic model
+        is worse", which ``evaluate_ids``' figures on log-mel cannot."""
+        import torch
+        m = self._recording_chain()
+        stft = m._default_stft()
+        wl = np.asarray(torch.as_tensor(recording_lens).cpu(), dtype=np.int64).reshape(-1)
+        x, wl, after = m._recording_input(recordings, wl, stft, wav_rate, condition)
+        fe = stft.frontend
+        r = fe.forward(x, wl, want=())
+        B, T = int(x.shape[0]), int(r["T"])
+        hop = self.hop_length
+        n = np.minimum(np.asarray(r["mel_lens"], np.int64).reshape(-1) * hop, np.asarray(wl, np.int64).reshape(-1))
+        # an int16 recording is compared with the vocoder's int16 PCM, a float32 one with its float32 waveform: one sample format per call
+        pcm = "int16" in str(x.dtype)
+        wav = torch.empty((B, T * hop), dtype=torch.int16 if pcm else torch.float32, device=torch.device("cuda", self._device_index))
+        import ctypes as C
+        eng, mel = self.engine, fe.resident()[0]
+        with eng.lock:   # e2etts_vocoder_btc on the front-end's HBM: the engine's stream after torch's (the output tensor) and after the front-end's
+            eng._order(wav)
+            eng._check(eng.lib.e2etts_order_after(eng._h, C.c_void_p(fe.stream())), "e2etts_order_after")
+            eng._check(eng.lib.e2etts_vocoder_btc(eng._h, mel.data_ptr(), B, T, None if pcm else wav.data_ptr(), wav.data_ptr() if pcm else None), "e2etts_vocoder")
+            critic.order_after_stream(eng.stream())
+        if after:
+            critic.order_after_stream(after)
+        return critic.run(x, n, wav, n)
+
     def evaluate(self, texts: list, recordings, recording_lens, speaker_id, **kwargs):
         """``evaluate_ids`` from texts: one recording per text.  A text that ``arrange_text`` would cut into pieces is refused: a
         recording is compared with one utterance."""

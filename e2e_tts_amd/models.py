@@ -1011,3 +1011,70 @@ def generate_melspecs(y, n_fft=1024, num_mels=80, sampling_rate=22050, hop_size=
     mel = torch.zeros((B, max(n // hop_size, 1), num_mels), dtype=torch.float32, device=stft.device)
     stft.frontend.forward(x, None, out_mel=mel, want=())
     return mel.transpose(1, 2).contiguous()
+
+
+class _Discriminators:
+    """What the two mirrors below share: one ``critic.Critic`` (both families live in one handle; a mirror made with ``critic=other.critic``
+    shares it), the state dicts until both are there, and the reference's ``forward(y, y_hat)``.
+
+    The library loads both families as one blob.  A mirror used ALONE therefore loads the other family with seeded stand-in weights
+    (``synth_critic_state(0)``): they cost device memory and the other family's launches, and nothing they compute is returned.  A forward
+    runs the whole critic once per side and materialises every map (``Critic.forward``), which come back through the host: the mirrors
+    are for parity checks against the reference's classes; ``Critic.run`` is the path for figures.  ``strict`` is accepted for signature
+    compatibility; missing or misshapen tensors are always an error (``packer.pack_critic``)."""
+    _family = ""
+
+    def __init__(self, config: Optional[dict] = None, device=None, critic=None):
+        from . import critic as cr
+        self.critic = critic if critic is not None else cr.Critic(config, _device_index(device))
+        self.training = False
+
+    def load_state_dict(self, state_dict: Mapping[str, object], strict: bool = True):
+        """Weights reach the device once both families' state dicts are known (the library packs them into one blob); a family that is
+        never loaded gets a seeded stand-in, so that one mirror can be used alone."""
+        self.critic._states[self._family] = state_dict
+        self.critic._loaded = False
+        return self
+
+    def eval(self):
+        return self
+
+    def _load(self):
+        c = self.critic
+        if not c._loaded:
+            from .synth_weights import synth_critic_state
+            stand_in = dict(zip(("mpd", "msd"), synth_critic_state(0, c.config)))
+            if self._family not in c._states:
+                raise RuntimeError(f"{type(self).__name__}: forward before load_state_dict")
+            c.load(c._states.get("mpd", stand_in["mpd"]), c._states.get("msd", stand_in["msd"]))
+
+    def forward(self, y, y_hat):
+        """y, y_hat [B, 1, T] -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs) as the reference returns them: per discriminator the flattened scores
+        [B, n] and the list of feature maps [B, C, T', p] / [B, C, T'], torch tensors on the GPU."""
+        torch = _torch()
+        self._load()
+        c = self.critic
+        dev = torch.device("cuda", c.device)
+        mine = [d for d, t in enumerate(c.tables) if t[0] == self._family]
+        out = []
+        for x in (y, y_hat):
+            x = torch.as_tensor(x, dtype=torch.float32)
+            if x.dim() != 3 or x.shape[1] != 1:
+                raise ValueError(f"expected samples of shape [B, 1, T], got {tuple(x.shape)}")
+            x = x.to(dev).contiguous()
+            c.forward(x, np.full(x.shape[0], x.shape[2], np.int64))
+            maps = [[torch.from_numpy(c.fmap(d, l)[0]).to(dev) for l in range(len(c.tables[d][2]))] for d in mine]
+            out.append(([m[-1].flatten(1, -1) for m in maps], maps))
+        return [s for s in out[0][0]], [s for s in out[1][0]], out[0][1], out[1][1]
+
+    __call__ = forward
+
+
+class MultiPeriodDiscriminator(_Discriminators):
+    """Mirror of the reference's ``MultiPeriodDiscriminator`` (V/discriminator.py:6-30) in eval(), on the critic library."""
+    _family = "mpd"
+
+
+class MultiScaleDiscriminator(_Discriminators):
+    """Mirror of the reference's ``MultiScaleDiscriminator`` (V/discriminator.py:33-62) in eval(), on the critic library."""
+    _family = "msd"

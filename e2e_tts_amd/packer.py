@@ -427,3 +427,107 @@ def pack_aligner_tensors(state_dict: Mapping[str, object], prefix: str = ALIGNER
 def pack_aligner(state_dict: Mapping[str, object], prefix: str = ALIGNER_PREFIX) -> np.ndarray:
     """The aligner's weights as a blob of their own, in build_blob's container; what pack() produces is unchanged."""
     return build_blob(pack_aligner_tensors(state_dict, prefix))
+
+
+# ---------------------------------------------------------------- the vocoder critic (include/e2etts_critic.h, csrc/critic/plan.h)
+def critic_effective_weight(sd: Mapping[str, object], prefix: str) -> np.ndarray:
+    """The weight a discriminator layer convolves with in eval(): weight_norm folded as the vocoder's is, or spectral_norm as the reference's
+    eval() computes it -- NO power iteration: w = weight_orig / sigma, sigma = u . (W_mat v) with the stored vectors, W_mat = weight_orig
+    as [Cout, -1], in torch's fp32 ops.  A non-finite or zero sigma is refused.  Conv2d weights [Cout, Cin, k, 1] come back as [Cout, Cin, k]."""
+    if prefix + ".weight_orig" in sd:
+        import torch
+        w = torch.as_tensor(_np(_need(sd, prefix + ".weight_orig"))).float()
+        u = torch.as_tensor(_np(_need(sd, prefix + ".weight_u", (w.shape[0],)))).float()
+        v = torch.as_tensor(_np(_need(sd, prefix + ".weight_v", (int(np.prod(w.shape[1:])),)))).float()
+        sigma = torch.dot(u, torch.mv(w.reshape(w.shape[0], -1), v))
+        if not np.isfinite(float(sigma)) or float(sigma) == 0.0:
+            raise ValueError(f"{prefix}: spectral norm sigma is {float(sigma)}")
+        out = (w / sigma).numpy()
+    else:
+        out = fold_weight_norm(_need(sd, prefix + ".weight_g"), _need(sd, prefix + ".weight_v"))
+    out = np.asarray(out, np.float32)
+    return out[..., 0] if out.ndim == 4 else out
+
+
+def stride_fold(w: np.ndarray, stride: int, pad: int):
+    """A dense convolution (w [Cout, Cin, k], stride s, padding pad) as a stride-1 convolution on the channels-last input [T, Cin] viewed as
+    [T / s, s * Cin]: q = ceil(pad / s), o = s q - pad, K' = ceil((o + k) / s); w'[n, j', f * Cin + c] = w[n, c, s j' + f - o] where that tap
+    exists, 0 elsewhere.  Returns (w' [Cout, K', s * Cin], q)."""
+    Cout, Cin, k = w.shape
+    s = int(stride)
+    q = -(-int(pad) // s)
+    o = s * q - int(pad)
+    kf = -(-(o + k) // s)
+    out = np.zeros((Cout, kf, s * Cin), np.float32)
+    for jf in range(kf):
+        for f in range(s):
+            j = s * jf + f - o
+            if 0 <= j < k:
+                out[:, jf, f * Cin:(f + 1) * Cin] = w[:, :, j]
+    return out, q
+
+
+def dense_splits(cin_f: int, kf: int) -> int:
+    """csrc/critic/plan.h: dense_splits -- the ranges the folded channel axis of a dense layer is cut into (whole 32-channel chunks, chains of
+    at least 128 terms, at most 8): one conv_gemm launch each, merged by a fixed tree."""
+    n = 8
+    while n > 1 and (cin_f % (32 * n) != 0 or cin_f * kf // n < 128):
+        n //= 2
+    return n
+
+
+def split_ranges(wf: np.ndarray) -> np.ndarray:
+    """Folded weights [Cout, K', Cin'] range by range, [n][Cout, K', Cin' / n]: every range is the whole weight matrix of its launch."""
+    Cout, kf, cf = wf.shape
+    n = dense_splits(cf, kf)
+    return np.ascontiguousarray(wf.reshape(Cout, kf, n, cf // n).transpose(2, 0, 1, 3))
+
+
+def group_fragments(w: np.ndarray, groups: int) -> np.ndarray:
+    """A grouped convolution's weights [Cout, Cin / groups, k] in the order the grouped kernel's wavefronts load them:
+    [group][32-column tile][tap][channel pair][lane], lane l holding w[group * Cout_g + tile * 32 + l % 32, 2 * pair + l // 32, tap], zeros
+    where the column is past Cout_g."""
+    Cout, cin_g, k = w.shape
+    cout_g = Cout // groups
+    ntp = -(-cout_g // 32)
+    wp = np.zeros((groups, ntp * 32, cin_g, k), np.float32)
+    wp[:, :cout_g] = w.reshape(groups, cout_g, cin_g, k)
+    f = wp.reshape(groups, ntp, 32, cin_g // 2, 2, k)        # g, tile, n, pair, half, tap
+    return np.ascontiguousarray(f.transpose(0, 1, 5, 3, 4, 2)).reshape(-1)   # g, tile, tap, pair, half, n  (lane = half * 32 + n)
+
+
+def pack_critic_tensors(state_mpd: Mapping[str, object], state_msd: Mapping[str, object], config=None) -> "OrderedDict[str, np.ndarray]":
+    """The reference's MultiPeriodDiscriminator / MultiScaleDiscriminator state dicts -> tensors `d<i>.l<l>.w / .b` of the critic library
+    (discriminators: the periods in the config's order, then the scales; l = n_layers is the post layer).  First layers [Cout, k], dense
+    layers stride-folded tap-major rows, one matrix per range of the K split, grouped layers in fragment order, post layers [k, Cin]."""
+    from .critic import default_config, disc_tables
+    cfg = default_config() if config is None else config
+    out: "OrderedDict[str, np.ndarray]" = OrderedDict()
+    for di, (kind, idx, layers) in enumerate(disc_tables(cfg)):
+        sd = {k: _np(v) for k, v in (state_mpd if kind == "mpd" else state_msd).items()}
+        cin = 1
+        for l, (cout, k, s, g, pad) in enumerate(layers):
+            post = l == len(layers) - 1
+            prefix = f"discriminators.{idx}." + ("conv_post" if post else f"convs.{l}")
+            w = critic_effective_weight(sd, prefix)
+            if w.shape != (cout, cin // g, k):
+                raise ValueError(f"{prefix}: weight of shape {w.shape}, the tables need {(cout, cin // g, k)}")
+            if not np.all(np.isfinite(w)):
+                raise ValueError(f"{prefix}: the folded weight is not finite")
+            if post:
+                t = np.ascontiguousarray(w[0].T)
+            elif l == 0:
+                t = w[:, 0, :]
+            elif g == 1:
+                t = split_ranges(stride_fold(w, s, pad)[0])
+            else:
+                t = group_fragments(w, g)
+            out[f"d{di}.l{l}.w"] = t
+            out[f"d{di}.l{l}.b"] = _need(sd, prefix + ".bias", (cout,))
+            cin = cout
+    return OrderedDict((k, np.ascontiguousarray(_np(v), dtype=np.float32).reshape(-1)) for k, v in out.items())
+
+
+def pack_critic(state_mpd: Mapping[str, object], state_msd: Mapping[str, object], config=None) -> np.ndarray:
+    """The critic's weights as a blob of their own, in build_blob's container; what pack() produces is unchanged."""
+    return build_blob(pack_critic_tensors(state_mpd, state_msd, config))
