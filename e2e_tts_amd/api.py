@@ -428,6 +428,22 @@ class TTS:
             critic.order_after_stream(after)
         return critic.run(x, n, wav, n)
 
+    def build_stats(self, recordings, recording_lens, wav_rate: Optional[int] = None, condition=None, batch: int = 32) -> dict:
+        """``stats.json`` of a corpus of recordings, as the reference's ``TextMelLoader.build_stats`` computes it from files on disk:
+        ``recordings`` [R, n] (float32 in [-1, 1] or int16 PCM; numpy or torch, host or GPU; ``recording_lens`` [R] samples) go through the
+        chain ``align_audio`` uses (``wav_rate``, ``condition``: as there), ``batch`` rows at a time, and the mel front-end's frame energies
+        and the pitch tracker's f0 are accumulated where they lie on the device (e2e_tts_amd.stats: the definition is
+        include/e2etts_stats.h).  -> ``{"f0": {mean, std}, "energy": {max, min, mean, std}}``, Python floats; no ``"pitch"`` block (the
+        reference's pyworld track is not built; see ``stats.CorpusStats.result``).  The result does not depend on ``batch``."""
+        from .models import build_stats
+        if int(batch) < 1:
+            raise ValueError("batch must be at least 1")
+        lens = np.asarray(recording_lens.cpu() if hasattr(recording_lens, "cpu") else recording_lens, dtype=np.int64).reshape(-1)
+        if len(recordings) != len(lens):
+            raise ValueError(f"{len(recordings)} recordings for {len(lens)} lengths")
+        batches = ((recordings[i:i + int(batch)], lens[i:i + int(batch)]) for i in range(0, len(lens), int(batch)))
+        return build_stats(self._recording_chain(), batches, wav_rate=wav_rate, condition=condition)
+
     def evaluate(self, texts: list, recordings, recording_lens, speaker_id, **kwargs):
         """``evaluate_ids`` from texts: one recording per text.  A text that ``arrange_text`` would cut into pieces is refused: a
         recording is compared with one utterance."""

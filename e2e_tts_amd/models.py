@@ -18,6 +18,10 @@ log-mel frames and frame energies -- is served by the mel library (include/e2ett
 The f0 track of a recording and the data loader's pitch targets -- the reference's ``extract_f0`` (parselmouth) and ``get_f0`` -- are
 served by the pitch library (include/e2etts_f0.h; unpinned against parselmouth): ``extract_f0``, ``f0_targets`` and
 ``UnsupervisedFastSpeech2.forward_audio(p_targets="extract")``.
+
+The corpus statistics every normalising link reads -- the reference's ``TextMelLoader.build_stats``, ``stats.json`` -- and the data
+loader's energy target are served by the statistics library (include/e2etts_stats.h): ``build_stats`` and
+``UnsupervisedFastSpeech2.forward_audio(e_targets="extract")``.
 """
 from __future__ import annotations
 
@@ -444,8 +448,10 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         if e_targets is not None:
             kw.update(energy=f32(e_targets))
         with eng.lock:
-            if after_stream:   # the engine's stream after the aligner's, as align_audio orders the aligner after the mel
-                eng._check(eng.lib.e2etts_order_after(eng._h, ctypes.c_void_p(after_stream)), "e2etts_order_after")
+            # the engine's stream after the aligner's, as align_audio orders the aligner after the mel (a tuple: after each of them)
+            for s in after_stream if isinstance(after_stream, tuple) else (after_stream,):
+                if s:
+                    eng._check(eng.lib.e2etts_order_after(eng._h, ctypes.c_void_p(s)), "e2etts_order_after")
             r = eng.acoustic_forced(ids, lens, spk, durations=dur.contiguous(), attn_soft=soft4[:, 0].contiguous() if soft else None,
                                     mel_lens=ml if soft else None, pitch_frames=True, energy_frames=True, T=T,
                                     want=("mel_lens", "log_d"), **kw)
@@ -520,6 +526,9 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         the mel front-end reads -- after ``condition`` and / or ``wav_rate`` too --, its track lies on the mel grid, and the data
         loader's targets (``f0_targets`` with this model's stats and pitch_quantization) feed the pass where they lie.  That needs a
         use_uv model: one without takes pyworld's extract_pitch in the reference, which is out of scope, and raises ValueError.
+        ``e_targets="extract"``: the energy targets are the data loader's ``(e - mean) / std`` (float32, ``stats["energy"]``) of the frame
+        energies the mel front-end has just left resident, made on the device (e2e_tts_amd.stats) and handed to the pass where they
+        lie; any other string raises ValueError.
         -> ``forward``'s two tuples.
 
         How close the teacher-forced ``mel_post`` (the second element of the first tuple, [B, T, n_mel] on the device) is to the
@@ -535,19 +544,52 @@ class UnsupervisedFastSpeech2(_EngineBacked):
 
         (``mcd_db`` there is on DCT cepstra of this project's log-mel, see include/e2etts_compare.h.)"""
         tap = None
+        extract_p = extract_e = False
         if isinstance(p_targets, str):
             if p_targets != "extract":
                 raise ValueError(f"p_targets must be None, targets, or 'extract' (got {p_targets!r})")
             if not self.config["variance"]["variance_embedding"]["use_uv"]:
                 raise ValueError("p_targets='extract' needs a use_uv model: the targets of a model without come from pyworld's extract_pitch "
                                  "in the reference, which this package does not restate")
+            extract_p = True
+        if isinstance(e_targets, str):
+            if e_targets != "extract":
+                raise ValueError(f"e_targets must be None, targets, or 'extract' (got {e_targets!r})")
+            es = self.stats.get("energy", {}) if isinstance(self.stats, Mapping) else {}
+            if "mean" not in es or "std" not in es:
+                raise ValueError("e_targets='extract' needs stats['energy']['mean'] and ['std'] (models.build_stats makes them from recordings)")
+            extract_e = True
+        if extract_p or extract_e:
             tap = {}
         attn_out, _, ml = self._align_audio(speaker, texts, txt_lens, wavs, wav_lens, attn_prior, False, None, wav_rate, condition, tap=tap)
         self._check_lengths(txt_lens, ml)
         T = int(attn_out[0].shape[2])
-        if tap is not None:
+        after = self._ensure_aligner()[0].encoder.stream()
+        if extract_p:
             p_targets = self._extracted_targets(tap, T)
-        return self._forced(speaker, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, self._ensure_aligner()[0].encoder.stream())
+        if extract_e:
+            e_targets, stats_stream = self._extracted_energy(tap["stft"].frontend, ml, T)
+            after = (after, stats_stream)
+        return self._forced(speaker, texts, txt_lens, attn_out, ml, T, p_targets, e_targets, step, after)
+
+    def _extracted_energy(self, fe, mel_lens, T):
+        """The data loader's energy target [B, T] on the device (get_prosody, src/tools/dataloader.py:179-183: ``(e - mean) / std`` in
+        float32, 0 beyond each length) from the frame energies the mel front-end's last forward left resident, with this model's
+        ``stats["energy"]``.  -> (the target, the stream it is enqueued on: the teacher-forced pass is ordered after it)."""
+        from .stats import CorpusStats
+        torch = _torch()
+        es = self.stats["energy"]
+        cache = self.__dict__.setdefault("_stats_handles", {})
+        if self._device not in cache:
+            cache[self._device] = CorpusStats(device=self._device)
+        st = cache[self._device]
+        energy = fe.resident()[1]
+        if int(energy.shape[1]) != T:
+            raise RuntimeError(f"the frame energies have {int(energy.shape[1])} frames, the mel {T}")
+        st.order_after_stream(fe.stream())                          # the statistics' stream after the mel's
+        out = torch.empty((len(mel_lens), T), dtype=torch.float32, device=torch.device("cuda", self._device))
+        st.normalize(energy, mel_lens, float(es["mean"]), float(es["std"]), out=out)
+        return out, st.hip_stream()
 
     def _extracted_targets(self, tap, T):
         """{"f0", "uv"} [B, T] on the device from the samples the mel front-end was handed."""
@@ -571,6 +613,20 @@ class UnsupervisedFastSpeech2(_EngineBacked):
         ve = self.config["variance"]["variance_embedding"]
         trk.targets(self.stats, ve["pitch_quantization"], out_f0=f0, out_uv=uv)
         return {"f0": f0, "uv": uv}
+
+
+def build_stats(model, batches, wav_rate=None, condition=None) -> dict:
+    """``stats.json`` of a corpus of recordings (the reference's ``TextMelLoader.build_stats``, src/tools/dataloader.py:106-151): every
+    ``(wavs, wav_lens)`` of ``batches`` goes through ``model.recording_features`` and its frame energies and f0 are accumulated on the
+    device (``stats.CorpusStats.add_recordings``).  -> ``CorpusStats.result()``; it does not depend on how the corpus was batched."""
+    from .stats import CorpusStats
+    st = CorpusStats(device=model._device)
+    try:
+        for wavs, wav_lens in batches:
+            st.add_recordings(model, wavs, wav_lens, wav_rate=wav_rate, condition=condition)
+        return st.result()
+    finally:
+        st.close()
 
 
 def f0_targets(f0_hz, stats: Mapping[str, object], pitch_quantization: str = "linear", pitch_eps: float = 0.000000001):
